@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the headline measurement: CVR-format SpMV on MI355X (BASELINE.json).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload webgoogle|livejournal|banded<rows>|rmat<scale>]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload webgoogle|livejournal|banded<rows>|rmat<scale>] [--dump-outputs DIR] [--full]
 
 With N > 1 and no torch.distributed environment the command starts itself once per GPU (python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ..., before anything touches the GPU) and relays rank 0's line; under
@@ -16,10 +16,14 @@ built its communicator and its first gather has been checked bit for bit against
 (gather of step k under the SpMV of step k+1), whichever 200 untimed steps show to be faster on this node.  Otherwise the same
 loop runs over torch.distributed.  The large workloads (banded<rows>, rmat<scale>: BASELINE.json configs[3], [4]) are built
 shard by shard on the GPU (cvr_amd/synth_dev.py) and handed to the library as device-resident CSR.
-Rank 0 prints ONE JSON line.  The roofline object prices the SpMV kernel alone (algorithmic bytes of SURVEY.md 8(d) / mean
-kernel time from HIP events on the launch stream); cpu_baseline is the unmodified reference built by oracle/Makefile into
-oracle/_ref/ (kind "reference"; the oracle's 8-lane OpenMP restatement, kind "port", when that binary is absent) on the host
-cores (rank 0, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up (a host-built matrix twice, as the timed steps have always followed: preprocess.warm),
+warms up, times the K steps (metric, value, ms_per_step: the wall time of one timed step), writes y of the last timed step if
+--dump-outputs is given, and prints the line.  Everything else is measured or checked with
+--full only: the roofline object, which prices the SpMV kernel alone (algorithmic bytes of SURVEY.md 8(d) / mean kernel time from HIP
+events on the launch stream, in launches of its own); the single-launch, value-dictionary-off, exchange-alone and copy-kernel figures;
+the check of y against the CSR loop and of the gathered vector across ranks; the other power-law shapes; and cpu_baseline, the
+unmodified reference built by oracle/Makefile into oracle/_ref/ (kind "reference"; the oracle's 8-lane OpenMP restatement, kind
+"port", when that binary is absent) on the host cores (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -513,6 +517,22 @@ def self_launch(args):
     sys.exit(r.returncode if r.returncode else (0 if line else 1))
 
 
+DUMP_LIMIT_BYTES = 60 << 20          # --dump-outputs writes at most this much
+
+
+def dump_outputs(d, y_t):
+    """--dump-outputs DIR: y of the last timed step (what a caller of the timed path receives; N > 1: the gathered vector, padding
+    removed) as DIR/y.npy, in the dtype the path computes in (fp32 or fp64).  A y larger than DUMP_LIMIT_BYTES is written as a fixed
+    sample: y at the sorted rows of DIR/y_rows.npy (float64, exact), drawn with seed 0 from the row count alone."""
+    os.makedirs(d, exist_ok=True)
+    y = y_t.cpu().numpy()
+    if y.nbytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(y), DUMP_LIMIT_BYTES // (y.itemsize + 8), replace=False))
+        np.save(os.path.join(d, "y_rows.npy"), rows.astype(np.float64))
+        y = y[rows]
+    np.save(os.path.join(d, "y.npy"), y)
+
+
 def _pre_times(info):
     """the preprocessing times of a handle (cvr_info): T_pre = analysis + conversion without the upload, as tools/compare_csr.py counts it"""
     return {"plan_s": info.plan_s, "probe_s": info.probe_s, "upload_s": info.upload_s, "convert_s": info.convert_s,
@@ -531,8 +551,12 @@ def main():
     ap.add_argument("--interleave", type=int, default=-1, help="interleaved chunks (cvr_options.interleave; -1 = the library's rule)")
     ap.add_argument("--partition", default="cost", choices=["cost", "nnz"], help="row shards balanced by predicted time (non-zeros + 1.25 per row: cvr_row_partition_cost) "
                     "or by non-zeros alone (the reference's rule)")
-    ap.add_argument("--other-workloads", default="auto", help="comma-separated shapes measured beside the headline in the same JSON line (N = 1, headline workload only); "
+    ap.add_argument("--other-workloads", default="auto", help="with --full: comma-separated shapes measured beside the headline in the same JSON line (N = 1, headline workload only); "
                     "auto = " + ",".join(OTHER_WORKLOADS) + " within a time box; none = skip")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: roofline and per-kernel figures, "
+                    "the parity guard, the other shapes, the CPU baseline (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes y of the last timed step to DIR/y.npy (a seeded sample beyond "
+                    f"{DUMP_LIMIT_BYTES >> 20} MiB, with its rows in DIR/y_rows.npy)")
     ap.add_argument("--two-streams", action="store_true", help="also report the throughput of independent SpMVs alternating on two streams "
                     "(off by default: concurrent kernels would distort a rocprofv3 kernel-time summary of this command)")
     ap.add_argument("--workload", default="webgoogle", help="webgoogle (the headline, default) | livejournal | orkut | wikitalk | banded[<rows>] | rmat[<scale>] (fp32)")
@@ -632,7 +656,8 @@ def main():
     info = A.info
     # The first cvr_create of a process also loads the code object and creates the library's streams (milliseconds); the preprocessing
     # times DESIGN section 5.7 / 5.11 and tools/compare_csr.py quote are those of a process that has done so.  Host workloads that build in
-    # a moment are therefore built a second time, untimed by the bench, and the JSON line carries both.
+    # a moment are therefore built a second time, untimed by the bench, and the JSON line carries both.  A plain run builds it too: the
+    # timed steps have always followed this second build's device work, and without it the headline's 1 000 steps read 0.3 % slower.
     warm_info = None
     if not (device_built or tune) and create_s < 2.0:
         t_w0 = time.perf_counter()
@@ -787,45 +812,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
-    # the SpMV kernel alone, HIP events on the launch stream (N > 1: this rank's shard, no gather)
-    def kernel_time(M, ybuf):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        # behind ~30 ms of untimed launches: after an idle spell the chip needs some ten milliseconds of work before a kernel takes its steady time (the headline
-        # behind a 20-step run: 20.93 us over the next 200 launches, 20.6 behind 1 000 steps -- what rocprofv3 averages over a whole run; profiles/r06_timed_region_20_steps.log)
-        n_w = max(args.warmup, min(2000, int(0.03 / max(wall / max(args.steps, 1), 1e-6))))
-        M.spmv_device(x.data_ptr(), ybuf.data_ptr(), sptr, repeat=n_w)
-        n_t = max(args.steps, 200)               # >= 100 timed back-to-back launches, whatever --steps says
-        a.record(stream)
-        M.spmv_device(x.data_ptr(), ybuf.data_ptr(), sptr, repeat=n_t)
-        b.record(stream)
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e-3 / n_t
-    kern_s = kernel_time(A, y)
-    xcheck("kernel_time")
-    gather_s = None
-    if sharded:                         # the exchange step alone, same message, same stream (reported beside the total)
-        e4, e5 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        def gather_once():
-            if comm is not None:
-                comm.all_gather(ybufs[0].data_ptr(), yalls[0].data_ptr(), max_rows, f32, sptr)
-            else:
-                shard.all_gather_y(ybufs[0], max_rows, out=yalls[0])
-        for _ in range(5):
-            gather_once()
-        e4.record(stream)
-        for _ in range(args.steps):
-            gather_once()
-        e5.record(stream)
-        torch.cuda.synchronize()
-        gather_s = e4.elapsed_time(e5) * 1e-3 / args.steps
-    # the same launches one by one, each between its own pair of events: median and minimum (SURVEY 8d asks for mean / median / min)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
-    for a, b in evs:
-        a.record(stream)
-        A.spmv_device(x.data_ptr(), y.data_ptr(), sptr)
-        b.record(stream)
-    torch.cuda.synchronize()
-    singles = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, yalls[last[0]][torch.from_numpy(pick).to(dev)] if sharded else y[:lrows])
+
     # throughput of independent SpMVs alternating on two streams with their own y (the per-launch floor of one overlaps the body
     # of the other); reported for information, never the value: the steps of the metric run one after the other.  A handle with
     # column panels keeps its partial sums in one buffer: one SpMV in flight at a time (include/cvr_amd.h), so no such figure.
@@ -842,98 +831,139 @@ def main():
             A.spmv_device(x.data_ptr(), pair[i & 1][1].data_ptr(), pair[i & 1][0])
         torch.cuda.synchronize()
         two = (time.perf_counter() - t0) / args.steps
-    kern_max_s = kern_s
-    if sharded:                         # the slowest rank's SpMV alone: what the job would run at without the exchange step
-        t = torch.tensor([kern_s], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        kern_max_s = float(t.item())
-    balg_local = synth.b_alg(lrows, ncols, lnnz, vbytes)
-    achieved = balg_local / kern_s / 1e9
-    streamed_local = int(info.image_bytes) + (ncols + lrows) * vbytes      # what this layout moves: image + x + y
 
-    # the same matrix with full values in the stream (value_dict = 0): separates the format from the compression of the 13
-    # distinct values the reference's loader gives a pattern file (spmv.cpp:417)
-    kern_nodict_s = None
-    if not sharded and not device_built and info.value_dict > 0 and not os.environ.get("CVR_BENCH_NO_DICT_OFF_RUN"):
-        try:
-            B = cvr_amd.CvrMatrix(lrows, ncols, lrp, lci, lva, device=local_rank, steps_per_chunk=args.steps_per_chunk, value_dict=0, col_panels=args.col_panels, interleave=args.interleave)
-            kern_nodict_s = kernel_time(B, torch.zeros(max(B.info.yext_elems, 1), dtype=tdt, device=dev))
-            B.close()
-        except Exception as e:
-            print(f"[bench] value_dict = 0 run failed: {e!r}", file=sys.stderr)
-
-    # parity guard on the timed configuration: y of the last step against the CSR loop (the reference's own self-check,
-    # spmv.cpp:1843-1850, 1916-1938): the product's host loop for host-built workloads, a torch fp64 loop on the rank's own
-    # shard for device-built ones
-    wrong = wrong_ref = -1
-    x_damaged = int(torch.count_nonzero(x[:ncols] != torch.from_numpy(synth.x_rand(ncols, np_dtype)).to(dev)).item())     # (the device reference below is made from this x)
-    if x_damaged:
-        print(f"[bench rank {rank}] x on the device differs from what was uploaded in {x_damaged} elements", file=sys.stderr)
-    if device_built:
-        from cvr_amd import synth_dev as D
-        yref_t, absy_t = D.csr_spmv_reference(lrp_t, lci_t, lva_t, x[:ncols])
-        tol_t = 1e-5 if f32 else 1e-12
-        if sharded:
-            # every rank checks the WHOLE gathered vector: the owners' references travel the same way as y (padded slices, all-gathered), so a
-            # rank's copy of another rank's slice is compared too -- the exchange is part of what is verified, not only the local SpMV
-            pad = torch.zeros(2 * max_rows, dtype=torch.float64, device=dev)
-            pad[:lrows] = yref_t
-            pad[max_rows: max_rows + lrows] = absy_t
-            allref = torch.zeros(world * 2 * max_rows, dtype=torch.float64, device=dev)
-            shard.all_gather_tensor(allref, pad)
+    if args.full:
+        # the SpMV kernel alone, HIP events on the launch stream (N > 1: this rank's shard, no gather)
+        def kernel_time(M, ybuf):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            # behind ~30 ms of untimed launches: after an idle spell the chip needs some ten milliseconds of work before a kernel takes its steady time (the headline
+            # behind a 20-step run: 20.93 us over the next 200 launches, 20.6 behind 1 000 steps -- what rocprofv3 averages over a whole run; profiles/r06_timed_region_20_steps.log)
+            n_w = max(args.warmup, min(2000, int(0.03 / max(wall / max(args.steps, 1), 1e-6))))
+            M.spmv_device(x.data_ptr(), ybuf.data_ptr(), sptr, repeat=n_w)
+            n_t = max(args.steps, 200)               # >= 100 timed back-to-back launches, whatever --steps says
+            a.record(stream)
+            M.spmv_device(x.data_ptr(), ybuf.data_ptr(), sptr, repeat=n_t)
+            b.record(stream)
             torch.cuda.synchronize()
-            allref = allref.view(world, 2, max_rows)
-            yg = yalls[last[0]].view(world, max_rows).to(torch.float64)
-            bad = torch.zeros(1, dtype=torch.int64, device=dev)
-            for p in range(world):
-                np_ = int(bounds[p + 1] - bounds[p])
-                bad += torch.count_nonzero((yg[p, :np_] - allref[p, 0, :np_]).abs() > tol_t * allref[p, 1, :np_] + 1e-300)
-            bad += x_damaged                                       # (a rank whose x is not the uploaded one fails the run whatever its y)
-            dist.all_reduce(bad, op=dist.ReduceOp.MAX)          # (the worst rank's count of wrong rows over the whole vector)
-        else:
-            yl = y[:lrows].to(torch.float64)
-            bad = torch.count_nonzero((yl - yref_t).abs() > tol_t * absy_t + 1e-300).to(torch.int64).reshape(1) + x_damaged
-        wrong = int(bad.item())
-    else:
-        yh = (yalls[last[0]][torch.from_numpy(pick).to(dev)] if sharded else y[:nrows]).cpu().numpy()
-        if rank == 0:
-            xh = synth.x_rand(ncols, np_dtype).astype(np.float64)          # (what was uploaded, not what the device holds now)
-            nt = len(os.sched_getaffinity(0))
-            yref = cvr_amd.csr_spmv_host(rp, ci, va.astype(np.float64), xh, nthreads=nt)
-            # rows off by more than tol * sum |a x| (1e-12 fp64, 1e-5 for the fp32 path, which has no reference
-            # counterpart), and beside it the reference's own criterion (abs 1e-3, spmv.cpp:1916-1938)
-            absy = cvr_amd.csr_spmv_host(rp, ci, np.abs(va).astype(np.float64), np.abs(xh), nthreads=nt)
-            tol = 1e-5 if f32 else 1e-12
-            wrong = int(np.count_nonzero(np.abs(yh.astype(np.float64) - yref) > tol * absy + (1e-30 if f32 else 1e-300)))
-            wrong_ref = int(cvr_amd.verdict(yh.astype(np.float64), yref, nrows))
-
-    # the exchange itself: every rank must hold the SAME gathered vector, and rank p's copy of slice p is the one its own check above
-    # covered -- so per slice, every rank's bits against the owner's (a 64-bit wrap-around sum of the slice's bit patterns)
-    gathered_mismatch = None
-    shard_sums = None
-    if sharded and device_built:          # what every rank built (the tests compare it with slices of the matrix built in one piece)
-        mine_s = [int(lrows), int(lnnz), int(lci_t.to(torch.int64).sum().item()), int((lva_t.to(torch.float64) * 1e6).round().to(torch.int64).sum().item())]
-        shard_sums = [None] * world
-        dist.all_gather_object(shard_sums, mine_s)
-    if sharded:
-        sizes = [int(bounds[p + 1] - bounds[p]) for p in range(world)]
-        mine = torch.stack([yalls[last[0]][p * max_rows: p * max_rows + sizes[p]].view(bits).to(torch.int64).sum() for p in range(world)])
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        tab = torch.stack([e.cpu() for e in every]).numpy()          # [rank][slice]
-        gathered_mismatch = int(sum(int(tab[r][p] != tab[p][p]) for r in range(world) for p in range(world)))
-        if gathered_mismatch and rank == 0:
-            print("[bench] gathered y differs between ranks: (rank, slice) pairs off: "
-                  + ", ".join(f"({r},{p})" for r in range(world) for p in range(world) if tab[r][p] != tab[p][p]), file=sys.stderr)
-    xcheck("verified")
-    if args.dump_y and os.environ.get("CVR_BENCH_DEBUG_DUMP") and sharded and device_built:
-        # (diagnostics, every rank: its shard's arrays hashed, its own y buffers, its reference, its copy of the gathered vector)
-        import hashlib
+            return a.elapsed_time(b) * 1e-3 / n_t
+        kern_s = kernel_time(A, y)
+        xcheck("kernel_time")
+        gather_s = None
+        if sharded:                         # the exchange step alone, same message, same stream (reported beside the total)
+            e4, e5 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            def gather_once():
+                if comm is not None:
+                    comm.all_gather(ybufs[0].data_ptr(), yalls[0].data_ptr(), max_rows, f32, sptr)
+                else:
+                    shard.all_gather_y(ybufs[0], max_rows, out=yalls[0])
+            for _ in range(5):
+                gather_once()
+            e4.record(stream)
+            for _ in range(args.steps):
+                gather_once()
+            e5.record(stream)
+            torch.cuda.synchronize()
+            gather_s = e4.elapsed_time(e5) * 1e-3 / args.steps
+        # the same launches one by one, each between its own pair of events: median and minimum (SURVEY 8d asks for mean / median / min)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 200))]
+        for a, b in evs:
+            a.record(stream)
+            A.spmv_device(x.data_ptr(), y.data_ptr(), sptr)
+            b.record(stream)
         torch.cuda.synchronize()
-        hs = [hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest() for t in (lrp_t, lci_t, lva_t)]
-        np.savez(args.dump_y + f".rank{rank}.npz", hashes=np.asarray(hs), y0=ybufs[0][:lrows].cpu().numpy(), y1=ybufs[1][:lrows].cpu().numpy(),
-                 yref=yref_t.cpu().numpy(), absy=absy_t.cpu().numpy(), yall0=yalls[0].cpu().numpy(), yall1=yalls[1].cpu().numpy(), last=np.asarray([last[0]]),
-                 x=x[:ncols].cpu().numpy())
+        singles = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+        kern_max_s = kern_s
+        if sharded:                         # the slowest rank's SpMV alone: what the job would run at without the exchange step
+            t = torch.tensor([kern_s], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            kern_max_s = float(t.item())
+        balg_local = synth.b_alg(lrows, ncols, lnnz, vbytes)
+        achieved = balg_local / kern_s / 1e9
+        streamed_local = int(info.image_bytes) + (ncols + lrows) * vbytes      # what this layout moves: image + x + y
+
+        # the same matrix with full values in the stream (value_dict = 0): separates the format from the compression of the 13
+        # distinct values the reference's loader gives a pattern file (spmv.cpp:417)
+        kern_nodict_s = None
+        if not sharded and not device_built and info.value_dict > 0 and not os.environ.get("CVR_BENCH_NO_DICT_OFF_RUN"):
+            try:
+                B = cvr_amd.CvrMatrix(lrows, ncols, lrp, lci, lva, device=local_rank, steps_per_chunk=args.steps_per_chunk, value_dict=0, col_panels=args.col_panels, interleave=args.interleave)
+                kern_nodict_s = kernel_time(B, torch.zeros(max(B.info.yext_elems, 1), dtype=tdt, device=dev))
+                B.close()
+            except Exception as e:
+                print(f"[bench] value_dict = 0 run failed: {e!r}", file=sys.stderr)
+
+        # parity guard on the timed configuration: y of the last step against the CSR loop (the reference's own self-check,
+        # spmv.cpp:1843-1850, 1916-1938): the product's host loop for host-built workloads, a torch fp64 loop on the rank's own
+        # shard for device-built ones
+        wrong = wrong_ref = -1
+        x_damaged = int(torch.count_nonzero(x[:ncols] != torch.from_numpy(synth.x_rand(ncols, np_dtype)).to(dev)).item())     # (the device reference below is made from this x)
+        if x_damaged:
+            print(f"[bench rank {rank}] x on the device differs from what was uploaded in {x_damaged} elements", file=sys.stderr)
+        if device_built:
+            from cvr_amd import synth_dev as D
+            yref_t, absy_t = D.csr_spmv_reference(lrp_t, lci_t, lva_t, x[:ncols])
+            tol_t = 1e-5 if f32 else 1e-12
+            if sharded:
+                # every rank checks the WHOLE gathered vector: the owners' references travel the same way as y (padded slices, all-gathered), so a
+                # rank's copy of another rank's slice is compared too -- the exchange is part of what is verified, not only the local SpMV
+                pad = torch.zeros(2 * max_rows, dtype=torch.float64, device=dev)
+                pad[:lrows] = yref_t
+                pad[max_rows: max_rows + lrows] = absy_t
+                allref = torch.zeros(world * 2 * max_rows, dtype=torch.float64, device=dev)
+                shard.all_gather_tensor(allref, pad)
+                torch.cuda.synchronize()
+                allref = allref.view(world, 2, max_rows)
+                yg = yalls[last[0]].view(world, max_rows).to(torch.float64)
+                bad = torch.zeros(1, dtype=torch.int64, device=dev)
+                for p in range(world):
+                    np_ = int(bounds[p + 1] - bounds[p])
+                    bad += torch.count_nonzero((yg[p, :np_] - allref[p, 0, :np_]).abs() > tol_t * allref[p, 1, :np_] + 1e-300)
+                bad += x_damaged                                       # (a rank whose x is not the uploaded one fails the run whatever its y)
+                dist.all_reduce(bad, op=dist.ReduceOp.MAX)          # (the worst rank's count of wrong rows over the whole vector)
+            else:
+                yl = y[:lrows].to(torch.float64)
+                bad = torch.count_nonzero((yl - yref_t).abs() > tol_t * absy_t + 1e-300).to(torch.int64).reshape(1) + x_damaged
+            wrong = int(bad.item())
+        else:
+            yh = (yalls[last[0]][torch.from_numpy(pick).to(dev)] if sharded else y[:nrows]).cpu().numpy()
+            if rank == 0:
+                xh = synth.x_rand(ncols, np_dtype).astype(np.float64)          # (what was uploaded, not what the device holds now)
+                nt = len(os.sched_getaffinity(0))
+                yref = cvr_amd.csr_spmv_host(rp, ci, va.astype(np.float64), xh, nthreads=nt)
+                # rows off by more than tol * sum |a x| (1e-12 fp64, 1e-5 for the fp32 path, which has no reference
+                # counterpart), and beside it the reference's own criterion (abs 1e-3, spmv.cpp:1916-1938)
+                absy = cvr_amd.csr_spmv_host(rp, ci, np.abs(va).astype(np.float64), np.abs(xh), nthreads=nt)
+                tol = 1e-5 if f32 else 1e-12
+                wrong = int(np.count_nonzero(np.abs(yh.astype(np.float64) - yref) > tol * absy + (1e-30 if f32 else 1e-300)))
+                wrong_ref = int(cvr_amd.verdict(yh.astype(np.float64), yref, nrows))
+
+        # the exchange itself: every rank must hold the SAME gathered vector, and rank p's copy of slice p is the one its own check above
+        # covered -- so per slice, every rank's bits against the owner's (a 64-bit wrap-around sum of the slice's bit patterns)
+        gathered_mismatch = None
+        shard_sums = None
+        if sharded and device_built:          # what every rank built (the tests compare it with slices of the matrix built in one piece)
+            mine_s = [int(lrows), int(lnnz), int(lci_t.to(torch.int64).sum().item()), int((lva_t.to(torch.float64) * 1e6).round().to(torch.int64).sum().item())]
+            shard_sums = [None] * world
+            dist.all_gather_object(shard_sums, mine_s)
+        if sharded:
+            sizes = [int(bounds[p + 1] - bounds[p]) for p in range(world)]
+            mine = torch.stack([yalls[last[0]][p * max_rows: p * max_rows + sizes[p]].view(bits).to(torch.int64).sum() for p in range(world)])
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            tab = torch.stack([e.cpu() for e in every]).numpy()          # [rank][slice]
+            gathered_mismatch = int(sum(int(tab[r][p] != tab[p][p]) for r in range(world) for p in range(world)))
+            if gathered_mismatch and rank == 0:
+                print("[bench] gathered y differs between ranks: (rank, slice) pairs off: "
+                      + ", ".join(f"({r},{p})" for r in range(world) for p in range(world) if tab[r][p] != tab[p][p]), file=sys.stderr)
+        xcheck("verified")
+        if args.dump_y and os.environ.get("CVR_BENCH_DEBUG_DUMP") and sharded and device_built:
+            # (diagnostics, every rank: its shard's arrays hashed, its own y buffers, its reference, its copy of the gathered vector)
+            import hashlib
+            torch.cuda.synchronize()
+            hs = [hashlib.sha1(t.cpu().numpy().tobytes()).hexdigest() for t in (lrp_t, lci_t, lva_t)]
+            np.savez(args.dump_y + f".rank{rank}.npz", hashes=np.asarray(hs), y0=ybufs[0][:lrows].cpu().numpy(), y1=ybufs[1][:lrows].cpu().numpy(),
+                     yref=yref_t.cpu().numpy(), absy=absy_t.cpu().numpy(), yall0=yalls[0].cpu().numpy(), yall1=yalls[1].cpu().numpy(), last=np.asarray([last[0]]),
+                     x=x[:ncols].cpu().numpy())
     if args.dump_y and rank == 0:
         torch.cuda.synchronize()
         ydump = (yalls[last[0]][torch.from_numpy(pick).to(dev)] if sharded else y[:nrows]).cpu().numpy()
@@ -943,7 +973,7 @@ def main():
             np.save(args.dump_y + ".pick.npy", np.asarray(pick))
             np.save(args.dump_y + ".bounds.npy", np.asarray(bounds))
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:                      # achievable-HBM yardstick measured live: 1 GiB streaming copy, read + write
             from cvr_amd import capi
             copy_gbs = capi.device_copy_gbs(local_rank, 1 << 30, 20)
@@ -953,7 +983,6 @@ def main():
         per = wall / args.steps
         emu = bool(args.emulate_rank)
         job_nnz = lnnz if emu else nnz            # (an emulated rank: the flops of its shard)
-        kname = ("cvr::spmv_gang_kernel" if info.gang else "cvr::spmv_ilv_kernel" if info.interleave else "cvr::spmv_seg_kernel" if info.col_phases > 1 else "cvr::spmv_kernel") + ("<float>" if f32 else "<double>")      # (column phases: the kernel without hand-out state; interleaved chunks: the hand-pipelined one)
         workload_text = f"{source}: {nrows}x{ncols}, nnz {nnz}, {'fp32' if f32 else 'fp64'}, y = A x with A (CVR64 image), x, y resident in HBM"
         out = {
             "metric": "SpMV GFLOP/s (2*nnz/t), web-Google fp64" if args.workload == "webgoogle" else f"SpMV GFLOP/s (2*nnz/t), {args.workload} {'fp32' if f32 else 'fp64'}"
@@ -978,39 +1007,44 @@ def main():
                        "lds_bytes_per_workgroup": int(info.lds_bytes), "near_diagonal_share": float(info.near_diagonal_share),
                        "value_dictionary_entries": int(info.value_dict),
                        "parallelism": ("rows sharded, x replicated, y all-gathered (%s)" % ("RCCL" if backend == "nccl" else backend)) if sharded else "1 GPU"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, **(pmc_fields(info, kname, workload_text, lnnz) if world == 1 else {"traffic": None}),
-                         "achieved_is": "algorithmic bytes of SURVEY 8(d) (12 B per non-zero for fp64, whatever the image stores) / kernel time",
-                         "kernel": kname, "kernel_us": kern_s * 1e6,
-                         "kernel_us_median_single_launches": singles[len(singles) // 2] if singles else None, "kernel_us_min_single_launches": singles[0] if singles else None,
-                         "copy_kernel_gbs": copy_gbs, "frac_of_copy_kernel": achieved / copy_gbs if copy_gbs else None,
-                         # the boxes of the pool run stream-bound kernels in one of two modes ~17 % apart (profiles/r05_bimodal_probe.log); the copy kernel
-                         # lands in the same mode as the process's other streaming kernels: which one this line was taken in
-                         "box_mode": None if not copy_gbs else ("fast (copy kernel >= 5.6 TB/s)" if copy_gbs >= 5600 else "slow (copy kernel < 5.6 TB/s)"),
-                         "algorithmic_bytes_per_launch": int(balg_local),
-                         "streamed_bytes_per_launch": streamed_local, "streamed_gbs": streamed_local / kern_s / 1e9,
-                         "kernel_us_value_dict_off": None if kern_nodict_s is None else kern_nodict_s * 1e6,
-                         "frac_value_dict_off": None if kern_nodict_s is None else balg_local / kern_nodict_s / 1e9 / HBM_PEAK_GBS},
             "image_bytes": int(info.image_bytes),
             "gbs_alg_whole_job": synth.b_alg(lrows if emu else nrows, ncols, job_nnz, vbytes) / per / 1e9,
             "event_ms_per_step_rank0": ev_s / args.steps * 1e3,
             "timed_region_host_clock_us": timed_region_us,          # where the K steps' wall time goes beside K kernels: host time stamps from the start of the timed region
-            "spmv_only_ms_max_over_ranks": kern_max_s * 1e3, "gflops_spmv_only_no_exchange": 2.0 * job_nnz / kern_max_s / 1e9,
-            "rank0_spmv_only_ms": kern_s * 1e3, "rank0_allgather_only_ms": None if gather_s is None else gather_s * 1e3,
             "preprocess": {**_pre_times(info), "tune_s": A.tuning_s, "workload_build_s": build_s, "create_and_preprocess_wall_s": create_s,
                            "which": "the first cvr_create of the process (code object load, stream creation included)",
                            "warm": None if warm_info is None else {**_pre_times(warm_info), "create_and_preprocess_wall_s": warm_create_s,
                                                                     "which": "the same matrix built a second time in this process"}},
             "independent_spmvs_on_two_streams": None if two is None else {"ms_per_spmv": two * 1e3, "gflops": 2.0 * nnz / two / 1e9},
-            "gathered_slices_differing_between_ranks": gathered_mismatch, "shard_checksums": shard_sums,
-            "verdict_wrong_rows": wrong, "verdict_tolerance": "rows with |y - y_csr| > %g * sum |a x|" % (1e-5 if f32 else 1e-12),
-            "verdict_wrong_rows_reference_criterion_abs_1e-3": wrong_ref if wrong_ref >= 0 else None, "gather_impl": gather_impl, "gather_calibration_ms_per_step": calib,
+            "gather_impl": gather_impl, "gather_calibration_ms_per_step": calib,
             # what RCCL itself reports for the library's communicator (ncclCommCount / ncclCommUserRank / ncclGetVersion): a multi-GPU record shows that the collective saw N ranks
             "rccl": rccl_info,
         }
-        # the other power-law shapes, in this process, time-boxed (the default run must finish within minutes): each entry lets the
+        if args.full:
+            kname = ("cvr::spmv_gang_kernel" if info.gang else "cvr::spmv_ilv_kernel" if info.interleave else "cvr::spmv_seg_kernel" if info.col_phases > 1 else "cvr::spmv_kernel") + ("<float>" if f32 else "<double>")      # (column phases: the kernel without hand-out state; interleaved chunks: the hand-pipelined one)
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, **(pmc_fields(info, kname, workload_text, lnnz) if world == 1 else {"traffic": None}),
+                             "achieved_is": "algorithmic bytes of SURVEY 8(d) (12 B per non-zero for fp64, whatever the image stores) / kernel time",
+                             "kernel": kname, "kernel_us": kern_s * 1e6,
+                             "kernel_us_median_single_launches": singles[len(singles) // 2] if singles else None, "kernel_us_min_single_launches": singles[0] if singles else None,
+                             "copy_kernel_gbs": copy_gbs, "frac_of_copy_kernel": achieved / copy_gbs if copy_gbs else None,
+                             # MI355X machines were seen to run stream-bound kernels in one of two modes ~17 % apart (profiles/r05_bimodal_probe.log); the copy kernel
+                             # lands in the same mode as the process's other streaming kernels: which one this line was taken in
+                             "box_mode": None if not copy_gbs else ("fast (copy kernel >= 5.6 TB/s)" if copy_gbs >= 5600 else "slow (copy kernel < 5.6 TB/s)"),
+                             "algorithmic_bytes_per_launch": int(balg_local),
+                             "streamed_bytes_per_launch": streamed_local, "streamed_gbs": streamed_local / kern_s / 1e9,
+                             "kernel_us_value_dict_off": None if kern_nodict_s is None else kern_nodict_s * 1e6,
+                             "frac_value_dict_off": None if kern_nodict_s is None else balg_local / kern_nodict_s / 1e9 / HBM_PEAK_GBS},
+                "spmv_only_ms_max_over_ranks": kern_max_s * 1e3, "gflops_spmv_only_no_exchange": 2.0 * job_nnz / kern_max_s / 1e9,
+                "rank0_spmv_only_ms": kern_s * 1e3, "rank0_allgather_only_ms": None if gather_s is None else gather_s * 1e3,
+                "gathered_slices_differing_between_ranks": gathered_mismatch, "shard_checksums": shard_sums,
+                "verdict_wrong_rows": wrong, "verdict_tolerance": "rows with |y - y_csr| > %g * sum |a x|" % (1e-5 if f32 else 1e-12),
+                "verdict_wrong_rows_reference_criterion_abs_1e-3": wrong_ref if wrong_ref >= 0 else None,
+            })
+        # the other power-law shapes, in this process, time-boxed (the --full run must finish within minutes): each entry lets the
         # fractions be recomputed from nnz and kernel time
-        if world == 1 and args.workload == "webgoogle" and not args.emulate_rank and args.other_workloads != "none":
+        if args.full and world == 1 and args.workload == "webgoogle" and not args.emulate_rank and args.other_workloads != "none":
             names = OTHER_WORKLOADS if args.other_workloads == "auto" else tuple(v for v in args.other_workloads.split(",") if v)
             others, t_box = {}, time.perf_counter()
             A.close()
@@ -1023,7 +1057,7 @@ def main():
                 except Exception as e:
                     others[name] = {"error": repr(e)}
             out["other_workloads"] = others
-        if world == 1 and not args.no_cpu_baseline and not device_built:
+        if args.full and world == 1 and not args.no_cpu_baseline and not device_built:
             try:
                 out["cpu_baseline"] = cpu_baseline(nrows, ncols, rp, ci, va)
             except Exception as e:   # the checker is optional on the bench box; the GPU numbers stand without it

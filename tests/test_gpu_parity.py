@@ -1016,7 +1016,7 @@ def test_one_rank_of_the_eight_gpu_configurations(workload, rank):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--emulate-rank", rank, "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--emulate-rank", rank, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1628,7 +1628,7 @@ def test_bench_line_keeps_the_driver_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "60", "--warmup", "5"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "60", "--warmup", "5", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -1649,6 +1649,32 @@ def test_bench_line_keeps_the_driver_contract():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, (k, cb)
     assert cb["kind"] in ("reference", "port") and cb["value"] > 0 and cb["cores"] >= 1
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """python bench.py without --full: ONE line with the headline fields for exactly --steps timed steps and nothing that takes runs of its own;
+    --dump-outputs writes y of the last timed step, which the oracle checks row by row on the same seeded web-Google-shaped matrix and x"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["unit"] == "GFLOP/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 5105039 / (d["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "other_workloads", "verdict_wrong_rows"):
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["y.npy"]
+    y = np.load(out / "y.npy")
+    nrows, ncols, rp, ci, va = synth.web_google_like()
+    assert y.shape == (nrows,) and y.dtype == np.float64
+    yref, absy = O.csr_spmv64(rp, ci, va, synth.x_rand(ncols))
+    _assert_close(y, yref, absy, TOL64, "bench.py --dump-outputs")
 
 
 def test_minimal_c_example_builds_and_runs():
@@ -1678,7 +1704,7 @@ def test_bench_starts_itself_for_two_ranks_on_one_device():
     env = dict(os.environ, CVR_BENCH_ONE_DEVICE="1", CVR_BENCH_NO_TUNE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--full"], capture_output=True, text=True,
                        timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1706,7 +1732,7 @@ def test_bench_eight_ranks_on_one_device(workload, tmp_path):
         env.pop(k, None)
     ypath = str(tmp_path / "y.npy")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "10", "--warmup", "2", "--workload", workload, "--no-cpu-baseline",
-                        "--dump-y", ypath], capture_output=True, text=True, timeout=1200, env=env)
+                        "--dump-y", ypath, "--full"], capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1788,7 +1814,7 @@ def test_bench_device_built_workload():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "rmat20", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "rmat20", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

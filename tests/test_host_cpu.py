@@ -470,3 +470,28 @@ def test_bench_cpu_baseline_respects_the_cgroup_quota(monkeypatch, tmp_path):
     assert bench._cpu_quota() == 2
     files["/sys/fs/cgroup/cpu/cpu.cfs_quota_us"] = "-1\n"
     assert bench._cpu_quota() is None
+
+
+def test_bench_dump_outputs_keeps_dtype_and_samples_beyond_the_limit(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: y as it is (fp32 / fp64) while it fits the limit; beyond it a sample at rows drawn with a fixed seed from the
+    row count alone, the rows beside it (float64), the whole within the limit, the same sample in every run"""
+    import importlib
+    import sys
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    for dt in (torch.float32, torch.float64):
+        y = torch.linspace(-1, 1, 1000, dtype=dt)
+        bench.dump_outputs(str(tmp_path / "small"), y)
+        got = np.load(tmp_path / "small" / "y.npy")
+        assert got.dtype == y.numpy().dtype and np.array_equal(got, y.numpy())
+    assert not (tmp_path / "small" / "y_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    y = torch.from_numpy(np.random.default_rng(5).random(10_000))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), y)
+    ya, ra = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "a" / "y_rows.npy")
+    assert ya.dtype == np.float64 and ra.dtype == np.float64 and ya.nbytes + ra.nbytes <= 4096
+    assert len(ra) == 4096 // 16 and np.all(np.diff(ra) > 0) and ra[-1] < 10_000
+    assert np.array_equal(ya, y.numpy()[ra.astype(np.int64)])
+    assert np.array_equal(ra, np.load(tmp_path / "b" / "y_rows.npy")) and np.array_equal(ya, np.load(tmp_path / "b" / "y.npy"))

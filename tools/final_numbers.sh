@@ -5,7 +5,7 @@
 TAG=${1:-r04}; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/${TAG}_final_numbers.log; [ -n "$2" ] || : > $OUT
 for w in ${2:-webgoogle livejournal orkut wikitalk rmat22 rmat24 rmat26 banded3.5e6 banded28e6}; do
   extra=""; steps=200; case $w in banded28e6|rmat26) steps=50;; esac          # (the two 8-GPU configurations whole on one GPU)
-  python3 $R/bench.py --workload $w --steps $steps --warmup 20 --no-cpu-baseline --other-workloads none $extra 2>/dev/null | python3 -c "
+  python3 $R/bench.py --workload $w --steps $steps --warmup 20 --no-cpu-baseline --other-workloads none --full $extra 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if not l.startswith('{'): continue

@@ -5,7 +5,7 @@ TAG=${1:-r06}; R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 export TMPDIR=/tmp
 SECONDS=0
 timeout 3000 python3 -m pytest tests -x -q -m gpu > $OUT/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc $? ${SECONDS}s"; tail -4 $OUT/${TAG}_pytest_gpu.log
-timeout 900 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench: ${SECONDS}s"; cut -c1-300 $OUT/${TAG}_bench.json
+timeout 900 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench: ${SECONDS}s"; cut -c1-300 $OUT/${TAG}_bench.json
 bash tools/profile_bench.sh ${TAG}_bench > $OUT/${TAG}_profile_bench.log 2>&1; tail -3 $OUT/${TAG}_profile_bench.log
 bash tools/profile_bench.sh ${TAG}_bench_livejournal --workload livejournal > $OUT/${TAG}_profile_bench_lj.log 2>&1; tail -3 $OUT/${TAG}_profile_bench_lj.log
 bash tools/profile_bench.sh ${TAG}_bench_orkut --workload orkut > $OUT/${TAG}_profile_bench_orkut.log 2>&1; tail -3 $OUT/${TAG}_profile_bench_orkut.log

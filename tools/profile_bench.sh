@@ -11,13 +11,13 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export CVR_BENCH_NO_DICT_OFF_RUN=1        # one SpMV configuration per profiled process
-CMD="python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --other-workloads none $ARGS"
+CMD="python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --other-workloads none --full $ARGS"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/bench_traced.json 2> $OUT/trace.err
 cp $OUT/trace/*/*kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" "TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum" "TCC_BUBBLE_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_DRAM_sum TCC_EA0_RDREQ_LEVEL_sum"; do
   i=$((i+1))
-  SECONDS=0; timeout 400 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/pmc$i -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --other-workloads none $ARGS > $OUT/pmc$i.json 2> $OUT/pmc$i.err
+  SECONDS=0; timeout 400 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/pmc$i -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --other-workloads none --full $ARGS > $OUT/pmc$i.json 2> $OUT/pmc$i.err
   echo "pmc pass $i ($grp): ${SECONDS}s"
 done
 python3 - <<PY

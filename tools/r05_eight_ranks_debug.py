@@ -9,7 +9,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 env = dict(os.environ, CVR_BENCH_ONE_DEVICE="1", CVR_BENCH_NO_TUNE="1", CVR_BENCH_DEBUG_DUMP="1")
 for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
     env.pop(k, None)
-r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "10", "--warmup", "2", "--workload", "rmat20", "--no-cpu-baseline", "--dump-y", "/tmp/y8.npy"],
+r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "10", "--warmup", "2", "--workload", "rmat20", "--no-cpu-baseline", "--dump-y", "/tmp/y8.npy", "--full"],
                    capture_output=True, text=True, timeout=900, env=env)
 d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 print({k: d.get(k) for k in ("verdict_wrong_rows", "gathered_slices_differing_between_ranks", "gather_impl")})

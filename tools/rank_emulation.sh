@@ -6,7 +6,7 @@
 W=${1:-rmat26}; N=${2:-8}
 OUT=gpurun_out/rank_emulation_$W; mkdir -p $OUT
 for r in $(seq 0 $((N-1))); do
-  python bench.py --workload $W --emulate-rank $r/$N --steps 100 --warmup 10 --no-cpu-baseline > $OUT/rank$r.json 2> $OUT/rank$r.err
+  python bench.py --workload $W --emulate-rank $r/$N --steps 100 --warmup 10 --no-cpu-baseline --full > $OUT/rank$r.json 2> $OUT/rank$r.err
 done
 python - <<PY
 import json, glob
