@@ -502,6 +502,17 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     // hipErrorInvalidValue after all of it)
     if (opt.interleave > 0 && opt.steps_per_chunk > cvr::kIlvMaxSteps)
         return fail(CVR_ERR_INVALID, "interleave = 1 takes steps_per_chunk <= %d (a chunk is sorted in one workgroup's LDS)", cvr::kIlvMaxSteps);
+    // several vectors at once (cvr_spmm_device): the plain layout, the one whose kernel has a k-wide form -- every other layout option off, and
+    // refused when the caller asked for it explicitly (value dictionary and narrow columns keep their own rules: they only change the decoding)
+    if (opt.nvec >= 2) {
+        const struct { const char *name; int32_t v; } conflict[] = {{"col_phases > 1", opt.col_phases > 1}, {"col_panels > 1", opt.col_panels > 1}, {"x_window > 0", opt.x_window > 0},
+                                                                    {"waves_per_block > 1", opt.waves_per_block > 1}, {"hub_table > 0", opt.hub_table > 0},
+                                                                    {"hub_reorder > 0", opt.hub_reorder > 0}, {"interleave > 0", opt.interleave > 0}, {"gang > 0", opt.gang > 0}};
+        for (const auto &c : conflict)
+            if (c.v) return fail(CVR_ERR_INVALID, "nvec = %d builds the plain layout for cvr_spmm_device: %s conflicts with it", opt.nvec, c.name);
+        opt.col_phases = 0; opt.col_panels = 1; opt.x_window = 0; opt.waves_per_block = 1;
+        opt.hub_table = 0; opt.hub_reorder = 0; opt.interleave = 0; opt.gang = 0;
+    }
 
     // CSR arrays already in device memory (of opt.device): the row_ptr of a small matrix comes back once for the argument checks (8 B per
     // row), that of a large one is checked by a kernel and stays (R-MAT-24: 33 ms of copies -> 0.5 ms);

@@ -77,6 +77,8 @@ void make_key(ImgKey &k, const cvr_source_key *src, const IOpt &o, size_t vsz)
                           o.col_phases, o.hub_table, o.narrow_cols, o.hub_reorder, o.row_tags16, o.piece_max, o.debug_col_mask, o.interleave};
     static_assert(sizeof(ov) <= sizeof(k.opt), "options fit the key");
     memcpy(k.opt, ov, sizeof(ov));
+    // (slot 16, zero before: a key of nvec 0 / 1 is the key images were saved under before the option existed)
+    k.opt[16] = o.nvec >= 2 ? o.nvec : 0;
     k.cus = o.cus; k.xcds = o.xcds;
     snprintf(k.lib, sizeof(k.lib), "%s", cvr_version());
 }

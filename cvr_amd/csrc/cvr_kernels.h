@@ -236,6 +236,11 @@ hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, h
                        uint32_t multi_rounds = 1,
                        const IterEpilogue *epi = nullptr, const FuseArgs *fuse = nullptr, void *y_fused = nullptr);
 size_t     spmv_lds_bytes(const DeviceImage &img);      // dynamic LDS of that launch
+// Several vectors (cvr_spmm_device): Y = A X over an image of the plain layout (spmm_plain), X / Y row-major with leading dimensions ldx / ldy (in values),
+// blocks of up to kSpmmBlock vectors per launch, then the cut rows' fix-up per vector.  hipErrorInvalidValue for another layout or an X beyond 4 GiB.
+constexpr int kSpmmBlock = 8;
+bool       spmm_plain(const DeviceImage &img);
+hipError_t launch_spmm(const DeviceImage &img, const void *X, int64_t ldx, void *Y, int64_t ldy, int32_t nvec, hipStream_t st);
 
 // column panels: one fix-up launch for all panels (each with its own y_ext inside the partial-sum buffer)
 struct FixPart { const int64_t *shared; void *yext; uint32_t nshared, nrows; };

@@ -436,6 +436,203 @@ __global__ __launch_bounds__(MW ? kLanes * kMaxWavesPerBlock : kLanes) void spmv
     }
 }
 
+// ---- several vectors: the plain kernel k-wide (cvr_spmm_device) ---------------------------------------------------------------
+// spmv_kernel of the plain layout (one chunk per wavefront, no LDS table of x) with KB accumulators per lane.  The stream, the
+// descriptors, `target` and the hand-out / steal logic are the same instructions (they follow the column words alone); what changes:
+//   * the gather: per slot the KB values X[col * ldx + 0 .. KB) of the block, side by side -- 16-byte loads when the host has found the
+//     block's base and ldx aligned for them (WIDE), loads of one value otherwise; the pad slots read row ncols, which is zero;
+//   * every running sum, steal slot and staged row is KB values wide ([64][KB] slots, [ystage_n][KB] stage), and the staged rows leave
+//     as one stream of values (lane i writes value i of the chunk's rows: consecutive addresses when ldy == KB).
+// Each vector's FMAs, ds_adds and stores come in the order spmv_kernel has for it, so column j of Y is bit for bit spmv_kernel's y for
+// X[:, j].  Vectors nb .. KB of the block (nvec not a power of two) are summed from whatever X holds there and never stored.
+// Software pipeline as spmv_kernel's plain launch (the gather one group ahead, the stream two): one group of gathers is 4 KB values per
+// lane -- 64 VGPRs for KB = 8 fp64 -- and the kernel must not spill (tests/test_spmm_host.py checks the ISA).
+template <typename T, int KB> struct XK { T v[kGroupSteps][KB]; };
+
+template <typename T, int KB, bool WIDE>
+__device__ __forceinline__ XK<T, KB> gather_k(__amdgpu_buffer_rsrc_t rx, const u32x4 c, const uint32_t mask, const uint32_t ldxb)
+{
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef float    f32x2 __attribute__((ext_vector_type(2)));
+    constexpr int U = WIDE ? (KB * (int)sizeof(T) < 16 ? KB * (int)sizeof(T) : 16) : (int)sizeof(T);      // bytes per load
+    constexpr int PER = U / (int)sizeof(T);
+    XK<T, KB> r;
+#pragma unroll
+    for (int j = 0; j < kGroupSteps; j++) {
+        const uint32_t off = (col_of(c, j) & mask) * ldxb;
+#pragma unroll
+        for (int q = 0; q < KB / PER; q++) {
+            const uint32_t o = off + (uint32_t)(q * U);
+            if constexpr (U == 16) {
+                const u32x4 w = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, o, 0, kPolDefault));
+                if constexpr (sizeof(T) == 8) {
+                    const f64x2 d = __builtin_bit_cast(f64x2, w);
+                    r.v[j][2 * q] = d.x; r.v[j][2 * q + 1] = d.y;
+                } else {
+                    const f32x4 f = __builtin_bit_cast(f32x4, w);
+                    r.v[j][4 * q] = f.x; r.v[j][4 * q + 1] = f.y; r.v[j][4 * q + 2] = f.z; r.v[j][4 * q + 3] = f.w;
+                }
+            } else if constexpr (U == 8) {
+                const u32x2 w = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rx, o, 0, kPolDefault));
+                if constexpr (sizeof(T) == 8) {
+                    r.v[j][q] = __builtin_bit_cast(double, w);
+                } else {
+                    const f32x2 f = __builtin_bit_cast(f32x2, w);
+                    r.v[j][2 * q] = f.x; r.v[j][2 * q + 1] = f.y;
+                }
+            } else {
+                r.v[j][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, o, 0, kPolDefault));
+            }
+        }
+    }
+    return r;
+}
+
+template <typename T, int KB> struct ChunkStateK {
+    T        acc[KB];
+    uint32_t cur, fed, feeding, own, tail;      // as ChunkState
+};
+
+template <typename T, int KB>
+__device__ __forceinline__ void store_row_k(T *__restrict__ Y, size_t dst, uint64_t ldy, uint32_t nb, const T *v)
+{
+    T *const p = Y + dst * ldy;
+#pragma unroll
+    for (int j = 0; j < KB; j++)
+        if ((uint32_t)j < nb) store_y(p + j, v[j]);
+}
+
+// sum_group with KB vectors
+template <typename T, int KB, bool DICT>
+__device__ __forceinline__ void sum_group_k(ChunkStateK<T, KB> &s, const Group<T, DICT> &Q, const XK<T, KB> &xq, T *__restrict__ Y, uint64_t ldy, uint32_t nb,
+                                            T *slot_lane, uint32_t row_first, uint32_t nseg, uint32_t head_dest, uint32_t last_dest, const T *dict, T *ystage,
+                                            bool staged)
+{
+    T av[kGroupSteps];
+#pragma unroll
+    for (int j = 0; j < kGroupSteps; j++) av[j] = val_of<T, DICT>(Q, j, dict);
+#pragma unroll
+    for (int j = 0; j < kGroupSteps; j++) {
+        const uint32_t cw = col_of(Q.c, j);
+#pragma unroll
+        for (int v = 0; v < KB; v++) s.acc[v] = fma_t(av[j], xq.v[j][v], s.acc[v]);
+        const bool     fl = (cw & kEndBit) != 0;
+        const uint64_t m = __ballot(fl);
+        if (m) {
+            if (!s.tail) {
+                if (fl) {
+                    if (staged) {
+#pragma unroll
+                        for (int v = 0; v < KB; v++) ystage[s.cur * KB + v] = s.acc[v];
+                    } else {
+                        const uint32_t dst = s.cur == 0 ? head_dest : s.cur == nseg - 1 ? last_dest : row_first + s.cur;
+                        store_row_k<T, KB>(Y, dst, ldy, nb, s.acc);
+                    }
+#pragma unroll
+                    for (int v = 0; v < KB; v++) s.acc[v] = 0;
+                    const uint32_t nx = s.fed + lane_rank(m);
+                    if (nx < nseg) s.cur = nx; else s.feeding = 0;
+                }
+                s.fed = __builtin_amdgcn_readfirstlane(s.fed + (uint32_t)__popcll(m));
+                if (s.fed >= nseg) { s.fed = nseg; s.tail = 1; }
+            } else if (fl && s.feeding) {
+#pragma unroll
+                for (int v = 0; v < KB; v++) { slot_lane[v] = s.acc[v]; s.acc[v] = 0; }
+                s.feeding = 0;
+                s.own = 1;
+            }
+        }
+    }
+}
+
+// X: the block's first value (X + 8 b of the caller's); xbytes: what the descriptor may read from there; ldxb = ldx * sizeof(T).
+// Y: likewise; nb: vectors of the block that are stored (<= KB).  LDS: [64][KB] steal slots, [ystage_n][KB] staged rows, the dictionary.
+template <typename T, int KB, bool DICT, bool C16, bool WIDE>
+__global__ __launch_bounds__(kLanes) void spmm_kernel(const uint8_t *__restrict__ stream, const uint4 *__restrict__ desc, const uint8_t *__restrict__ target,
+                                                      const T *__restrict__ X, uint32_t xbytes, uint32_t ldxb, T *__restrict__ Y, uint64_t ldy, uint32_t nb, int G,
+                                                      uint32_t nchunks, uint32_t nblocks_per_xcd, int swz, uint32_t cmask, const T *__restrict__ dict_g, uint32_t ndict,
+                                                      uint32_t ystage_n, const uint32_t *__restrict__ cbase, uint32_t pad_col)
+{
+    constexpr int GB = DICT ? kGroupBytesDict : C16 ? (sizeof(T) == 8 ? kGroupBytes64C16 : kGroupBytes32C16) : sizeof(T) == 8 ? kGroupBytes64 : kGroupBytes32;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    T *const slots = reinterpret_cast<T *>(smem);
+    T *const ystage = slots + kLanes * KB;
+    T *const dict = ystage + (size_t)ystage_n * KB;
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t k = __builtin_amdgcn_readfirstlane(remap_block(blockIdx.x, nblocks_per_xcd, swz));
+    if (k >= nchunks) return;
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(X, xbytes);
+    const uint32_t voff = lane * 16;
+    T *const       slot_lane = slots + lane * KB;
+
+    constexpr int  QN = 2;                              // DEPTH = 1, QA = 1
+    const __amdgpu_buffer_rsrc_t rs = make_rsrc(stream + (size_t)k * ((size_t)G * GB), (uint32_t)G * GB);
+    Group<T, DICT> Q[QN];
+#pragma unroll
+    for (int i = 0; i < QN; i++) Q[i] = load_group<T, kPolDefault, DICT, C16>(rs, voff, (uint32_t)i * GB);
+    const uint4    d = desc[k];
+    const uint32_t cb = C16 ? cbase[k] : 0u;
+    if constexpr (DICT) {
+        for (uint32_t i = threadIdx.x; i < (uint32_t)kDictMax; i += blockDim.x) dict[i] = i < ndict ? dict_g[i] : T(0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+
+    const uint32_t row_first = d.x, nseg = d.y, head_dest = d.z, last_dest = d.w;
+    const uint32_t tg = target[(size_t)k * kLanes + lane];
+    ChunkStateK<T, KB> s;
+#pragma unroll
+    for (int v = 0; v < KB; v++) s.acc[v] = 0;
+    s.cur = lane;
+    s.fed = nseg < kLanes ? nseg : kLanes;
+    s.feeding = lane < s.fed;
+    s.own = 0;
+    s.tail = s.fed == nseg;
+    const bool staged = nseg <= ystage_n;
+    if constexpr (C16) Q[0].c = widen_cols(Q[0].c, cb, pad_col);
+    XK<T, KB> xs = gather_k<T, KB, WIDE>(rx, Q[0].c, cmask, ldxb);
+    for (int g = 0; g < G; g++) {
+        const Group<T, DICT> Qn = load_group<T, kPolDefault, DICT, C16>(rs, voff, (uint32_t)(g + QN) * GB);
+        if constexpr (C16) Q[1].c = widen_cols(Q[1].c, cb, pad_col);
+        const XK<T, KB> xn = gather_k<T, KB, WIDE>(rx, Q[1].c, cmask, ldxb);
+        sum_group_k<T, KB, DICT>(s, Q[0], xs, Y, ldy, nb, slot_lane, row_first, nseg, head_dest, last_dest, dict, ystage, staged);
+        Q[0] = Q[1];
+        Q[1] = Qn;
+        xs = xn;
+    }
+
+    // tail records: stolen partial sums go to the victim's slots (one ds_add per vector, lanes as in spmv_kernel), owners store
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    if (tg != lane) {
+#pragma unroll
+        for (int v = 0; v < KB; v++) __hip_atomic_fetch_add(&slots[tg * KB + v], s.acc[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (s.own) {
+        if (staged) {
+#pragma unroll
+            for (int v = 0; v < KB; v++) ystage[s.cur * KB + v] = slot_lane[v];
+        } else {
+            T own[KB];
+#pragma unroll
+            for (int v = 0; v < KB; v++) own[v] = slot_lane[v];
+            const uint32_t dst = s.cur == 0 ? head_dest : s.cur == nseg - 1 ? last_dest : row_first + s.cur;
+            store_row_k<T, KB>(Y, dst, ldy, nb, own);
+        }
+    }
+    if (staged) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        const uint32_t nout = nseg * KB;
+        for (uint32_t e = lane; e < nout; e += kLanes) {
+            const uint32_t i = e / KB, v = e % KB;
+            if (v < nb) {
+                const uint32_t dst = i == 0 ? head_dest : i == nseg - 1 ? last_dest : row_first + i;
+                store_y(Y + (size_t)dst * ldy + v, ystage[e]);
+            }
+        }
+    }
+}
+
 // ---- column phases: the kernel of the resident layout -------------------------------------------------------------------
 // With column phases the last column word of EVERY piece of a lane stream -- a (row, phase) segment, or what a lane stole of
 // one -- carries the chunk's row it belongs to (bits [col_bits, 31)), so a lane needs no state but its running sum: when a
@@ -1430,6 +1627,25 @@ __global__ __launch_bounds__(kLanes * kWavesPerBlock) void fixup_kernel(const in
     if (lane == 0) yext[row] = carry[2 * c0 + 1] + v;
 }
 
+// the same for the nb vectors of a block of cvr_spmm_device (rows of ldy values): vector by vector, each summed as fixup_kernel sums it
+template <typename T>
+__global__ __launch_bounds__(kLanes * kWavesPerBlock) void spmm_fixup_kernel(const int64_t *__restrict__ shared, uint32_t nshared, T *__restrict__ Y,
+                                                                             uint64_t ldy, uint32_t nb, uint32_t nrows)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t s = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (s >= nshared) return;
+    const int64_t row = shared[3 * (size_t)s], c0 = shared[3 * (size_t)s + 1], c1 = shared[3 * (size_t)s + 2];
+    const T      *carry = Y + (size_t)(nrows + 1) * ldy;
+    for (uint32_t j = 0; j < nb; j++) {
+        T v = 0;
+        for (int64_t c = c0 + 1 + lane; c <= c1; c += kLanes) v += carry[(size_t)(2 * c) * ldy + j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) Y[(size_t)row * ldy + j] = carry[(size_t)(2 * c0 + 1) * ldy + j] + v;
+    }
+}
+
 // column panels: a workgroup owns kCombineRows consecutive rows.  For every panel in turn it streams the panel's
 // partial sums of those rows (a contiguous range of the panel's y_ext: the panel's rows are sorted) together with their
 // row numbers and adds them into LDS accumulators; a row occurs at most once per panel, and a barrier separates the
@@ -1930,6 +2146,68 @@ hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, h
     const uint32_t fb = (img.nshared + kWavesPerBlock - 1) / kWavesPerBlock;
     with_real(img.f32, [&](auto real) { using T = decltype(real); hipLaunchKernelGGL(fixup_kernel<T>, dim3(fb), dim3(kLanes * kWavesPerBlock), 0, st, img.shared, img.nshared, static_cast<T *>(y_ext), img.nrows); });
     return hipGetLastError();
+}
+
+bool spmm_plain(const DeviceImage &img)
+{
+    return img.phases <= 1 && img.wpb <= 1 && img.win_elems == 0 && img.hub_n == 0 && img.order_n == 0 && !img.ilv && img.gang == 0 && !(img.c16 && img.dict);
+}
+
+// Row sums a wavefront of spmm_kernel stages: the image's stage (sized for its fullest chunk), as far as 20 KiB of LDS per workgroup allow -- the
+// kernel's registers leave room for two or three wavefronts per SIMD, and the LDS is not to lower that; chunks of more segments store directly.
+static uint32_t spmm_stage(const DeviceImage &img, int KB)
+{
+    const size_t  vs = img.f32 ? 4 : 8, budget = 20480 - (img.dict ? kDictMax * vs : 0);
+    const int64_t rows = (int64_t)(budget / (KB * vs)) - kLanes;
+    return (uint32_t)std::max<int64_t>(0, std::min<int64_t>(img.ystage, rows & ~(int64_t)63));
+}
+
+hipError_t launch_spmm(const DeviceImage &img, const void *X, int64_t ldx, void *Y, int64_t ldy, int32_t nvec, hipStream_t st)
+{
+    if (!spmm_plain(img) || nvec < 1 || ldx < nvec || ldy < nvec) return hipErrorInvalidValue;
+    const uint64_t vs = img.f32 ? 4 : 8;
+    if (((uint64_t)img.pad_col + 1) * (uint64_t)ldx * vs > 0xffffffffull) return hipErrorInvalidValue;      // X is addressed through a 32-bit buffer descriptor
+    if (img.nchunks == 0) return hipSuccess;
+    // the grid and block -> chunk mapping of launch_spmv's plain launch
+    const uint32_t nblocks = img.nchunks, per_xcd = (nblocks + 7) / 8;
+    const uint32_t run8 = img.xcd_swizzle >= 3 ? 8u << (img.xcd_swizzle - 2) : 0u;
+    const uint32_t grid = run8 ? (nblocks + run8 - 1) / run8 * run8 : img.xcd_swizzle == 2 ? ((per_xcd + 31) / 32) * 32 * 8 : img.xcd_swizzle ? per_xcd * 8 : nblocks;
+    const uint32_t per = img.xcd_swizzle == 1 || run8 ? nblocks : per_xcd;
+    for (int32_t b0 = 0; b0 < nvec; b0 += kSpmmBlock) {
+        const uint32_t nb = (uint32_t)std::min<int32_t>(kSpmmBlock, nvec - b0);
+        const int      KB = nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8;
+        const void    *Xb = static_cast<const uint8_t *>(X) + (size_t)b0 * vs;
+        void          *Yb = static_cast<uint8_t *>(Y) + (size_t)b0 * vs;
+        // wide gathers only where every one of them is aligned: the block's base and the row pitch multiples of the load's width
+        const uint64_t U = std::min<uint64_t>(16, (uint64_t)KB * vs);
+        const bool     wide = U > vs && reinterpret_cast<uintptr_t>(Xb) % U == 0 && ((uint64_t)ldx * vs) % U == 0;
+        const uint32_t xbytes = (uint32_t)(((uint64_t)img.pad_col * (uint64_t)ldx + nb) * vs);      // rows 0 .. ncols - 1 whole, of row ncols the block's nb values
+        const uint32_t ldxb = (uint32_t)((uint64_t)ldx * vs);
+        const uint32_t ys = spmm_stage(img, KB);
+        const size_t   lds = ((size_t)(kLanes + ys) * KB + (img.dict ? kDictMax : 0)) * vs;
+        with_real(img.f32, [&](auto real) {
+            using T = decltype(real);
+            const T *x = static_cast<const T *>(Xb), *dict = static_cast<const T *>(img.dict);
+            T       *y = static_cast<T *>(Yb);
+            auto go = [&](auto KBc) {
+                constexpr int K = decltype(KBc)::value;
+                with_flag(img.dict != nullptr, [&](auto DI) { with_flag(img.c16, [&](auto CS) { with_flag(wide, [&](auto WI) {
+                    constexpr bool kDict = decltype(DI)::value, kC16 = decltype(CS)::value, kWide = decltype(WI)::value;
+                    if constexpr (!(kDict && kC16) && !(kWide && K == 1))
+                        hipLaunchKernelGGL((spmm_kernel<T, K, kDict, kC16, kWide>), dim3(grid), dim3(kLanes), lds, st, img.stream, img.desc, img.target, x, xbytes, ldxb, y,
+                                           (uint64_t)ldy, nb, img.G, img.nchunks, per, img.xcd_swizzle, img.col_mask, dict, img.ndict, ys, img.cbase, img.pad_col);
+                }); }); });
+            };
+            if (KB == 1) go(std::integral_constant<int, 1>{}); else if (KB == 2) go(std::integral_constant<int, 2>{}); else if (KB == 4) go(std::integral_constant<int, 4>{}); else go(std::integral_constant<int, 8>{});
+            if (img.nshared) {
+                const uint32_t fb = (img.nshared + kWavesPerBlock - 1) / kWavesPerBlock;
+                hipLaunchKernelGGL(spmm_fixup_kernel<T>, dim3(fb), dim3(kLanes * kWavesPerBlock), 0, st, img.shared, img.nshared, y, (uint64_t)ldy, nb, img.nrows);
+            }
+        });
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // (cvr_create's warm-up thread: asking for a kernel's attributes makes the runtime load this file's code object, which the first launch would

@@ -117,7 +117,11 @@ typedef struct {
                                   order -- a token in LDS passes from unit to unit, so the sums are those of the CSR loop whatever the wavefronts'
                                   timing (bitwise reproducible) -- : four times the non-zeros share the lines of x a gather instruction touches.
                                   0 = off, 1 = on, <0 = auto (default): for interleaved column panels of four wavefronts per workgroup          */
-    int32_t reserved[3];       /* 0 */
+    int32_t nvec;              /* vectors the caller multiplies this matrix by at once (cvr_spmm_device).  0 / 1 (default): the layout rules as
+                                  above.  >= 2: the plain layout -- one chunk per workgroup, no window, column phases, column panels, hub table,
+                                  re-ordering, interleaved or gang chunks (value dictionary and narrow columns by their own rules) --, the one whose
+                                  kernel has a k-wide form; an explicit setting of any of those options beyond off is refused (CVR_ERR_INVALID) */
+    int32_t reserved[2];       /* 0 */
 } cvr_options;
 /* Automatic layout: with steps_per_chunk = 0, waves_per_block = 0, x_window < 0 and col_phases < 0 (the defaults) cvr_create
  * looks at the uploaded CSR on the device (are the rows sorted by column? which share of the non-zeros lies near the
@@ -213,6 +217,21 @@ int cvr_spmv(cvr_handle *h, const void *x_host, void *y_host, int iters, cvr_tim
 int cvr_spmv_device(cvr_handle *h, const void *x_dev, void *y_dev, void *stream);
 /* the same, `n` launches back to back (the Ntimes loop of spmv.cpp:1024 without a host round trip per launch) */
 int cvr_spmv_device_repeat(cvr_handle *h, const void *x_dev, void *y_dev, void *stream, int n);
+
+/* Several vectors at once: Y = A X for nvec vectors in one pass over the image (its stream, descriptors and `target` are read once
+ * for all of them, and every gather fetches the nvec values of a column that lie side by side).  X_dev: info.x_elems rows of ldx values
+ * (row-major; row c holds x_0[c] .. x_{nvec-1}[c]), the first nvec values of row ncols must be 0.  Y_dev: info.yext_elems rows of ldy
+ * values; the first nrows rows are Y, the rest is scratch (carry slots of cut rows, per vector).  Values at positions >= nvec of a row
+ * of Y are not written, values at positions >= nvec of a row of X are not used.  ldx >= nvec, ldy >= nvec; any alignment of the
+ * element type; (ncols + 1) * ldx values must stay within 4 GiB.  Blocks of up to 8 vectors per launch, all on `stream` (NULL = HIP's
+ * null stream); makes the handle's device current.  Every column j of Y is bit for bit what cvr_spmv_device computes for X[:, j].
+ * Handles whose image is not the plain layout (create them with cvr_options.nvec >= 2) take only nvec = 1 with ldx = ldy = 1, which
+ * is cvr_spmv_device; anything else is CVR_ERR_STATE.  Null pointers, nvec < 1, ld < nvec: CVR_ERR_INVALID before any device work. */
+int cvr_spmm_device(cvr_handle *h, const void *X_dev, int64_t ldx, void *Y_dev, int64_t ldy, int32_t nvec, void *stream);
+/* host X (ncols x nvec, row-major, ld = nvec) and Y (nrows x nvec): copies, one untimed warm-up, `iters` timed launches, as cvr_spmv */
+int cvr_spmm(cvr_handle *h, const void *X_host, void *Y_host, int32_t nvec, int iters, cvr_timing *timing);
+/* 1: the handle's image runs cvr_spmm_device for any nvec; 0: it only takes nvec = 1 with ldx = ldy = 1 (any layout) */
+int cvr_spmm_supported(const cvr_handle *h);
 /* The column-panel count cvr_create chooses for col_panels = -1 (host only, no device needed): 1 unless x is >= 24 MB
  * -- or >= 12 MB and the matrix is too large for the resident layout (more slots or rows than its workgroups hold in one pass) --
  * and the estimated share of x gathers missing a 4-MiB L2 (*l2_miss_estimate, sampled over eight windows of 65 536
