@@ -37,6 +37,16 @@ class Options(C.Structure):
                 ("col_panels", C.c_int32), ("value_dict", C.c_int32), ("col_phases", C.c_int32), ("hub_table", C.c_int32), ("narrow_cols", C.c_int32),
                 ("hub_reorder", C.c_int32), ("row_tags16", C.c_int32), ("row_bands", C.c_int32), ("piece_max", C.c_int32), ("interleave", C.c_int32), ("gang", C.c_int32), ("nvec", C.c_int32), ("reserved", C.c_int32 * 2)]
 
+    # cvr_options.mutable_values took reserved[0] in C (include/cvr_amd.h); the Python struct keeps the two-word `reserved` field of the
+    # same bytes, and the option reads and writes its first word
+    @property
+    def mutable_values(self):
+        return self.reserved[0]
+
+    @mutable_values.setter
+    def mutable_values(self, v):
+        self.reserved[0] = int(v)
+
 
 class Timing(C.Structure):
     _fields_ = [("iters", C.c_int32), ("mean_s", C.c_double), ("min_s", C.c_double), ("max_s", C.c_double),
@@ -63,7 +73,8 @@ class MmMatrix(C.Structure):
 
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
-           "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
+           "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
+           "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
            "cvr_tune_steps", "cvr_tune", "cvr_auto_panels", "cvr_power_iteration", "cvr_comm_unique_id", "cvr_comm_create", "cvr_comm_destroy", "cvr_comm_all_gather", "cvr_spmv_gather_repeat",
@@ -107,6 +118,9 @@ def lib():
         L.cvr_spmm_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_spmm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.POINTER(Timing)]
         L.cvr_spmm_supported.argtypes = [C.c_void_p]
+        L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
+        L.cvr_update_values_supported.argtypes = [C.c_void_p]
         for f in ("cvr_x_device", "cvr_y_device", "cvr_stream"):
             getattr(L, f).argtypes = [C.c_void_p]
             getattr(L, f).restype = C.c_void_p
@@ -360,8 +374,9 @@ class CvrMatrix:
     def __init__(self, nrows, ncols, row_ptr, col_idx, vals, device=0, steps_per_chunk=0, split_threshold=0,
                  xcd_swizzle=-1, x_window=-1, keep_csr=False, debug_col_mask=0,
                  col_panels=-1, value_dict=-1, tune_steps=False, waves_per_block=0, col_phases=-1, hub_table=-1, narrow_cols=-1, hub_reorder=-1,
-                 row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0):
-        """tune_steps: choose steps_per_chunk by measurement first (cvr_tune_steps; its cost is self.tuning_s).
+                 row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
+        """mutable_values=1: the handle takes new values of the same pattern later (update_values, update_values_device; no value dictionary).
+        tune_steps: choose steps_per_chunk by measurement first (cvr_tune_steps; its cost is self.tuning_s).
         nvec >= 2: the plain layout, for spmm() / spmm_device() with up to that many vectors at once (cvr_options.nvec).
         debug_col_mask is a profiling knob (tools/sweep.py): it travels through the environment (CVR_DEBUG_COL_MASK), not through cvr_options."""
         self._h = C.c_void_p()
@@ -380,7 +395,7 @@ class CvrMatrix:
         view = CsrView(nrows, ncols, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(self.f32))
         self._build(view, nrows, ncols, device, steps_per_chunk, split_threshold, xcd_swizzle, x_window, keep_csr,
                     debug_col_mask, col_panels, value_dict, tune_steps, waves_per_block, col_phases, hub_table, narrow_cols, hub_reorder,
-                    row_tags16, row_bands, piece_max, interleave, gang, nvec)
+                    row_tags16, row_bands, piece_max, interleave, gang, nvec, mutable_values)
 
     def save_image(self, path, key=None):
         """cvr_save_image: the converted image on disk, keyed by `key` (capi.source_key of the .mtx file; None = no source key),
@@ -390,7 +405,7 @@ class CvrMatrix:
             raise CvrError(rc, "cvr_save_image")
 
     @classmethod
-    def from_image(cls, path, key=None, device=0, nvec=0, **options):
+    def from_image(cls, path, key=None, device=0, nvec=0, mutable_values=0, **options):
         """cvr_load_image: a handle from a saved image (CvrError with code ERR_STATE when the file was written for another source,
         other options -- nvec among them --, another device geometry or library version)"""
         self = cls.__new__(cls)
@@ -400,6 +415,7 @@ class CvrMatrix:
         lib().cvr_default_options(C.byref(opt))
         opt.device = device
         opt.nvec = nvec
+        opt.mutable_values = mutable_values
         for k, v in options.items():
             setattr(opt, k, v)
         sec = C.c_double()
@@ -417,7 +433,7 @@ class CvrMatrix:
 
     @classmethod
     def from_device(cls, nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0, steps_per_chunk=0,
-                    split_threshold=0, keep_csr=False, col_panels=-1, value_dict=-1, tune_steps=False, hub_table=-1, hub_reorder=-1, interleave=-1, gang=-1, nvec=0):
+                    split_threshold=0, keep_csr=False, col_panels=-1, value_dict=-1, tune_steps=False, hub_table=-1, hub_reorder=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
         """CSR arrays already in the memory of `device` (raw pointers: int64 row_ptr[nrows+1], int32 col_idx, fp64/fp32 vals),
         e.g. the .data_ptr() of torch tensors: cvr_csr_view.arrays_on_device = 1"""
         self = cls.__new__(cls)
@@ -427,12 +443,12 @@ class CvrMatrix:
         self.dtype = np.float32 if self.f32 else np.float64
         view = CsrView(nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev, int(self.f32), 1)
         self._build(view, nrows, ncols, device, steps_per_chunk, split_threshold, -1, -1, keep_csr, 0, col_panels, value_dict, tune_steps,
-                    hub_table=hub_table, hub_reorder=hub_reorder, interleave=interleave, gang=gang, nvec=nvec)
+                    hub_table=hub_table, hub_reorder=hub_reorder, interleave=interleave, gang=gang, nvec=nvec, mutable_values=mutable_values)
         return self
 
     def _build(self, view, nrows, ncols, device, steps_per_chunk, split_threshold, xcd_swizzle, x_window, keep_csr,
                debug_col_mask, col_panels, value_dict, tune_steps, waves_per_block=0, col_phases=-1, hub_table=-1, narrow_cols=-1, hub_reorder=-1,
-               row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0):
+               row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
         opt = Options()
         lib().cvr_default_options(C.byref(opt))
         opt.device, opt.steps_per_chunk, opt.split_threshold = device, steps_per_chunk, split_threshold
@@ -442,6 +458,7 @@ class CvrMatrix:
         opt.interleave = interleave
         opt.gang = gang
         opt.nvec = nvec
+        opt.mutable_values = mutable_values
         # profiling knobs (tools/sweep.py): cvr_create / cvr_tune read them from the environment.  Only a knob the caller passed is
         # touched, and what the environment held before comes back once the handle exists (a value the user exported stays theirs).
         saved = {}
@@ -527,6 +544,24 @@ class CvrMatrix:
     def spmm_supported(self):
         """True: spmm_device takes any number of vectors (the plain layout); False: only one of stride 1"""
         return bool(lib().cvr_spmm_supported(self._h))
+
+    def update_values(self, vals):
+        """new values of the same pattern from host memory (cvr_update_values): vals indexed like the creation's vals (row_ptr[nrows]
+        elements); returns when the image holds them"""
+        vals = np.ascontiguousarray(vals, dtype=self.dtype)
+        rc = lib().cvr_update_values(self._h, vals.ctypes.data)
+        if rc:
+            raise CvrError(rc, "cvr_update_values")
+
+    def update_values_device(self, vals_ptr, stream=None):
+        """asynchronous update from a device array of the handle's device (cvr_update_values_device), ordered like spmv_device"""
+        rc = lib().cvr_update_values_device(self._h, vals_ptr, stream)
+        if rc:
+            raise CvrError(rc, "cvr_update_values_device")
+
+    def update_values_supported(self):
+        """True: the handle takes update_values / update_values_device (mutable_values, no kept CSR)"""
+        return bool(lib().cvr_update_values_supported(self._h))
 
     def spmv_gather(self, comm, x_ptr, y_ptrs, yall_ptrs, max_rows, steps, stream=None, overlap=False):
         """`steps` sharded SpMVs, each followed by the all-gather of this rank's y slice over RCCL, looped inside the

@@ -20,38 +20,48 @@ int fail(int code, const char *fmt, ...)
 
 
 
+// A buffer of the handle that every launch writes or reads (the panels' partial sums h->d_z; the hub table's compacted copy of x; the image of a
+// mutable handle, which cvr_update_values_device rewrites): a launch on ANOTHER stream must not start before the previous one is through with it.
+// The event is recorded when the stream CHANGES, on the stream of the launches before (behind their last pass), not after every SpMV: back-to-back
+// launches on one stream are ordered by the stream, and an event per SpMV is a packet between the combine pass and the next panel kernel
+// (profiles/r06_z_event.log).
+static bool event_per_spmv()
+{
+    static const bool on = cvr::debug_env("z_event_per_spmv");
+    return on;
+}
+hipError_t handle_enter(cvr_handle *h, hipStream_t st)
+{
+    if (!h->z_used) return hipSuccess;
+    if (event_per_spmv()) return hipStreamWaitEvent(st, h->z_free, 0);
+    if (h->z_stream == st) return hipSuccess;
+    // (stream capture: a dependency between a capturing stream and one outside the capture cannot be expressed -- and recording on the legacy stream would
+    //  end the capture; the graph's replays are ordered by the stream they are launched into.  Two streams of ONE capture do get their edge.)
+    hipStreamCaptureStatus cap_now = hipStreamCaptureStatusNone, cap_before = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap_now);
+    if (hipStreamIsCapturing(h->z_stream, &cap_before) != hipSuccess) { (void)hipGetLastError(); cap_before = hipStreamCaptureStatusNone; }
+    if ((cap_now == hipStreamCaptureStatusActive) != (cap_before == hipStreamCaptureStatusActive)) return hipSuccess;
+    if (hipEventRecord(h->z_free, h->z_stream) != hipSuccess) {      // (that stream was destroyed meanwhile: whatever it still runs is waited for the blunt way)
+        (void)hipGetLastError();
+        return hipDeviceSynchronize();
+    }
+    return hipStreamWaitEvent(st, h->z_free, 0);
+}
+hipError_t handle_leave(cvr_handle *h, hipStream_t st)
+{
+    h->z_used = true;
+    h->z_stream = st;
+    return event_per_spmv() ? hipEventRecord(h->z_free, st) : hipSuccess;
+}
+
 // y_ext = A x for the whole handle on `st`: one SpMV launch, or one per column panel followed by the combine
 hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st)
 {
-    // A buffer of the handle that every SpMV writes and reads (the panels' partial sums h->d_z; the hub table's compacted copy of x): a launch on ANOTHER stream
-    // must not start before the previous one is through with it.  The event is recorded when the stream CHANGES, on the stream of the launches before (behind
-    // their last pass), not after every SpMV: back-to-back launches on one stream are ordered by the stream, and an event per SpMV is a packet between the
-    // combine pass and the next panel kernel (profiles/r06_z_event.log).
-    static const bool event_per_spmv = cvr::debug_env("z_event_per_spmv");
-    auto enter = [&]() -> hipError_t {
-        if (!h->z_used) return hipSuccess;
-        if (event_per_spmv) return hipStreamWaitEvent(st, h->z_free, 0);
-        if (h->z_stream == st) return hipSuccess;
-        // (stream capture: a dependency between a capturing stream and one outside the capture cannot be expressed -- and recording on the legacy stream would
-        //  end the capture; the graph's replays are ordered by the stream they are launched into.  Two streams of ONE capture do get their edge.)
-        hipStreamCaptureStatus cap_now = hipStreamCaptureStatusNone, cap_before = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap_now);
-        if (hipStreamIsCapturing(h->z_stream, &cap_before) != hipSuccess) { (void)hipGetLastError(); cap_before = hipStreamCaptureStatusNone; }
-        if ((cap_now == hipStreamCaptureStatusActive) != (cap_before == hipStreamCaptureStatusActive)) return hipSuccess;
-        if (hipEventRecord(h->z_free, h->z_stream) != hipSuccess) {      // (that stream was destroyed meanwhile: whatever it still runs is waited for the blunt way)
-            (void)hipGetLastError();
-            return hipDeviceSynchronize();
-        }
-        return hipStreamWaitEvent(st, h->z_free, 0);
-    };
-    auto leave = [&]() -> hipError_t {
-        h->z_used = true;
-        h->z_stream = st;
-        return event_per_spmv ? hipEventRecord(h->z_free, st) : hipSuccess;
-    };
+    auto enter = [&]() { return handle_enter(h, st); };
+    auto leave = [&]() { return handle_leave(h, st); };
     if (!h->paneled()) {
         if (h->parts.empty()) return hipSuccess;
-        if (h->parts[0].img.hub_n == 0) return cvr::launch_spmv(h->parts[0].img, x, y, st);
+        if (h->parts[0].img.hub_n == 0 && !h->d_map) return cvr::launch_spmv(h->parts[0].img, x, y, st);
         hipError_t e = enter();
         if (e != hipSuccess) return e;
         e = cvr::launch_spmv(h->parts[0].img, x, y, st);
@@ -490,6 +500,15 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     const bool on_device = csr_in->arrays_on_device != 0;
     int rc = on_device ? CVR_OK : check_csr(csr_in);          // host arrays: rejected before any device work
     if (rc) return rc;
+    // new values later (cvr_update_values_device): the handle maps every slot to its CSR position -- the dictionary, which stores codes of the
+    // values seen at creation, is off; positions + 1 must fit a u32 beside the pad mark
+    if (opt.mutable_values != 0) {
+        if (opt.mutable_values != 1) return fail(CVR_ERR_INVALID, "mutable_values takes 0 or 1");
+        if (opt.value_dict > 0) return fail(CVR_ERR_INVALID, "mutable_values = 1 keeps the values in the image: value_dict > 0 conflicts with it");
+        opt.value_dict = 0;
+        if (!on_device && csr_in->nrows > 0 && csr_in->row_ptr[csr_in->nrows] >= (int64_t)cvr::kNoSource)
+            return fail(CVR_ERR_INVALID, "mutable_values: row_ptr[nrows] must stay below 2^32 - 1");
+    }
     clk.lap("options, check_csr (host)");
     if (ndev <= 0) return fail(CVR_ERR_NO_DEVICE, "no HIP device visible: libcvr_amd has no CPU fallback");
     if (opt.device < 0 || opt.device >= ndev) return fail(CVR_ERR_NO_DEVICE, "device %d out of range [0, %d)", opt.device, ndev);
@@ -548,6 +567,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
             j0 = rp_host.front(); j1 = rp_host.back();
         }
         dev_j0 = j0; dev_j1 = j1;
+        if (opt.mutable_values && j1 >= (int64_t)cvr::kNoSource) return fail(CVR_ERR_INVALID, "mutable_values: row_ptr[nrows] must stay below 2^32 - 1");
         rc = check_columns_device(hostv.col_idx, j0, j1, hostv.ncols);
         if (rc) return rc;
         const double xb = (double)hostv.ncols * (hostv.is_f32 ? 4.0 : 8.0);
@@ -622,6 +642,19 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     CREATE_TRY(hipEventCreate(&h->events[1]));
     clk.lap("handle, stream");
     const double t_up0 = now_s();
+    if (opt.mutable_values) {
+        // the caller's values wait on the device until cvr_preprocess writes them through the map (cvr_update.hip); everything from here to
+        // the image reads CSR positions instead: element i = i + 1 (device memory, also for host arrays -- the host split is not taken)
+        const int64_t nv = rows_on_device ? dev_j1 : nrows ? csr->row_ptr[nrows] : 0;
+        h->mutable_vals = true;
+        h->nvals = nv;
+        CREATE_TRY(hipMalloc(&h->d_vals0, std::max<size_t>(vsz * (size_t)nv, 16)));
+        CREATE_TRY(hipMalloc(&h->d_idx, std::max<size_t>(vsz * (size_t)nv, 16)));
+        if (nv) CREATE_TRY(hipMemcpyAsync(h->d_vals0, csr->vals, vsz * (size_t)nv, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        CREATE_TRY(cvr::launch_index_values(h->d_idx, (uint64_t)nv, f32, h->stream));
+        CREATE_TRY(hipStreamSynchronize(h->stream));
+        hostv.vals = h->d_idx;
+    }
     // Host arrays of a matrix that may get column panels (x of 24 MB or more -- 12 MB beyond the resident layout --, or panels asked for) are uploaded once, as they
     // are: the panel rule and the split run on that copy (building split arrays on the host means allocating, touching and
     // freeing another copy of the matrix there, which costs more than the PCIe transfer: LiveJournal shape 60 ms to split +
@@ -635,7 +668,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     const int64_t  sj0 = rows_on_device ? dev_j0 : nrows ? csr->row_ptr[0] : 0, sj1 = rows_on_device ? dev_j1 : nrows ? csr->row_ptr[nrows] : 0;
     const int64_t *rp_d = csr_in->row_ptr;
     const int32_t *ci_d = csr_in->col_idx;
-    const void    *va_d = csr_in->vals;
+    const void    *va_d = csr->vals;
     bool           dev_split = on_device;
     int            P = opt.col_panels;
     const double   xbytes = (double)ncols * (double)vsz;
@@ -647,7 +680,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     // gang panels: profiles/r06_thin_lists_rule.log)
     const bool     ask_window = P < 0 && !mid_range && xbytes >= kNoWindowPanelBytes && xbytes < 24e6 && sj1 > sj0 && nrows >= 4096 && ncols >= 4096 && opt.steps_per_chunk == 0 && opt.waves_per_block == 0 &&
                                 opt.x_window < 0 && opt.col_phases < 0 && opt.interleave < 0 && opt.gang < 0 && opt.hub_table < 0 && !opt.debug_col_mask && !cvr::debug_env("no_auto_layout") && !cvr::debug_env("no_window_question");
-    if (!on_device && (P > 1 || (P < 0 && (xbytes >= 24e6 || mid_range || ask_window))) && sj1 > 0 && sj1 < (int64_t)0xffffffffll && !cvr::debug_env("host_split")) {
+    if (!on_device && (P > 1 || (P < 0 && (xbytes >= 24e6 || mid_range || ask_window))) && sj1 > 0 && sj1 < (int64_t)0xffffffffll && (h->mutable_vals || !cvr::debug_env("host_split"))) {
         auto         up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t b_rp = up(sizeof(int64_t) * ((size_t)nrows + 1)), b_ci = up(sizeof(int32_t) * (size_t)sj1), b_va = up(vsz * (size_t)sj1);
         if (hipMalloc(&staged.rp, b_rp + b_ci + b_va) == hipSuccess) {
@@ -657,7 +690,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
         if (staged.rp &&
             hipMemcpy(staged.rp, csr->row_ptr, sizeof(int64_t) * ((size_t)nrows + 1), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(staged.ci, csr->col_idx, sizeof(int32_t) * (size_t)sj1, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(staged.va, csr->vals, vsz * (size_t)sj1, hipMemcpyHostToDevice) == hipSuccess) {
+            hipMemcpy(staged.va, csr->vals, vsz * (size_t)sj1, h->d_idx ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) == hipSuccess) {
             rp_d = static_cast<const int64_t *>(staged.rp); ci_d = static_cast<const int32_t *>(staged.ci); va_d = staged.va;
             dev_split = true;
         } else {
@@ -837,6 +870,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
             staged.release();       // the split arrays replace the staging copy
             for (int p = 0; p < P; p++) nsubs[(size_t)p] = dsg.d.sub0[p + 1] - dsg.d.sub0[p];
         } else {
+            if (h->mutable_vals && sj1 > 0) { cvr_destroy(h); return fail(CVR_ERR_NOMEM, "mutable_values: no device memory for the staging copy the column-panel split runs on"); }
             split_panels(*csr, P, sp);
             for (int p = 0; p < P; p++) nsubs[(size_t)p] = (int64_t)sp.rows[(size_t)p].size();
         }
@@ -1151,6 +1185,7 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     CREATE_TRY(hipMemsetAsync(h->d_y, 0, vsz * (size_t)in.yext_elems, h->stream));
     CREATE_TRY(hipMemsetAsync(h->d_err, 0, sizeof(uint32_t), h->stream));
     CREATE_TRY(hipStreamSynchronize(h->stream));   // the caller may free its CSR when this returns
+    if (h->d_idx) { (void)hipFree(h->d_idx); h->d_idx = nullptr; }      // (mutable_values: the parts' device CSR holds the positions now)
     in.upload_s = now_s() - t_up0 - in.plan_s - in.probe_s - panel_rule_s - in.hub_select_s;      // (hub selection and the layout probe are reported on their own)
     in.plan_s += panel_rule_s;
     cvr::free_plan_scratch(h->plan_ws);
@@ -1175,6 +1210,8 @@ int cvr_preprocess(cvr_handle *h, int keep_csr, double *seconds)
         if (seconds) *seconds = h->info.convert_s;
         h->info.preprocess_wall_s = now_s() - t_wall0;
         h->converted = true;
+        { const int rcm = mutable_after_convert(h, keep_csr != 0); if (rcm) return rcm; }
+        h->csr_kept = keep_csr != 0;
         if (!keep_csr) { for (Part &p : h->parts) p.release_csr(); h->release_split(); }
         return CVR_OK;
     }
@@ -1307,8 +1344,10 @@ int cvr_preprocess(cvr_handle *h, int keep_csr, double *seconds)
     if (err) return fail(CVR_ERR_INTERNAL, "device converter self-check failed (flags 0x%x)", err);
     h->info.nsegments = 0;
     for (uint32_t v : seg_totals) h->info.nsegments += v;
-    h->info.preprocess_wall_s = now_s() - t_wall0;
     h->converted = true;
+    { const int rcm = mutable_after_convert(h, keep_csr != 0); if (rcm) return rcm; }
+    h->info.preprocess_wall_s = now_s() - t_wall0;
+    h->csr_kept = keep_csr != 0;
     if (!keep_csr) { for (Part &p : h->parts) p.release_csr(); h->release_split(); }
     return CVR_OK;
 }
@@ -1334,6 +1373,7 @@ int cvr_destroy(cvr_handle *h)
     if (h->d_small) (void)hipFree(h->d_small);
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     if (h->z_free) (void)hipEventDestroy(h->z_free);
+    for (void *p : {(void *)h->d_map, (void *)h->d_upd, h->d_vals0, h->d_idx}) if (p) (void)hipFree(p);
     for (void *p : {(void *)h->d_err, h->d_z, (void *)h->d_rows, (void *)h->d_rows16, (void *)h->d_cbits, (void *)h->d_cut, (void *)h->d_block_off, (void *)h->d_cpanels, (void *)h->d_fixparts, (void *)h->d_multi, h->d_dict, h->d_x, h->d_y}) if (p) (void)hipFree(p);
     release_stream(h->device, h->stream);
     delete h;

@@ -79,6 +79,8 @@ void make_key(ImgKey &k, const cvr_source_key *src, const IOpt &o, size_t vsz)
     memcpy(k.opt, ov, sizeof(ov));
     // (slot 16, zero before: a key of nvec 0 / 1 is the key images were saved under before the option existed)
     k.opt[16] = o.nvec >= 2 ? o.nvec : 0;
+    // (slot 17, zero before: mutable_values -- such a file also holds the handle's position map)
+    k.opt[17] = o.mutable_values ? 1 : 0;
     k.cus = o.cus; k.xcds = o.xcds;
     snprintf(k.lib, sizeof(k.lib), "%s", cvr_version());
 }
@@ -149,6 +151,11 @@ int cvr_save_image(cvr_handle *h, const char *path, const cvr_source_key *key)
         const uint32_t nblocks = (uint32_t)((h->info.nrows + cvr::kCombineRows - 1) / cvr::kCombineRows);
         w.dev(h->d_rows, sizeof(uint32_t) * (size_t)std::max<int64_t>(nsub, 1), host);
         w.dev(h->d_block_off, sizeof(uint32_t) * (size_t)nparts * (nblocks + 1), host);
+    }
+    if (h->mutable_vals) {          // mutable_values: the values array's length and the position map (cvr_update.hip)
+        const int64_t nvals = h->nvals;
+        w.pod(nvals);
+        w.dev(h->d_map, sizeof(uint32_t) * 256 * (size_t)h->map_groups, host);
     }
     const uint64_t tail = kImgMagic;      // (a truncated file does not end with it)
     w.pod(tail);
@@ -307,6 +314,17 @@ int cvr_load_image(cvr_handle **out, const char *path, const cvr_source_key *exp
             LOAD_TRY(hipMemcpy(h->d_multi, pa.data(), sizeof(cvr::PanelArgs) * pa.size(), hipMemcpyHostToDevice));
         }
     }
+    if (opt.mutable_values) {          // (the key says the file was saved from a mutable handle: its map follows)
+        unsigned long long ngroups = 0;
+        for (const Part &p : h->parts) ngroups += (unsigned long long)p.nchunks * (unsigned long long)p.img.G;
+        int64_t nvals = -1;
+        r.pod(nvals);
+        if (!r.ok || nvals < 0 || nvals >= (int64_t)cvr::kNoSource || h->ndict != 0) { r.ok = false; LOAD_TRY(hipSuccess); }
+        h->mutable_vals = true;
+        h->nvals = nvals;
+        LOAD_TRY(r.dev(h->d_map, pinned, pinned_bytes, h->stream, sizeof(uint32_t) * 256 * ngroups, false, 16));
+        if (!h->d_map) LOAD_TRY(hipMalloc(&h->d_map, 16));
+    }
     uint64_t tail = 0;
     r.pod(tail);
     if (tail != kImgMagic) r.ok = false;
@@ -323,6 +341,7 @@ int cvr_load_image(cvr_handle **out, const char *path, const cvr_source_key *exp
     pinned = nullptr;
 #undef LOAD_TRY
     { const int rcf = setup_fuse(h); if (rcf) { cvr_destroy(h); return rcf; } }          // (the fused combine's tables follow from the chunk tables: made again, not stored)
+    if (h->mutable_vals) { const int rcm = mutable_tables(h); if (rcm) { cvr_destroy(h); return rcm; } }
     ilv_runtime_settings(h);
     h->converted = true;
     // what the first run spent on analysis and conversion does not apply to this handle

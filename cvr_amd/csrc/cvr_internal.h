@@ -189,6 +189,17 @@ struct cvr_handle {
     size_t seg_arena_bytes = 0;
     bool   preconverted = false;         // cvr_create converted the image already (cvr_fused.hip): the first cvr_preprocess has nothing left to do
     IOpt opt_used;                       // the options the handle was created with (the image cache keys on them: cvr_image_io.hip)
+    // cvr_options.mutable_values (cvr_update.hip): the image was converted with CSR positions for values; d_map = where every slot's value comes
+    // from (a u32 per slot, all parts' groups one after the other), d_upd = the parts' streams for the update kernels; d_vals0 = the creation
+    // values until cvr_preprocess has written them (kept with the CSR under keep_csr); nvals = row_ptr[nrows], the length of a values array
+    bool                mutable_vals = false;
+    bool                csr_kept = false;        // the last cvr_preprocess had keep_csr != 0
+    uint32_t           *d_map = nullptr;
+    cvr::UpdatePart    *d_upd = nullptr;
+    unsigned long long  map_groups = 0;
+    void               *d_vals0 = nullptr;
+    void               *d_idx = nullptr;         // cvr_create only: the positions + 1 that stand in for the values on the way to the image
+    int64_t             nvals = 0;
 
     bool paneled() const { return parts.size() > 1; }
 };
@@ -209,6 +220,14 @@ int        setup_fuse(cvr_handle *h);
 int        setup_combine_bits(cvr_handle *h, int64_t nsub);                    // the fused combine's tables, for handles whose panels all carry gang chunks and run one per XCD (after d_multi)
 void       ilv_runtime_settings(cvr_handle *h);          // helper wavefronts / sweep direction of interleaved images (launch parameters)      // y_ext = A x for the whole handle on `st`
 IOpt       make_iopt(const cvr_options *in);
+// The handle's image (column panels' partial sums, hub table's x, a mutable handle's values) is shared by every launch on it: a launch on
+// another stream than the one before waits for that one (the event is recorded when the stream changes).  Around every launch that reads or
+// writes it: enter before, leave after.
+hipError_t handle_enter(cvr_handle *h, hipStream_t st);
+hipError_t handle_leave(cvr_handle *h, hipStream_t st);
+// ---- cvr_update.hip: mutable_values -- the parts table of the update kernels, and what follows a conversion (map on the first, creation values)
+int        mutable_tables(cvr_handle *h);
+int        mutable_after_convert(cvr_handle *h, bool keep_csr);
 int        check_csr(const cvr_csr_view *c, bool columns_on_host = true);
 int        check_columns_device(const int32_t *ci_dev, int64_t j0, int64_t j1, int64_t ncols);
 

@@ -242,6 +242,20 @@ constexpr int kSpmmBlock = 8;
 bool       spmm_plain(const DeviceImage &img);
 hipError_t launch_spmm(const DeviceImage &img, const void *X, int64_t ldx, void *Y, int64_t ldy, int32_t nvec, hipStream_t st);
 
+// New values of the same pattern (cvr_update.hip; cvr_options.mutable_values): the value block of every group of every image, through a map of
+// one u32 per slot -- map[g * 256 + e] = the CSR position whose value stands at element e of group g's value block (groups of all parts
+// numbered one after the other), kNoSource for pad slots and tail slots (+0.0).  parts[0 .. nparts] (device; parts[nparts].g0 = all groups):
+// the stream of every image, its first group in that numbering, the bytes of one of its groups and where the value block starts in one.
+constexpr uint32_t kNoSource = 0xffffffffu;
+struct UpdatePart { uint8_t *stream; unsigned long long g0; uint32_t gbytes, voff; };
+// map from an image converted with value i + 1 (bit pattern, as the value type) at CSR position i: 0 -> kNoSource, v -> v - 1; a value
+// beyond nvals sets bit 8 of *err_flag.  One wavefront per group.  Asynchronous on st.
+hipError_t launch_value_map(const UpdatePart *parts, uint32_t nparts, uint64_t ngroups, bool f32, uint32_t *map, uint64_t nvals, uint32_t *err_flag, hipStream_t st);
+// value block element e of group g = vals[map[g * 256 + e]] (bit for bit; +0.0 for kNoSource).  One wavefront per group.  Asynchronous on st.
+hipError_t launch_update_values(const UpdatePart *parts, uint32_t nparts, uint64_t ngroups, bool f32, const uint32_t *map, const void *vals, hipStream_t st);
+// element i = the bit pattern of i + 1 as the value type (u64 / u32), i < n: the values a mutable handle is converted with
+hipError_t launch_index_values(void *out, uint64_t n, bool f32, hipStream_t st);
+
 // column panels: one fix-up launch for all panels (each with its own y_ext inside the partial-sum buffer)
 struct FixPart { const int64_t *shared; void *yext; uint32_t nshared, nrows; };
 hipError_t launch_fixup_multi(const FixPart *parts, uint32_t nparts, uint32_t max_nshared, bool f32, hipStream_t st);

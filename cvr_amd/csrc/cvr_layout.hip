@@ -670,7 +670,7 @@ int build_part(cvr_handle *h, Part &part, int64_t nrows, int64_t ncols, const in
     if (rp && !adopted && nrows > 0) HIP_TRY(hipMemcpyAsync(part.d_rp, rp, sizeof(int64_t) * ((size_t)nrows + 1), hipMemcpyHostToDevice, h->stream));
     if (nnz_span && !adopted) {
         HIP_TRY(hipMemcpyAsync(part.d_ci, ci, sizeof(int32_t) * nnz_span, civa_kind, h->stream));
-        HIP_TRY(hipMemcpyAsync(part.d_va, va, vsz * nnz_span, civa_kind, h->stream));
+        HIP_TRY(hipMemcpyAsync(part.d_va, va, vsz * nnz_span, va == h->d_idx ? hipMemcpyDeviceToDevice : civa_kind, h->stream));      // (mutable_values: positions on the device)
     }
     PartPlan    local;
     IOpt        popt = opt;

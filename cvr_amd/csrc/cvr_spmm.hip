@@ -34,7 +34,9 @@ int spmm_device(cvr_handle *h, const void *X, int64_t ldx, void *Y, int64_t ldy,
     if (!img) return fail(CVR_ERR_STATE, "cvr_spmm_device: this handle's image is not the plain layout; create it with cvr_options.nvec >= 2 for several vectors");
     if ((uint64_t)(h->info.ncols + 1) * (uint64_t)ldx * h->vsz > 0xffffffffull)
         return fail(CVR_ERR_INVALID, "X of %lld rows of %lld values exceeds the 4 GiB a buffer descriptor addresses", (long long)(h->info.ncols + 1), (long long)ldx);
+    if (h->d_map) HIP_TRY(handle_enter(h, st));          // (a mutable handle's image: ordered with its updates)
     HIP_TRY(cvr::launch_spmm(*img, X, ldx, Y, ldy, nvec, st));
+    if (h->d_map) HIP_TRY(handle_leave(h, st));
     return CVR_OK;
 }
 

@@ -121,7 +121,12 @@ typedef struct {
                                   above.  >= 2: the plain layout -- one chunk per workgroup, no window, column phases, column panels, hub table,
                                   re-ordering, interleaved or gang chunks (value dictionary and narrow columns by their own rules) --, the one whose
                                   kernel has a k-wide form; an explicit setting of any of those options beyond off is refused (CVR_ERR_INVALID) */
-    int32_t reserved[2];       /* 0 */
+    int32_t mutable_values;    /* 1: the handle keeps, for every slot of its image, the CSR position its value came from (a u32 per slot: 4 *
+                                  cvr_info.nslots device bytes beside the image), so that cvr_update_values_device can write new values of the same
+                                  sparsity pattern without converting again.  The value dictionary is then off (value_dict < 0 turns it off, an explicit
+                                  value_dict > 0 is refused with CVR_ERR_INVALID), and row_ptr[nrows] must stay below 2^32 - 1 (CVR_ERR_INVALID).
+                                  Every other option and rule works as without it.  0 (default): nothing of this; the former reserved[0]     */
+    int32_t reserved[1];       /* 0 */
 } cvr_options;
 /* Automatic layout: with steps_per_chunk = 0, waves_per_block = 0, x_window < 0 and col_phases < 0 (the defaults) cvr_create
  * looks at the uploaded CSR on the device (are the rows sorted by column? which share of the non-zeros lies near the
@@ -232,6 +237,21 @@ int cvr_spmm_device(cvr_handle *h, const void *X_dev, int64_t ldx, void *Y_dev, 
 int cvr_spmm(cvr_handle *h, const void *X_host, void *Y_host, int32_t nvec, int iters, cvr_timing *timing);
 /* 1: the handle's image runs cvr_spmm_device for any nvec; 0: it only takes nvec = 1 with ldx = ldy = 1 (any layout) */
 int cvr_spmm_supported(const cvr_handle *h);
+/* New values for a handle created with cvr_options.mutable_values = 1: the same sparsity pattern, other values.  vals_dev is a device array
+ * of the handle's device (double or float by is_f32), indexed exactly like the cvr_csr_view.vals the handle was created from: element i is
+ * the value of CSR position i, 0 <= i < row_ptr[nrows].  One kernel writes them into the image (value block of every group, through the
+ * handle's position map); every SpMV, SpMM and power-iteration step after it computes with them.  Values are copied bit for bit (NaN, Inf,
+ * -0.0 and explicit zeros included, none checked).  Asynchronous on `stream` (NULL = HIP's null stream) and capturable in a HIP graph, like
+ * cvr_spmv_device; ordered like the handle's SpMV launches: when the launch before went to another stream the update waits for it, and a
+ * launch on a third stream waits for the update.  vals_dev may be reused once the update has run on `stream`.
+ * Errors (all checked before any device work): null handle or array CVR_ERR_INVALID; a handle created without mutable_values, one not yet
+ * through cvr_preprocess, or one that kept its device CSR (cvr_preprocess with keep_csr != 0: a later cvr_preprocess would convert the
+ * creation values again; refreshing the kept CSR is not offered) CVR_ERR_STATE. */
+int cvr_update_values_device(cvr_handle *h, const void *vals_dev, void *stream);
+/* the same from host memory: copied on the handle's stream, returns when the image holds the new values */
+int cvr_update_values(cvr_handle *h, const void *vals_host);
+/* 1: cvr_update_values* accept this handle (mutable_values, preprocessed, no kept CSR); 0 otherwise */
+int cvr_update_values_supported(const cvr_handle *h);
 /* The column-panel count cvr_create chooses for col_panels = -1 (host only, no device needed): 1 unless x is >= 24 MB
  * -- or >= 12 MB and the matrix is too large for the resident layout (more slots or rows than its workgroups hold in one pass) --
  * and the estimated share of x gathers missing a 4-MiB L2 (*l2_miss_estimate, sampled over eight windows of 65 536
