@@ -74,6 +74,7 @@ class MmMatrix(C.Structure):
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
+           "cvr_spmv_scaled_device", "cvr_spmv_scaled",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -118,6 +119,8 @@ def lib():
         L.cvr_spmm_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_spmm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.POINTER(Timing)]
         L.cvr_spmm_supported.argtypes = [C.c_void_p]
+        L.cvr_spmv_scaled_device.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.cvr_spmv_scaled.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -517,6 +520,30 @@ class CvrMatrix:
             rc = lib().cvr_spmv_device_repeat(self._h, x_ptr, y_ptr, stream, repeat)
         if rc:
             raise CvrError(rc, "cvr_spmv_device")
+
+    def spmv_scaled(self, x, y, alpha=1.0, beta=0.0):
+        """y = alpha A x + beta y through host buffers (cvr_spmv_scaled): returns the new y (nrows values of the handle's dtype); x may be
+        None when alpha == 0, y is not read when beta == 0"""
+        xa = None if x is None else np.ascontiguousarray(x, dtype=self.dtype)
+        if xa is not None and len(xa) < self.ncols:
+            raise ValueError("x is shorter than ncols")
+        out = np.zeros(max(self.nrows, 1), dtype=self.dtype)
+        if y is not None:
+            ya = np.asarray(y, dtype=self.dtype)
+            if len(ya) < self.nrows:
+                raise ValueError("y is shorter than nrows")
+            out[: self.nrows] = ya[: self.nrows]
+        rc = lib().cvr_spmv_scaled(self._h, float(alpha), None if xa is None else xa.ctypes.data, float(beta), out.ctypes.data)
+        if rc:
+            raise CvrError(rc, "cvr_spmv_scaled")
+        return out[: self.nrows]
+
+    def spmv_scaled_device(self, x_ptr, y_ptr, alpha, beta, stream=None):
+        """asynchronous y = alpha A x + beta y on caller-owned device buffers (cvr_spmv_scaled_device; buffers as spmv_device, the first
+        nrows values of y_ext are y); x_ptr may be None when alpha == 0"""
+        rc = lib().cvr_spmv_scaled_device(self._h, float(alpha), x_ptr, float(beta), y_ptr, stream)
+        if rc:
+            raise CvrError(rc, "cvr_spmv_scaled_device")
 
     def spmm(self, X, iters=1):
         """Y = A X for the k columns of X (host array of shape (ncols, k)) in one pass per block of 8 (cvr_spmm); returns (Y of shape

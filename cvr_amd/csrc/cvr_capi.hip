@@ -55,19 +55,20 @@ hipError_t handle_leave(cvr_handle *h, hipStream_t st)
 }
 
 // y_ext = A x for the whole handle on `st`: one SpMV launch, or one per column panel followed by the combine
-hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st)
+hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st, const cvr::ScaleEpi *sc)
 {
     auto enter = [&]() { return handle_enter(h, st); };
     auto leave = [&]() { return handle_leave(h, st); };
     if (!h->paneled()) {
         if (h->parts.empty()) return hipSuccess;
-        if (h->parts[0].img.hub_n == 0 && !h->d_map) return cvr::launch_spmv(h->parts[0].img, x, y, st);
+        if (h->parts[0].img.hub_n == 0 && !h->d_map) return cvr::launch_spmv(h->parts[0].img, x, y, st, true, nullptr, 0, 1, nullptr, nullptr, nullptr, sc);
         hipError_t e = enter();
         if (e != hipSuccess) return e;
-        e = cvr::launch_spmv(h->parts[0].img, x, y, st);
+        e = cvr::launch_spmv(h->parts[0].img, x, y, st, true, nullptr, 0, 1, nullptr, nullptr, nullptr, sc);
         if (e != hipSuccess) return e;
         return leave();
     }
+    if (sc && h->d_fuse) return hipErrorInvalidValue;          // (the fused combine writes cut rows twice: cvr_spmv_scaled_device takes its two-pass form)
     { const hipError_t e = enter(); if (e != hipSuccess) return e; }
     if (h->d_multi) {          // eight panels per launch, panel b & 7 on the XCD of the workgroups b
         cvr::DeviceImage shared = h->parts[0].img;
@@ -99,7 +100,7 @@ hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st)
     hipError_t e = fold ? hipSuccess : cvr::launch_fixup_multi(h->d_fixparts, (uint32_t)h->parts.size(), h->max_nshared, h->vsz == 4, st);
     if (e != hipSuccess) return e;
     e = cvr::launch_combine(h->d_cpanels, (uint32_t)h->parts.size(), h->d_block_off, y, (uint32_t)h->info.nrows, h->vsz == 4, st, h->combine_batch, h->combine_mul, h->d_cbits, fold ? h->d_cut : nullptr,
-                            fold ? h->ncut_fold : 0u);
+                            fold ? h->ncut_fold : 0u, sc);
     if (e != hipSuccess) return e;
     return leave();
 }
@@ -1373,7 +1374,7 @@ int cvr_destroy(cvr_handle *h)
     if (h->d_small) (void)hipFree(h->d_small);
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     if (h->z_free) (void)hipEventDestroy(h->z_free);
-    for (void *p : {(void *)h->d_map, (void *)h->d_upd, h->d_vals0, h->d_idx}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)h->d_map, (void *)h->d_upd, h->d_vals0, h->d_idx, h->d_scaled_tmp}) if (p) (void)hipFree(p);
     for (void *p : {(void *)h->d_err, h->d_z, (void *)h->d_rows, (void *)h->d_rows16, (void *)h->d_cbits, (void *)h->d_cut, (void *)h->d_block_off, (void *)h->d_cpanels, (void *)h->d_fixparts, (void *)h->d_multi, h->d_dict, h->d_x, h->d_y}) if (p) (void)hipFree(p);
     release_stream(h->device, h->stream);
     delete h;

@@ -200,6 +200,8 @@ struct cvr_handle {
     void               *d_vals0 = nullptr;
     void               *d_idx = nullptr;         // cvr_create only: the positions + 1 that stand in for the values on the way to the image
     int64_t             nvals = 0;
+    void               *d_scaled_tmp = nullptr;  // the plain product of cvr_spmv_scaled_device's two-pass form (cvr_scaled.hip; y_ext's size, allocated at its first use)
+    bool                scaled_two_pass = cvr::debug_env("scaled_two_pass") != nullptr;      // CVR_DEBUG=scaled_two_pass when the handle was made: that form always
 
     bool paneled() const { return parts.size() > 1; }
 };
@@ -213,7 +215,7 @@ namespace cvrh {
 // whole chip and switch themselves off otherwise.  Cached per device; {256, 8} if the query fails.
 struct Chip { int cus = 256, xcds = 8; };
 Chip       chip_of(int device);
-hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st);
+hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st, const cvr::ScaleEpi *sc = nullptr);      // sc: the scaled product's write-out (not with the fused combine)
 int        setup_fuse(cvr_handle *h);
 // The combine pass's bitmap (cvr_kernels.h: launch_combine_bits_build) for a panelled handle with at most 16 panels and half or more of its (row, panel) pairs filled:
 // allocated and filled on the handle's stream behind the combine tables.  nsub = the handle's partial sums (all panels).  CVR_DEBUG=combine_bits=0|1 overrides the rule.

@@ -219,6 +219,14 @@ struct PanelArgs { const uint8_t *stream; const uint4 *desc; const uint8_t *targ
 // before|| (prev: that step's partials, null = 1).  cvr_iter.hip's power_step_kernel is the same step as a pass of its own.
 struct IterEpilogue { void *xnext = nullptr; const double *prev = nullptr; double *out = nullptr; uint32_t nsets = 0; };
 bool iter_epilogue_ok(const DeviceImage &img);      // launch_spmv honours `epi` for this image
+// The scaled product (cvr_spmv_scaled_device) in the write-out: where a kernel stores a row's FINAL value (dst < nrows; carry slots and the dump slot are
+// scratch and keep the raw sum) it stores alpha * v + beta * y[dst] instead of v, in T (alpha and beta rounded to T first; two rounded products and a
+// rounded sum, no fused multiply-add).  mode 0: off (the plain product), 1: alpha * v (beta == 0: y is not read), 2: alpha * v + beta * y[dst].
+struct ScaleEpi { double alpha = 1, beta = 0; uint32_t nrows = 0, mode = 0; };
+// y[i] = alpha * t[i] + beta * y[i], i < n, by the rule above (mode 1: alpha * t[i]); t == null: beta * y[i] (alpha == 0), or +0 with mode 0 -- the two-pass
+// form of ScaleEpi (layouts whose write-out does not take it, CVR_DEBUG=scaled_two_pass) and the alpha == 0 call.  Asynchronous on st.
+hipError_t launch_axpby(const void *t, void *y, int64_t n, bool f32, const ScaleEpi &sc, hipStream_t st);
+bool       scale_fused_ok(const DeviceImage &img, bool multi);      // launch_spmv honours `sc` for this image (multi: a panel launch, whose output is partial sums)
 // The combine pass of column panels INSIDE the panel kernel (gang chunks; round 6): a gang that has stored its rows' partial sums counts itself in at
 // every block of kCombineRows rows its sub-rows may lie in (range[gang] = {first, last block}; the ranges of a panel's gangs tile all blocks), and the
 // workgroup whose count completes a block -- expect[block] = gangs of all panels that cover it -- adds that block's partial sums, panel by panel in panel
@@ -234,7 +242,7 @@ hipError_t launch_fuse_cut_rows(const int64_t *shared, uint32_t nshared, const u
 hipError_t launch_fuse_patch(const uint32_t *rows_list, uint32_t nlist, const FusePanel *panels_dev, const struct CombinePanel *cpanels, const uint32_t *nsub, uint32_t npanels, void *y, bool f32, hipStream_t st);
 hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, hipStream_t st, bool with_fixup = true, const PanelArgs *multi = nullptr, uint32_t multi_chunks = 0,
                        uint32_t multi_rounds = 1,
-                       const IterEpilogue *epi = nullptr, const FuseArgs *fuse = nullptr, void *y_fused = nullptr);
+                       const IterEpilogue *epi = nullptr, const FuseArgs *fuse = nullptr, void *y_fused = nullptr, const ScaleEpi *sc = nullptr);
 size_t     spmv_lds_bytes(const DeviceImage &img);      // dynamic LDS of that launch
 // Several vectors (cvr_spmm_device): Y = A X over an image of the plain layout (spmm_plain), X / Y row-major with leading dimensions ldx / ldy (in values),
 // blocks of up to kSpmmBlock vectors per launch, then the cut rows' fix-up per vector.  hipErrorInvalidValue for another layout or an X beyond 4 GiB.
@@ -274,7 +282,7 @@ constexpr uint32_t kMaxCutFold = 8;
 // 32-bit row numbers of all panels' partial sums and the array CombinePanel.rows points into (the same order).  Asynchronous on st.
 hipError_t launch_cut_table(const struct FixPart *parts, uint32_t nparts, uint32_t max_nshared, const struct CombinePanel *panels, const uint16_t *rows16_base, const uint32_t *rows32, CutEntry *out, uint32_t *count, hipStream_t st);
 hipError_t launch_combine(const CombinePanel *panels, uint32_t npanels, const uint32_t *block_off, void *y, uint32_t nrows, bool f32, hipStream_t st, int batch = 4, int mul = 1,
-                          const uint32_t *bits = nullptr, const CutEntry *cut = nullptr, uint32_t ncut = 0);      // bits (mul = 1, <= 16 panels): the bitmap form -- a thread owns four rows, no row numbers read (combine_bits_kernel)
+                          const uint32_t *bits = nullptr, const CutEntry *cut = nullptr, uint32_t ncut = 0, const ScaleEpi *sc = nullptr);      // bits (mul = 1, <= 16 panels): the bitmap form -- a thread owns four rows, no row numbers read (combine_bits_kernel)
 // bits[(p * nblocks + b) * 32 + w]: the rows b * kCombineRows + 32 w .. that have a partial sum in panel p (nblocks = ceil(nrows / kCombineRows)); asynchronous on st
 hipError_t launch_combine_bits_build(const CombinePanel *panels, uint32_t npanels, const uint32_t *block_off, uint32_t nrows, uint32_t *bits, hipStream_t st);      // batch: panels whose loads share a round trip (4 or 8); mul: blocks of kCombineRows rows per workgroup (1 or 8)
 

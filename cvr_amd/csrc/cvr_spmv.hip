@@ -197,6 +197,21 @@ __device__ __forceinline__ uint32_t remap_block(uint32_t b, uint32_t nblocks_per
 // (profiles/r01_waves_per_block.log)
 template <typename T> __device__ __forceinline__ void store_y(T *p, T v) { *p = v; }
 
+// the scaled product's write-out (ScaleEpi, cvr_kernels.h): a row's final value (dst < nrows) becomes alpha * v + beta * y[dst] -- rounded products, rounded
+// sum (the build has -ffp-contract=off) --, or alpha * v when beta is 0 (y not read); scratch slots keep v
+template <typename T> __device__ __forceinline__ T scale_row(const ScaleEpi &sc, T v, T yold) { return sc.mode == 2 ? (T)sc.alpha * v + (T)sc.beta * yold : (T)sc.alpha * v; }
+template <typename T> __device__ __forceinline__ void store_y_scaled(T *yext, uint32_t dst, T v, const ScaleEpi &sc)
+{
+    if (dst < sc.nrows) v = scale_row(sc, v, sc.mode == 2 ? yext[dst] : T(0));
+    store_y(yext + dst, v);
+}
+// the same where the epilogue is a run-time argument only (the ring kernels: their instantiations stay as they are), mode 0 = the plain store
+template <typename T> __device__ __forceinline__ void store_y_rt(T *yext, uint32_t dst, T v, const ScaleEpi &sc)
+{
+    if (sc.mode != 0) store_y_scaled(yext, dst, v, sc);
+    else store_y(yext + dst, v);
+}
+
 // Wave-uniform and per-lane state of one chunk.
 template <typename T> struct ChunkState {
     T        acc;       // running sum of the lane's current segment
@@ -218,10 +233,10 @@ template <typename T> __device__ __forceinline__ void lds_add_wg(T *p, T v)     
 
 // four steps of all 64 lanes: FMA, then the write-back of the lanes whose segment ends at the step.  (Images with column phases
 // run through spmv_seg_kernel below, which needs none of this hand-out state.)
-template <typename T, int WIN, bool DICT>
+template <typename T, int WIN, bool DICT, bool SC = false>
 __device__ __forceinline__ void sum_group(ChunkState<T> &s, const Group<T, DICT> &Q, const X4<T> &xq, T *__restrict__ yext,
                                           T *slot_lane, uint32_t row_first, uint32_t nseg, uint32_t head_dest,
-                                          uint32_t last_dest, const T *dict, T *ystage, bool staged)
+                                          uint32_t last_dest, const T *dict, T *ystage, bool staged, const ScaleEpi &sc)
 {
     // the four values first: with a dictionary they are LDS reads, which would otherwise be issued (and waited for) one by
     // one between the steps' LDS writes
@@ -241,7 +256,8 @@ __device__ __forceinline__ void sum_group(ChunkState<T> &s, const Group<T, DICT>
                         ystage[s.cur] = s.acc;           // written out coalesced at the end of the chunk
                     } else {
                         const uint32_t dst = s.cur == 0 ? head_dest : s.cur == nseg - 1 ? last_dest : row_first + s.cur;
-                        store_y(yext + dst, s.acc);
+                        if constexpr (SC) store_y_scaled(yext, dst, s.acc, sc);
+                        else store_y(yext + dst, s.acc);
                     }
                     s.acc = 0;
                     const uint32_t nx = s.fed + lane_rank(m);
@@ -264,13 +280,14 @@ __device__ __forceinline__ void sum_group(ChunkState<T> &s, const Group<T, DICT>
 // multi != null (column panels, one panel per XCD at a time): workgroup b works on panel b & 7 of the eight the launch covers --
 // the workgroups with equal b & 7 share an XCD under round-robin dealing, so that XCD's L2 only ever holds that panel's slice
 // of x -- and takes the panel's chunk b >> 3; what differs between the panels comes from multi[b & 7].
-template <typename T, int QA, int XPOL, int DEPTH, int WIN, bool DICT, bool MW, bool C16>
+// SC: the scaled product's write-out (ScaleEpi `sc`; the instantiations without it are the plain product's, unchanged)
+template <typename T, int QA, int XPOL, int DEPTH, int WIN, bool DICT, bool MW, bool C16, bool SC = false>
 __global__ __launch_bounds__(MW ? kLanes * kMaxWavesPerBlock : kLanes) void spmv_kernel(
     const uint8_t *__restrict__ stream_a, const uint4 *__restrict__ desc_a, const uint8_t *__restrict__ target_a,
     const T *__restrict__ x, T *__restrict__ yext_a, int G, uint32_t nchunks_a, uint32_t nblocks_per_xcd, int swz,
     uint32_t cmask, uint32_t xbytes, const uint32_t *__restrict__ win_base, uint32_t wn, const T *__restrict__ dict_g, uint32_t ndict,
     uint32_t ystage_a, const T *__restrict__ hub_x, uint32_t hub_n, uint32_t kstride,
-    const uint32_t *__restrict__ cbase, uint32_t pad_col, const PanelArgs *__restrict__ multi, uint32_t stream_mod)
+    const uint32_t *__restrict__ cbase, uint32_t pad_col, const PanelArgs *__restrict__ multi, uint32_t stream_mod, ScaleEpi sc = ScaleEpi{})
 {
     const uint8_t *__restrict__ stream = stream_a, *__restrict__ target = target_a;
     const uint4 *__restrict__   desc = desc_a;
@@ -398,7 +415,7 @@ __global__ __launch_bounds__(MW ? kLanes * kMaxWavesPerBlock : kLanes) void spmv
             const Group<T, DICT> Qn = load_group<T, SPOL, DICT, C16>(rs, voff, (uint32_t)(g + QN) * GB);
             if constexpr (C16) Q[DEPTH].c = widen_cols(Q[DEPTH].c, cb, pad_col);       // (arrived an iteration ago: the gather below needs it anyway)
             const X4<T>    xn = gather<T, XPOL, WIN>(rx, win, Q[DEPTH].c, cmask, wbase, wn, (hub_n + 3u) & ~3u, wn);
-            sum_group<T, WIN, DICT>(s, Q[0], xs[0], yext, slot_lane, row_first, nseg, head_dest, last_dest, dict, ystage, staged);
+            sum_group<T, WIN, DICT, SC>(s, Q[0], xs[0], yext, slot_lane, row_first, nseg, head_dest, last_dest, dict, ystage, staged, sc);
 #pragma unroll
             for (int i = 0; i + 1 < QN; i++) Q[i] = Q[i + 1];
             Q[QN - 1] = Qn;
@@ -416,7 +433,8 @@ __global__ __launch_bounds__(MW ? kLanes * kMaxWavesPerBlock : kLanes) void spmv
                 ystage[s.cur] = *slot_lane;
             } else {
                 const uint32_t dst = s.cur == 0 ? head_dest : s.cur == nseg - 1 ? last_dest : row_first + s.cur;
-                store_y(yext + dst, *slot_lane);
+                if constexpr (SC) store_y_scaled(yext, dst, *slot_lane, sc);
+                else store_y(yext + dst, *slot_lane);
             }
         }
         if (staged) {
@@ -424,7 +442,8 @@ __global__ __launch_bounds__(MW ? kLanes * kMaxWavesPerBlock : kLanes) void spmv
             const uint32_t nout = nseg;
             for (uint32_t i = lane; i < nout; i += kLanes) {
                 const uint32_t dst = i == 0 ? head_dest : i == nout - 1 ? last_dest : row_first + i;
-                store_y(yext + dst, ystage[i]);
+                if constexpr (SC) store_y_scaled(yext, dst, ystage[i], sc);
+                else store_y(yext + dst, ystage[i]);
             }
         }
         if (kstride == 0) break;
@@ -699,12 +718,13 @@ __device__ __forceinline__ void sum_group_seg(T &acc, const SegGroup<T, DICT, TA
 // prof[(blockIdx.x * 16 + wave) * 8 + 0..7]; tools/phase_clocks.py turns the dump into the per-XCD histogram of profiles/.
 __device__ __forceinline__ unsigned long long prof_now() { return __builtin_amdgcn_s_memrealtime(); }
 
-template <typename T, int QA, int DEPTH, int WIN, bool DICT, bool LOADER, bool TAG, bool PROF = false>
+// SC: the scaled product's write-out (ScaleEpi `sc`; never together with the iterative epilogue)
+template <typename T, int QA, int DEPTH, int WIN, bool DICT, bool LOADER, bool TAG, bool PROF = false, bool SC = false>
 __global__ __launch_bounds__(kLanes * kMaxWavesPerBlock) void spmv_seg_kernel(
     const uint8_t *__restrict__ stream_a, const uint4 *__restrict__ desc_a, const T *__restrict__ x, T *__restrict__ yext_a, int G, uint32_t nchunks_a,
     uint32_t nblocks_per_xcd, int swz, uint32_t cmask, uint32_t xbytes, const uint32_t *__restrict__ win_base, uint32_t wn,
     const T *__restrict__ dict_g, uint32_t ndict, uint32_t ystage_a, const uint2 *__restrict__ desc2_a, uint32_t col_bits, uint32_t nw_arg, int gb,
-    const PanelArgs *__restrict__ multi, IterEpilogue epi, unsigned long long *__restrict__ prof = nullptr)
+    const PanelArgs *__restrict__ multi, IterEpilogue epi, unsigned long long *__restrict__ prof = nullptr, ScaleEpi sc = ScaleEpi{})
 {
     unsigned long long pc[5] = {0, 0, 0, 0, 0};
     if constexpr (PROF) pc[0] = prof_now();
@@ -865,6 +885,28 @@ __global__ __launch_bounds__(kLanes * kMaxWavesPerBlock) void spmv_seg_kernel(
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if constexpr (PROF) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); pc[3] = prof_now(); }
+    if (SC && !epi.out) {
+        // the scaled product: old y of eight rows per lane in flight (one round trip per 512 rows, as the iterative epilogue's x below), then the rows
+        // leave as in the plain write-out
+        constexpr int kRows = 8;
+        for (uint32_t i0 = lane; i0 < nri; i0 += kLanes * kRows) {
+            T yo[kRows];
+#pragma unroll
+            for (int u = 0; u < kRows; u++) {
+                const uint32_t i = i0 + u * kLanes, dst = i == 0 ? d.z : i == nri - 1 ? d.w : d.x + i;
+                yo[u] = sc.mode == 2 && i < nri && dst < sc.nrows ? yext[dst] : T(0);
+            }
+#pragma unroll
+            for (int u = 0; u < kRows; u++) {
+                const uint32_t i = i0 + u * kLanes;
+                if (i >= nri) break;
+                const uint32_t dst = i == 0 ? d.z : i == nri - 1 ? d.w : d.x + i;
+                const T        v = ystage[i];
+                __builtin_nontemporal_store(dst < sc.nrows ? scale_row(sc, v, yo[u]) : v, yext + dst);
+            }
+        }
+        return;
+    }
     if (!epi.out) {
         // (y leaves past the caches -- nontemporal: on the headline's single image nobody on the chip reads it before the caller does, and its 7 MB need not
         // displace x or the window's lines in the L2s for the next SpMV: 21.05 -> 20.69 us on the web-Google shape, same box, three pairs of runs:
@@ -1075,7 +1117,7 @@ template <typename T, bool DICT, bool TAG, bool SNT>
 __global__ __launch_bounds__((RingLayout<T, DICT, TAG>::THREADS)) __attribute__((amdgpu_num_vgpr(kRingCap))) void spmv_ilv_kernel(
     const uint8_t *__restrict__ stream_a, const uint4 *__restrict__ desc_a, const uint2 *__restrict__ desc2_a, const T *__restrict__ x, T *__restrict__ yext_a, int G_alloc,
     uint32_t nchunks_a, uint32_t nblocks_per_xcd, int swz, uint32_t cmask, uint32_t xbytes_a, const T *__restrict__ dict_g, uint32_t ndict, uint32_t ystage_a, uint32_t col_bits,
-    uint32_t col_base_a, const PanelArgs *__restrict__ multi, uint32_t nw_compute, uint32_t help_ahead, uint32_t help_per_line, uint32_t flip)
+    uint32_t col_base_a, const PanelArgs *__restrict__ multi, uint32_t nw_compute, uint32_t help_ahead, uint32_t help_per_line, uint32_t flip, ScaleEpi sc)
 {
     using L = RingLayout<T, DICT, TAG>;
     constexpr int D = L::D, QN = 2 * D, XB = L::XB, QB = L::QB, K = (D - 1) * (4 + L::NS);
@@ -1257,7 +1299,7 @@ __global__ __launch_bounds__((RingLayout<T, DICT, TAG>::THREADS)) __attribute__(
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (uint32_t i = lane; i < nri; i += kLanes) {          // the rows leave coalesced (head / last row of a chunk that shares it: its carry slot)
         const uint32_t dst = i == 0 ? d.z : i == nri - 1 ? d.w : d.x + i;
-        store_y(yext + dst, ystage[i]);
+        store_y_rt(yext, dst, ystage[i], sc);
     }
 }
 
@@ -1387,7 +1429,7 @@ __global__ __launch_bounds__((RingLayout<T, DICT, TAG, kGangCap, 8>::THREADS)) _
     const uint8_t *__restrict__ stream_a, const uint4 *__restrict__ desc_a, const uint2 *__restrict__ desc2_a, const T *__restrict__ x, T *__restrict__ yext_a, int G_alloc,
     uint32_t nchunks_a, uint32_t nblocks_per_xcd, int swz, uint32_t cmask, uint32_t xbytes_a, const T *__restrict__ dict_g, uint32_t ndict, uint32_t ystage_a, uint32_t col_bits,
     uint32_t col_base_a, const PanelArgs *__restrict__ multi, uint32_t nw_compute, uint32_t help_ahead, uint32_t help_per_line, uint32_t flip, const uint32_t *__restrict__ gbase_a,
-    const FuseArgs *__restrict__ fuse, T *__restrict__ y_fused, uint32_t no_token)
+    const FuseArgs *__restrict__ fuse, T *__restrict__ y_fused, uint32_t no_token, ScaleEpi sc)
 {
     using L = RingLayout<T, DICT, TAG, kGangCap, 8>;          // (an x slot per ring position: a group's gathers never land in registers a step still reads)
     constexpr int D = L::D, QN = 2 * D, XB = L::XB, QB = L::QB, K = (D - 1) * (4 + L::NS), U = kGangUnit;
@@ -1602,7 +1644,7 @@ __global__ __launch_bounds__((RingLayout<T, DICT, TAG, kGangCap, 8>::THREADS)) _
         } else {
             for (uint32_t i = lane; i < nri; i += kLanes) {
                 const uint32_t dst = i == 0 ? d.z : i == nri - 1 ? d.w : d.x + i;
-                store_y(yext + dst, ystage[i]);
+                store_y_rt(yext, dst, ystage[i], sc);
             }
         }
     }
@@ -1613,7 +1655,7 @@ __global__ __launch_bounds__((RingLayout<T, DICT, TAG, kGangCap, 8>::THREADS)) _
 // row, fixed summation tree (replaces the atomics of spmv.cpp:1280-1282, 1640-1649)
 template <typename T>
 __global__ __launch_bounds__(kLanes * kWavesPerBlock) void fixup_kernel(const int64_t *__restrict__ shared, uint32_t nshared,
-                                                                        T *__restrict__ yext, uint32_t nrows)
+                                                                        T *__restrict__ yext, uint32_t nrows, ScaleEpi sc)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t s = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -1624,7 +1666,7 @@ __global__ __launch_bounds__(kLanes * kWavesPerBlock) void fixup_kernel(const in
     for (int64_t c = c0 + 1 + lane; c <= c1; c += kLanes) v += carry[2 * c];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) yext[row] = carry[2 * c0 + 1] + v;
+    if (lane == 0) store_y_rt(yext, (uint32_t)row, carry[2 * c0 + 1] + v, sc);      // (the scaled product: the row's final value, as every row here)
 }
 
 // the same for the nb vectors of a block of cvr_spmm_device (rows of ldy values): vector by vector, each summed as fixup_kernel sums it
@@ -1654,9 +1696,10 @@ __global__ __launch_bounds__(kLanes * kWavesPerBlock) void spmm_fixup_kernel(con
 // wiki-Talk shape: 6 % of the rows hold all the non-zeros -- a block of 1 024 rows has a few dozen partial sums per panel and the pass is
 // all launch and round-trip latency (2 339 workgroups, 13.7 us); with MUL = 8 a workgroup has eight times the entries per round trip and
 // there are an eighth of the workgroups.
-template <typename T, int kBatch, int kEach, int MUL, int NT = 256>
+// SC: the scaled product's write-out (ScaleEpi `sc`; the instantiations without it are the plain pass's, unchanged)
+template <typename T, int kBatch, int kEach, int MUL, int NT = 256, bool SC = false>
 __global__ __launch_bounds__(NT) void combine_kernel(const CombinePanel *__restrict__ panels, uint32_t npanels, const uint32_t *__restrict__ block_off,
-                                                      uint32_t nblocks, T *__restrict__ y, uint32_t nrows, uint32_t plain_store)
+                                                      uint32_t nblocks, T *__restrict__ y, uint32_t nrows, uint32_t plain_store, ScaleEpi sc)
 {
     // The loads of kBatch panels are issued together (kEach entries per thread and panel in registers), then added panel by panel:
     // one memory round trip per batch instead of one per panel in front of every barrier (16 panels: 54 -> 3x us on the
@@ -1720,7 +1763,16 @@ __global__ __launch_bounds__(NT) void combine_kernel(const CombinePanel *__restr
         }
     }
     // y is written past the caches (nontemporal): nobody on this chip reads it before the caller does, and it need not displace x or the image there
-    if (plain_store & 1u) for (uint32_t i = threadIdx.x; i < kRows && r0 + i < nrows; i += blockDim.x) y[r0 + i] = acc[i];
+    if constexpr (SC) {          // the scaled product: old y of up to eight rows per thread in flight, then their stores
+        constexpr uint32_t kPer = (kRows + NT - 1) / NT < 8 ? (kRows + NT - 1) / NT : 8;
+        for (uint32_t i0 = threadIdx.x; i0 < kRows; i0 += (uint32_t)NT * kPer) {
+            T yo[kPer];
+#pragma unroll
+            for (uint32_t e = 0; e < kPer; e++) { const uint32_t i = i0 + e * NT; yo[e] = sc.mode == 2 && i < kRows && r0 + i < nrows ? y[r0 + i] : T(0); }
+#pragma unroll
+            for (uint32_t e = 0; e < kPer; e++) { const uint32_t i = i0 + e * NT; if (i < kRows && r0 + i < nrows) __builtin_nontemporal_store(scale_row(sc, acc[i], yo[e]), &y[r0 + i]); }
+        }
+    } else if (plain_store & 1u) for (uint32_t i = threadIdx.x; i < kRows && r0 + i < nrows; i += blockDim.x) y[r0 + i] = acc[i];
     else for (uint32_t i = threadIdx.x; i < kRows && r0 + i < nrows; i += blockDim.x) __builtin_nontemporal_store(acc[i], &y[r0 + i]);
 }
 
@@ -1731,9 +1783,10 @@ __global__ __launch_bounds__(NT) void combine_kernel(const CombinePanel *__restr
 // all panels of two rows are in flight together.  The additions are combine_kernel's (panel order, absent sums skipped): the same bits.
 // com-Orkut shape: 40 MB of row numbers -> 3 MB of bitmap beside 160 MB of sums and 25 MB of y, 41.6 -> 33 us (profiles/r06_combine_bitmap.log); a
 // load instruction is issued per (row, panel) whether the sum exists or not, which is why sparsely filled shapes keep the row numbers.
-template <typename T, int PMAX>
+template <typename T, int PMAX, bool SC = false>
 __global__ __launch_bounds__(256) void combine_bits_kernel(const CombinePanel *__restrict__ panels, uint32_t npanels, const uint32_t *__restrict__ block_off, uint32_t nblocks,
-                                                           const uint32_t *__restrict__ bits, T *__restrict__ y, uint32_t nrows, const CutEntry *__restrict__ cut, uint32_t ncut)
+                                                           const uint32_t *__restrict__ bits, T *__restrict__ y, uint32_t nrows, const CutEntry *__restrict__ cut, uint32_t ncut,
+                                                           ScaleEpi sc)
 {
     __shared__ uint2    s_bp[PMAX][32];          // .x = the word's bits, .y = set bits of the panel in the block's words before it
     __shared__ uint32_t s_lo[PMAX];
@@ -1794,11 +1847,20 @@ __global__ __launch_bounds__(256) void combine_bits_kernel(const CombinePanel *_
                 if (c.x & mB) { hasB |= 1u << p; vB[p] = __builtin_nontemporal_load(zp[p] + (lo[p] + c.y + (uint32_t)__popc(c.x & (mB - 1u)))); }
             }
         }
+        T yA = T(0), yB = T(0);          // (the scaled product: old y of the two rows, issued behind the panels' loads)
+        if constexpr (SC) {
+            if (sc.mode == 2 && r0 + iA < nrows) yA = y[r0 + iA];
+            if (sc.mode == 2 && r0 + iB < nrows) yB = y[r0 + iB];
+        }
         T accA = T(0), accB = T(0);
 #pragma unroll
         for (int p = 0; p < PMAX; p++) {
             if (hasA & (1u << p)) accA += vA[p];
             if (hasB & (1u << p)) accB += vB[p];
+        }
+        if constexpr (SC) {
+            accA = scale_row(sc, accA, yA);
+            accB = scale_row(sc, accB, yB);
         }
         if (r0 + iA < nrows) __builtin_nontemporal_store(accA, &y[r0 + iA]);
         if (r0 + iB < nrows) __builtin_nontemporal_store(accB, &y[r0 + iB]);
@@ -1870,6 +1932,10 @@ __global__ __launch_bounds__(kLanes * 4) void fixup_multi_kernel(const FixPart *
 
 }  // namespace
 
+// run-time flags -> template arguments, without macro towers: with_flag(v, f) calls f(std::true_type / false_type)
+template <typename F> inline void with_flag(bool v, F &&f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> inline void with_real(bool f32, F &&f) { if (f32) f(float{}); else f(double{}); }
+
 hipError_t launch_fixup_multi(const FixPart *parts, uint32_t nparts, uint32_t max_nshared, bool f32, hipStream_t st)
 {
     if (nparts == 0 || max_nshared == 0) return hipSuccess;
@@ -1895,43 +1961,48 @@ hipError_t launch_cut_table(const FixPart *parts, uint32_t nparts, uint32_t max_
 }
 
 hipError_t launch_combine(const CombinePanel *panels, uint32_t npanels, const uint32_t *block_off, void *y, uint32_t nrows, bool f32, hipStream_t st, int batch, int mul, const uint32_t *bits, const CutEntry *cut,
-                          uint32_t ncut)
+                          uint32_t ncut, const ScaleEpi *sc)
 {
     if (nrows == 0) return hipSuccess;
     const uint32_t nblocks = (nrows + kCombineRows - 1) / kCombineRows;
+    const ScaleEpi scv = sc ? *sc : ScaleEpi{};
     if (bits && mul == 1 && npanels <= 16u) {          // the bitmap form (combine_bits_kernel)
-        if (npanels <= 8u) {
-            if (f32) hipLaunchKernelGGL((combine_bits_kernel<float, 8>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<float *>(y), nrows, cut, ncut);
-            else hipLaunchKernelGGL((combine_bits_kernel<double, 8>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<double *>(y), nrows, cut, ncut);
-        } else {
-            if (f32) hipLaunchKernelGGL((combine_bits_kernel<float, 16>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<float *>(y), nrows, cut, ncut);
-            else hipLaunchKernelGGL((combine_bits_kernel<double, 16>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<double *>(y), nrows, cut, ncut);
-        }
+        with_flag(scv.mode != 0, [&](auto SCF) {
+            constexpr bool kSc = decltype(SCF)::value;
+            if (npanels <= 8u) {
+                if (f32) hipLaunchKernelGGL((combine_bits_kernel<float, 8, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<float *>(y), nrows, cut, ncut, scv);
+                else hipLaunchKernelGGL((combine_bits_kernel<double, 8, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<double *>(y), nrows, cut, ncut, scv);
+            } else {
+                if (f32) hipLaunchKernelGGL((combine_bits_kernel<float, 16, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<float *>(y), nrows, cut, ncut, scv);
+                else hipLaunchKernelGGL((combine_bits_kernel<double, 16, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, bits, static_cast<double *>(y), nrows, cut, ncut, scv);
+            }
+        });
         return hipGetLastError();
     }
     const uint32_t plain = (cvr::debug_env("combine_plain_store") ? 1u : 0u) | (cvr::debug_env("combine_plain_loads") ? 2u : 0u);
-    auto go = [&](auto real) {
+    auto go = [&](auto real, auto SCF) {
         using T = decltype(real);
+        constexpr bool kSc = decltype(SCF)::value;
         T *yt = static_cast<T *>(y);
         // batch: 4 / 8 = that many panels per round trip with four entries per thread each; 16 / 17 = sixteen panels with two / one; 9 - 12 (eight blocks per
         // workgroup only): 1 024 or 512 threads -- 9 = 8 panels x 1 entry x 1 024 threads, 10 = 8 x 2 x 1 024, 11 = 8 x 2 x 512, 12 = 16 x 1 x 1 024
         if (mul == 8) {
             const uint32_t grid = (nblocks + 7) / 8;
-            if (batch >= 16) hipLaunchKernelGGL((combine_kernel<T, 16, 2, 8>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 9) hipLaunchKernelGGL((combine_kernel<T, 8, 1, 8, 1024>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);      // (1 024 threads for the eight blocks)
-            else if (batch == 10) hipLaunchKernelGGL((combine_kernel<T, 8, 2, 8, 1024>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 11) hipLaunchKernelGGL((combine_kernel<T, 8, 2, 8, 512>), dim3(grid), dim3(512), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 12) hipLaunchKernelGGL((combine_kernel<T, 16, 1, 8, 1024>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 8) hipLaunchKernelGGL((combine_kernel<T, 8, 4, 8>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else hipLaunchKernelGGL((combine_kernel<T, 4, 4, 8>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
+            if (batch >= 16) hipLaunchKernelGGL((combine_kernel<T, 16, 2, 8, 256, kSc>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 9) hipLaunchKernelGGL((combine_kernel<T, 8, 1, 8, 1024, kSc>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);      // (1 024 threads for the eight blocks)
+            else if (batch == 10) hipLaunchKernelGGL((combine_kernel<T, 8, 2, 8, 1024, kSc>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 11) hipLaunchKernelGGL((combine_kernel<T, 8, 2, 8, 512, kSc>), dim3(grid), dim3(512), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 12) hipLaunchKernelGGL((combine_kernel<T, 16, 1, 8, 1024, kSc>), dim3(grid), dim3(1024), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 8) hipLaunchKernelGGL((combine_kernel<T, 8, 4, 8, 256, kSc>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else hipLaunchKernelGGL((combine_kernel<T, 4, 4, 8, 256, kSc>), dim3(grid), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
         } else {
-            if (batch == 17) hipLaunchKernelGGL((combine_kernel<T, 16, 1, 1>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 16) hipLaunchKernelGGL((combine_kernel<T, 16, 2, 1>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else if (batch == 8) hipLaunchKernelGGL((combine_kernel<T, 8, 4, 1>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
-            else hipLaunchKernelGGL((combine_kernel<T, 4, 4, 1>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain);
+            if (batch == 17) hipLaunchKernelGGL((combine_kernel<T, 16, 1, 1, 256, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 16) hipLaunchKernelGGL((combine_kernel<T, 16, 2, 1, 256, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else if (batch == 8) hipLaunchKernelGGL((combine_kernel<T, 8, 4, 1, 256, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
+            else hipLaunchKernelGGL((combine_kernel<T, 4, 4, 1, 256, kSc>), dim3(nblocks), dim3(256), 0, st, panels, npanels, block_off, nblocks, yt, nrows, plain, scv);
         }
     };
-    if (f32) go(float{}); else go(double{});
+    with_flag(scv.mode != 0, [&](auto SCF) { if (f32) go(float{}, SCF); else go(double{}, SCF); });
     return hipGetLastError();
 }
 
@@ -2038,6 +2109,28 @@ hipError_t launch_fuse_patch(const uint32_t *rows_list, uint32_t nlist, const Fu
 }
 
 bool iter_epilogue_ok(const DeviceImage &img) { return img.phases > 1 && !img.ilv && img.nshared == 0 && img.nchunks > 0 && (img.nchunks + (img.wpb > 1 ? img.wpb : 1) - 1) / (img.wpb > 1 ? img.wpb : 1) <= 1024u; }
+// every kernel of a single image writes its rows' final values through the epilogue; a panel launch writes partial sums (the combine pass takes it)
+bool scale_fused_ok(const DeviceImage &, bool multi) { return !multi; }
+
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void axpby_kernel(const T *__restrict__ t, T *__restrict__ y, int64_t n, ScaleEpi sc)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        if (t) y[i] = scale_row(sc, t[i], sc.mode == 2 ? y[i] : T(0));
+        else y[i] = sc.mode == 2 ? (T)sc.beta * y[i] : T(0);
+    }
+}
+}  // namespace
+
+hipError_t launch_axpby(const void *t, void *y, int64_t n, bool f32, const ScaleEpi &sc, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    const uint32_t grid = (uint32_t)std::min<int64_t>((n + 255) / 256, 8192);
+    if (f32) hipLaunchKernelGGL(axpby_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(t), static_cast<float *>(y), n, sc);
+    else hipLaunchKernelGGL(axpby_kernel<double>, dim3(grid), dim3(256), 0, st, static_cast<const double *>(t), static_cast<double *>(y), n, sc);
+    return hipGetLastError();
+}
 
 size_t spmv_lds_bytes(const DeviceImage &img)
 {
@@ -2047,13 +2140,13 @@ size_t spmv_lds_bytes(const DeviceImage &img)
     return (size_t)(wpb * (slots + img.ystage) + (img.dict ? kDictMax : 0) + (use_win ? ((img.hub_n + 3u) & ~3u) + img.win_elems + 4 : 0)) * (img.f32 ? 4 : 8) + (img.phases > 1 ? 16 : 0) + (img.ilv ? 64 : 0);      // (column phases: + the arrival counter of the iterative epilogue; interleaved: + the progress words of the computing wavefronts)
 }
 
-// run-time flags -> template arguments, without macro towers: with_flag(v, f) calls f(std::true_type / false_type)
-template <typename F> inline void with_flag(bool v, F &&f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
-template <typename F> inline void with_real(bool f32, F &&f) { if (f32) f(float{}); else f(double{}); }
 
 hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, hipStream_t st, bool with_fixup, const PanelArgs *multi, uint32_t multi_chunks, uint32_t multi_rounds,
-                       const IterEpilogue *epi, const FuseArgs *fuse, void *y_fused)
+                       const IterEpilogue *epi, const FuseArgs *fuse, void *y_fused, const ScaleEpi *sc)
 {
+    if (sc && sc->mode == 0) sc = nullptr;
+    if (sc && (!scale_fused_ok(img, multi != nullptr) || epi || fuse)) return hipErrorInvalidValue;
+    const ScaleEpi scv = sc ? *sc : ScaleEpi{};
     if (img.nchunks == 0 && !multi) return hipSuccess;
     if (fuse && !(img.gang && multi && y_fused)) return hipErrorInvalidValue;
     if (epi && (multi || !iter_epilogue_ok(img))) return hipErrorInvalidValue;
@@ -2099,19 +2192,24 @@ hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, h
                         const uint32_t roomg = (uint32_t)LG::THREADS / kLanes, Hg = fuse ? 0u : roomg > wpb ? std::min<uint32_t>(roomg - wpb, img.ilv_helpers * wpb) : 0u;      // helpers: all on the gang's stream (none with the fused combine: its barriers are the whole workgroup's)
                         with_flag(img.ilv_stream_nt != 0, [&](auto SN) {
                             hipLaunchKernelGGL((spmv_gang_kernel<T, kDict, decltype(TG)::value, decltype(SN)::value>), dim3(grid), dim3(kLanes * (wpb + Hg)), lds, st, img.stream, img.desc, img.desc2, x, y, img.G, img.nchunks, per, swz,
-                                               img.col_mask, (uint32_t)xb, dict, img.ndict, img.ystage, img.col_bits, img.col_base, multi, wpb, img.ilv_ahead, img.ilv_per_line, img.flip_now, img.gbase, fuse, static_cast<T *>(y_fused), cvr::debug_env("gang_no_token") ? 1u : 0u);
+                                               img.col_mask, (uint32_t)xb, dict, img.ndict, img.ystage, img.col_bits, img.col_base, multi, wpb, img.ilv_ahead, img.ilv_per_line, img.flip_now, img.gbase, fuse, static_cast<T *>(y_fused), cvr::debug_env("gang_no_token") ? 1u : 0u, scv);
                         });
                         return;
                     }
                     with_flag(img.ilv_stream_nt != 0, [&](auto SN) {
                         hipLaunchKernelGGL((spmv_ilv_kernel<T, kDict, decltype(TG)::value, decltype(SN)::value>), dim3(grid), dim3(kLanes * wpb * (1u + H)), lds, st, img.stream, img.desc, img.desc2, x, y, img.G, img.nchunks, per, swz,
-                                           img.col_mask, (uint32_t)xb, dict, img.ndict, img.ystage, img.col_bits, img.col_base, multi, wpb, img.ilv_ahead, img.ilv_per_line, img.flip_now);
+                                           img.col_mask, (uint32_t)xb, dict, img.ndict, img.ystage, img.col_bits, img.col_base, multi, wpb, img.ilv_ahead, img.ilv_per_line, img.flip_now, scv);
                     });
                 });
             } else if (img.phases > 1) {    // column phases: every piece carries its row
                 with_flag(img.tag16, [&](auto TG) { with_flag(use_win, [&](auto WI) { with_flag(loaders > 0, [&](auto LD) {
                     constexpr int kWin = decltype(WI)::value ? 1 : 0;
                     if constexpr (decltype(LD)::value && !decltype(WI)::value) return;          // (loaders only come with a window)
+                    else if (sc) {          // the scaled product's instantiation (never with the time stamps or the iterative epilogue)
+                        hipLaunchKernelGGL((spmv_seg_kernel<T, 1, 1, kWin, kDict, decltype(LD)::value, decltype(TG)::value, false, true>), dim3(grid), dim3(kLanes * (wpb + loaders)), lds, st, img.stream,
+                                           img.desc, x, y, img.G, img.nchunks, per, swz, img.col_mask, (uint32_t)xb, img.win_base, img.win_elems, dict, img.ndict, img.ystage, img.desc2, img.col_bits,
+                                           wpb, 0, multi, IterEpilogue{}, static_cast<unsigned long long *>(nullptr), scv);
+                    }
                     else if (img.prof && !multi && !epi && std::is_same<T, double>::value && kDict && decltype(LD)::value && !decltype(TG)::value) {
                         // the same kernel with its phases' time stamps (CVR_DEBUG=phase_clocks): that one instantiation exists -- fp64, dictionary, loader
                         // wavefronts, no 16-bit tags, the headline's --; every other layout runs its ordinary kernel (it used to launch nothing and leave y as it was)
@@ -2126,16 +2224,18 @@ hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, h
                 }); }); });
             } else if (img.c16 && !use_win && !kDict && wpb == 1 && !multi) {          // narrow chunks (banded matrices)
                 if constexpr (!kDict)
-                    hipLaunchKernelGGL((spmv_kernel<T, 1, kPolDefault, 1, 0, false, false, true>), dim3(grid), dim3(kLanes), lds, st, img.stream, img.desc, img.target, x, y, img.G, img.nchunks, per, swz,
-                                       img.col_mask, (uint32_t)xb, img.win_base, 0u, static_cast<const T *>(nullptr), 0u, img.ystage, static_cast<const T *>(nullptr), 0u, kstride, img.cbase, img.pad_col,
-                                       static_cast<const PanelArgs *>(nullptr), img.stream_mod);
+                    with_flag(sc != nullptr, [&](auto SC) {
+                        hipLaunchKernelGGL((spmv_kernel<T, 1, kPolDefault, 1, 0, false, false, true, decltype(SC)::value>), dim3(grid), dim3(kLanes), lds, st, img.stream, img.desc, img.target, x, y, img.G,
+                                           img.nchunks, per, swz, img.col_mask, (uint32_t)xb, img.win_base, 0u, static_cast<const T *>(nullptr), 0u, img.ystage, static_cast<const T *>(nullptr), 0u,
+                                           kstride, img.cbase, img.pad_col, static_cast<const PanelArgs *>(nullptr), img.stream_mod, scv);
+                    });
             } else {                        // the general kernel: rows handed out by ballot / rank; LDS table: none, a window of x, or a hub table
                 with_flag(wpb > 1, [&](auto MW) {
-                    auto go = [&](auto W) {
-                        hipLaunchKernelGGL((spmv_kernel<T, 1, kPolDefault, 1, decltype(W)::value, kDict, decltype(MW)::value, false>), dim3(grid), dim3(kLanes * wpb), lds, st, img.stream, img.desc, img.target,
-                                           x, y, img.G, img.nchunks, per, swz, img.col_mask, (uint32_t)xb, img.win_base, img.win_elems, dict, img.ndict, img.ystage, static_cast<const T *>(img.hub_x),
-                                           img.hub_n, kstride, img.cbase, img.pad_col, multi, img.stream_mod);
-                    };
+                    auto go = [&](auto W) { with_flag(sc != nullptr, [&](auto SC) {
+                        hipLaunchKernelGGL((spmv_kernel<T, 1, kPolDefault, 1, decltype(W)::value, kDict, decltype(MW)::value, false, decltype(SC)::value>), dim3(grid), dim3(kLanes * wpb), lds, st, img.stream,
+                                           img.desc, img.target, x, y, img.G, img.nchunks, per, swz, img.col_mask, (uint32_t)xb, img.win_base, img.win_elems, dict, img.ndict, img.ystage,
+                                           static_cast<const T *>(img.hub_x), img.hub_n, kstride, img.cbase, img.pad_col, multi, img.stream_mod, scv);
+                    }); };
                     if (use_win && img.hub_n && img.ilv_stream_nt) go(std::integral_constant<int, 3>{}); else if (use_win && img.hub_n) go(std::integral_constant<int, 2>{}); else if (use_win) go(std::integral_constant<int, 1>{}); else go(std::integral_constant<int, 0>{});
                 });
             }
@@ -2144,7 +2244,7 @@ hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, h
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || img.nshared == 0 || !with_fixup) return e;
     const uint32_t fb = (img.nshared + kWavesPerBlock - 1) / kWavesPerBlock;
-    with_real(img.f32, [&](auto real) { using T = decltype(real); hipLaunchKernelGGL(fixup_kernel<T>, dim3(fb), dim3(kLanes * kWavesPerBlock), 0, st, img.shared, img.nshared, static_cast<T *>(y_ext), img.nrows); });
+    with_real(img.f32, [&](auto real) { using T = decltype(real); hipLaunchKernelGGL(fixup_kernel<T>, dim3(fb), dim3(kLanes * kWavesPerBlock), 0, st, img.shared, img.nshared, static_cast<T *>(y_ext), img.nrows, scv); });
     return hipGetLastError();
 }
 

@@ -237,6 +237,19 @@ int cvr_spmm_device(cvr_handle *h, const void *X_dev, int64_t ldx, void *Y_dev, 
 int cvr_spmm(cvr_handle *h, const void *X_host, void *Y_host, int32_t nvec, int iters, cvr_timing *timing);
 /* 1: the handle's image runs cvr_spmm_device for any nvec; 0: it only takes nvec = 1 with ldx = ldy = 1 (any layout) */
 int cvr_spmm_supported(const cvr_handle *h);
+/* y = alpha * A x + beta * y on the device: cvr_spmv_device with the scaling done where each row is written (the SpMV kernel's write-out,
+ * the fix-up of rows cut over chunks, the combine pass of column panels): no pass of its own, one read of old y.  Buffers as for
+ * cvr_spmv_device: x_dev holds info.x_elems values with x_dev[ncols] == 0; y_dev holds info.yext_elems values, the first nrows are y (input
+ * when beta != 0, always output), the rest is scratch.  Arithmetic in the handle's type T: alpha and beta are rounded to T first, then
+ * y[i] = (alpha * s_i) + (beta * y_old[i]) with each product and the sum rounded on their own (no fused multiply-add), where s_i is bit for
+ * bit the y[i] of cvr_spmv_device for the same x (+0 for rows without non-zeros).  beta == 0: y is not read (NaN or Inf there have no
+ * effect) and y[i] = alpha * s_i.  alpha == 0: neither the matrix nor x is read (x may be NULL), y[i] = beta * y_old[i], or +0 when beta is
+ * 0 too.  Asynchronous on `stream` (NULL = HIP's null stream), capturable in a HIP graph and ordered with other launches as
+ * cvr_spmv_device is.  Every single-GPU handle.  Errors: null handle or y, or null x with alpha != 0: CVR_ERR_INVALID before any device
+ * work; a handle before cvr_preprocess: CVR_ERR_STATE. */
+int cvr_spmv_scaled_device(cvr_handle *h, double alpha, const void *x_dev, double beta, void *y_dev, void *stream);
+/* the same with host x (ncols values) and y (nrows values, in and out); synchronous, one launch, no timing loop */
+int cvr_spmv_scaled(cvr_handle *h, double alpha, const void *x_host, double beta, void *y_host);
 /* New values for a handle created with cvr_options.mutable_values = 1: the same sparsity pattern, other values.  vals_dev is a device array
  * of the handle's device (double or float by is_f32), indexed exactly like the cvr_csr_view.vals the handle was created from: element i is
  * the value of CSR position i, 0 <= i < row_ptr[nrows].  One kernel writes them into the image (value block of every group, through the
