@@ -47,6 +47,15 @@ class Options(C.Structure):
     def mutable_values(self, v):
         self.reserved[0] = int(v)
 
+    # cvr_options.transpose took reserved[1], the last reserved word: the handle of A^T built on the device from A's CSR
+    @property
+    def transpose(self):
+        return self.reserved[1]
+
+    @transpose.setter
+    def transpose(self, v):
+        self.reserved[1] = int(v)
+
 
 class Timing(C.Structure):
     _fields_ = [("iters", C.c_int32), ("mean_s", C.c_double), ("min_s", C.c_double), ("max_s", C.c_double),
@@ -377,8 +386,10 @@ class CvrMatrix:
     def __init__(self, nrows, ncols, row_ptr, col_idx, vals, device=0, steps_per_chunk=0, split_threshold=0,
                  xcd_swizzle=-1, x_window=-1, keep_csr=False, debug_col_mask=0,
                  col_panels=-1, value_dict=-1, tune_steps=False, waves_per_block=0, col_phases=-1, hub_table=-1, narrow_cols=-1, hub_reorder=-1,
-                 row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
-        """mutable_values=1: the handle takes new values of the same pattern later (update_values, update_values_device; no value dictionary).
+                 row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0, transpose=0):
+        """transpose=1: the handle of A^T, built on the device from this CSR of A (cvr_options.transpose): nrows / ncols of the object are
+        A's ncols / nrows, x has nrows(A) values, y ncols(A); update_values takes values indexed like A's vals.
+        mutable_values=1: the handle takes new values of the same pattern later (update_values, update_values_device; no value dictionary).
         tune_steps: choose steps_per_chunk by measurement first (cvr_tune_steps; its cost is self.tuning_s).
         nvec >= 2: the plain layout, for spmm() / spmm_device() with up to that many vectors at once (cvr_options.nvec).
         debug_col_mask is a profiling knob (tools/sweep.py): it travels through the environment (CVR_DEBUG_COL_MASK), not through cvr_options."""
@@ -398,7 +409,7 @@ class CvrMatrix:
         view = CsrView(nrows, ncols, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(self.f32))
         self._build(view, nrows, ncols, device, steps_per_chunk, split_threshold, xcd_swizzle, x_window, keep_csr,
                     debug_col_mask, col_panels, value_dict, tune_steps, waves_per_block, col_phases, hub_table, narrow_cols, hub_reorder,
-                    row_tags16, row_bands, piece_max, interleave, gang, nvec, mutable_values)
+                    row_tags16, row_bands, piece_max, interleave, gang, nvec, mutable_values, transpose)
 
     def save_image(self, path, key=None):
         """cvr_save_image: the converted image on disk, keyed by `key` (capi.source_key of the .mtx file; None = no source key),
@@ -408,7 +419,7 @@ class CvrMatrix:
             raise CvrError(rc, "cvr_save_image")
 
     @classmethod
-    def from_image(cls, path, key=None, device=0, nvec=0, mutable_values=0, **options):
+    def from_image(cls, path, key=None, device=0, nvec=0, mutable_values=0, transpose=0, **options):
         """cvr_load_image: a handle from a saved image (CvrError with code ERR_STATE when the file was written for another source,
         other options -- nvec among them --, another device geometry or library version)"""
         self = cls.__new__(cls)
@@ -419,6 +430,7 @@ class CvrMatrix:
         opt.device = device
         opt.nvec = nvec
         opt.mutable_values = mutable_values
+        opt.transpose = transpose
         for k, v in options.items():
             setattr(opt, k, v)
         sec = C.c_double()
@@ -436,9 +448,10 @@ class CvrMatrix:
 
     @classmethod
     def from_device(cls, nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0, steps_per_chunk=0,
-                    split_threshold=0, keep_csr=False, col_panels=-1, value_dict=-1, tune_steps=False, hub_table=-1, hub_reorder=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
+                    split_threshold=0, keep_csr=False, col_panels=-1, value_dict=-1, tune_steps=False, hub_table=-1, hub_reorder=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0,
+                    transpose=0):
         """CSR arrays already in the memory of `device` (raw pointers: int64 row_ptr[nrows+1], int32 col_idx, fp64/fp32 vals),
-        e.g. the .data_ptr() of torch tensors: cvr_csr_view.arrays_on_device = 1"""
+        e.g. the .data_ptr() of torch tensors: cvr_csr_view.arrays_on_device = 1 (transpose=1: the handle of A^T, as in __init__)"""
         self = cls.__new__(cls)
         self._h = C.c_void_p()
         self.tuning_s = 0.0
@@ -446,12 +459,13 @@ class CvrMatrix:
         self.dtype = np.float32 if self.f32 else np.float64
         view = CsrView(nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev, int(self.f32), 1)
         self._build(view, nrows, ncols, device, steps_per_chunk, split_threshold, -1, -1, keep_csr, 0, col_panels, value_dict, tune_steps,
-                    hub_table=hub_table, hub_reorder=hub_reorder, interleave=interleave, gang=gang, nvec=nvec, mutable_values=mutable_values)
+                    hub_table=hub_table, hub_reorder=hub_reorder, interleave=interleave, gang=gang, nvec=nvec, mutable_values=mutable_values,
+                    transpose=transpose)
         return self
 
     def _build(self, view, nrows, ncols, device, steps_per_chunk, split_threshold, xcd_swizzle, x_window, keep_csr,
                debug_col_mask, col_panels, value_dict, tune_steps, waves_per_block=0, col_phases=-1, hub_table=-1, narrow_cols=-1, hub_reorder=-1,
-               row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0):
+               row_tags16=-1, row_bands=-1, piece_max=-1, interleave=-1, gang=-1, nvec=0, mutable_values=0, transpose=0):
         opt = Options()
         lib().cvr_default_options(C.byref(opt))
         opt.device, opt.steps_per_chunk, opt.split_threshold = device, steps_per_chunk, split_threshold
@@ -462,6 +476,7 @@ class CvrMatrix:
         opt.gang = gang
         opt.nvec = nvec
         opt.mutable_values = mutable_values
+        opt.transpose = transpose
         # profiling knobs (tools/sweep.py): cvr_create / cvr_tune read them from the environment.  Only a knob the caller passed is
         # touched, and what the environment held before comes back once the handle exists (a value the user exported stays theirs).
         saved = {}
@@ -498,7 +513,7 @@ class CvrMatrix:
         self.preprocess_s = sec.value
         self.info = Info()
         lib().cvr_get_info(self._h, C.byref(self.info))
-        self.nrows, self.ncols = nrows, ncols
+        self.nrows, self.ncols = self.info.nrows, self.info.ncols          # (the handle's: A^T's with transpose=1)
 
     def spmv(self, x, iters=1):
         """y = A x through host buffers; returns (y, Timing)"""

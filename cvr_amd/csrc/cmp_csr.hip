@@ -173,6 +173,50 @@ int cmp_csr_bench(cmp_csr *c, int kind, int warmup, int iters, double *mean_s, d
     return 0;
 }
 
+// rocSPARSE's csr2csc (numeric: pattern and values) of the comparator's device CSR -- the transpose a caller of rocSPARSE would run to get
+// the CSR of A^T: mean seconds per call over `iters` back-to-back calls (HIP events), behind `warmup` untimed ones; output arrays and work
+// buffer are allocated once, outside the timing.  *csc_col_ptr_last (may be NULL): the last column pointer (= nnz) as a sanity check.
+int cmp_csr2csc_bench(cmp_csr *c, int warmup, int iters, double *mean_s, long long *csc_col_ptr_last)
+{
+    const size_t vs = c->f32 ? 4 : 8, nz = (size_t)(c->nnz ? c->nnz : 1);
+    size_t       bytes = 0;
+    RSC(rocsparse_csr2csc_buffer_size(c->rs, c->nrows, c->ncols, (rocsparse_int)c->nnz, c->rp, c->ci, rocsparse_action_numeric, &bytes));
+    void *work = nullptr, *cv = nullptr, *cr = nullptr, *cp = nullptr;
+    int   rc = 0;
+    auto  once = [&]() -> int {
+        if (c->f32)
+            RSC(rocsparse_scsr2csc(c->rs, c->nrows, c->ncols, (rocsparse_int)c->nnz, static_cast<const float *>(c->va), c->rp, c->ci, static_cast<float *>(cv),
+                                   static_cast<rocsparse_int *>(cr), static_cast<rocsparse_int *>(cp), rocsparse_action_numeric, rocsparse_index_base_zero, work));
+        else
+            RSC(rocsparse_dcsr2csc(c->rs, c->nrows, c->ncols, (rocsparse_int)c->nnz, static_cast<const double *>(c->va), c->rp, c->ci, static_cast<double *>(cv),
+                                   static_cast<rocsparse_int *>(cr), static_cast<rocsparse_int *>(cp), rocsparse_action_numeric, rocsparse_index_base_zero, work));
+        return 0;
+    };
+    auto run = [&]() -> int {
+        HIPC(hipMalloc(&work, bytes ? bytes : 16));
+        HIPC(hipMalloc(&cv, vs * nz));
+        HIPC(hipMalloc(&cr, 4 * nz));
+        HIPC(hipMalloc(&cp, 4 * ((size_t)c->ncols + 1)));
+        for (int i = 0; i < warmup; i++) { const int r = once(); if (r) return r; }
+        HIPC(hipEventRecord(c->e0, c->st));
+        for (int i = 0; i < iters; i++) { const int r = once(); if (r) return r; }
+        HIPC(hipEventRecord(c->e1, c->st));
+        HIPC(hipEventSynchronize(c->e1));
+        float ms = 0;
+        HIPC(hipEventElapsedTime(&ms, c->e0, c->e1));
+        if (mean_s) *mean_s = ms * 1e-3 / (iters > 0 ? iters : 1);
+        if (csc_col_ptr_last) {
+            rocsparse_int last = 0;
+            HIPC(hipMemcpy(&last, static_cast<rocsparse_int *>(cp) + c->ncols, sizeof(last), hipMemcpyDeviceToHost));
+            *csc_col_ptr_last = last;
+        }
+        return 0;
+    };
+    rc = run();
+    for (void *p : {work, cv, cr, cp}) if (p) (void)hipFree(p);
+    return rc;
+}
+
 int cmp_csr_destroy(cmp_csr *c)
 {
     if (!c) return 0;

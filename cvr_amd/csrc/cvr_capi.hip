@@ -378,6 +378,34 @@ int check_rows_device(const int64_t *rp_dev, int64_t nrows, int64_t *rp0, int64_
     *rp0 = host[0]; *rpn = host[1];
     return CVR_OK;
 }
+// device arrays: the checks of row_ptr -- on the host below device_plan_rows() rows (the copy comes back in rp_host), by a kernel from there on
+// (*rows_on_device: row_ptr never comes to the host) --; *j0 / *j1 = row_ptr[0] / row_ptr[nrows].  The column range is checked apart.
+int check_rows_of_device_csr(const cvr_csr_view &v, std::vector<int64_t> &rp_host, bool *rows_on_device, int64_t *j0, int64_t *j1)
+{
+    *rows_on_device = false; *j0 = 0; *j1 = 0;
+    int rc;
+    if (v.nrows >= device_plan_rows() && v.nrows > 0 && !cvr::debug_env("device_rows_to_host")) {
+        // a matrix the device plans anyway: its row pointers are checked and used where they are (rows_on_device)
+        cvr_csr_view shape = v;
+        shape.nrows = 0; shape.row_ptr = nullptr;                 // (the checks of check_csr that need no rows: sizes, ncols, x within 4 GiB)
+        rc = check_csr(&shape, false);
+        if (rc) return rc;
+        rc = check_rows_device(v.row_ptr, v.nrows, j0, j1);
+        if (rc) return rc;
+        if (*j1 > *j0 && (!v.col_idx || !v.vals)) return fail(CVR_ERR_INVALID, "col_idx / vals is null");
+        *rows_on_device = true;
+    } else {
+        rp_host.resize((size_t)v.nrows + 1, 0);
+        if (v.nrows > 0) HIP_TRY(hipMemcpy(rp_host.data(), v.row_ptr, sizeof(int64_t) * rp_host.size(), hipMemcpyDeviceToHost));
+        cvr_csr_view hv = v;
+        hv.row_ptr = rp_host.data();
+        rc = check_csr(&hv, false);
+        if (rc) return rc;
+        *j0 = rp_host.front(); *j1 = rp_host.back();
+    }
+    return CVR_OK;
+}
+
 int check_columns_device(const int32_t *ci_dev, int64_t j0, int64_t j1, int64_t ncols)
 {
     if (j1 <= j0) return CVR_OK;
@@ -488,7 +516,14 @@ struct PhaseClock {
 };
 }  // namespace
 
-int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *opt_in)
+// what the create of A^T's CSR takes from A (cvr_options.transpose with mutable_values): the creation values, indexed like A's vals
+struct PositionSource {
+    const void   *vals;
+    hipMemcpyKind kind;
+    int64_t       nvals;        // A's row_ptr[nrows]
+};
+
+static int create_impl(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *opt_in, const PositionSource *src)
 {
     cvr::debug_refresh();          // (first: everything below, the phase clock included, reads this call's CVR_DEBUG)
     PhaseClock clk;
@@ -548,25 +583,9 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
         if (hostv.nrows < 0 || hostv.ncols < 0 || (hostv.nrows > 0 && !hostv.row_ptr)) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
         HIP_TRY(hipSetDevice(opt.device));
         int64_t j0 = 0, j1 = 0;
-        if (hostv.nrows >= device_plan_rows() && hostv.nrows > 0 && !cvr::debug_env("device_rows_to_host")) {
-            // a matrix the device plans anyway: its row pointers are checked and used where they are (rows_on_device)
-            cvr_csr_view shape = hostv;
-            shape.nrows = 0; shape.row_ptr = nullptr;                 // (the checks of check_csr that need no rows: sizes, ncols, x within 4 GiB)
-            rc = check_csr(&shape, false);
-            if (rc) return rc;
-            rc = check_rows_device(hostv.row_ptr, hostv.nrows, &j0, &j1);
-            if (rc) return rc;
-            if (j1 > j0 && (!hostv.col_idx || !hostv.vals)) return fail(CVR_ERR_INVALID, "col_idx / vals is null");
-            rows_on_device = true;
-            hostv.row_ptr = nullptr;                                   // (nothing below may read rows on the host)
-        } else {
-            rp_host.resize((size_t)hostv.nrows + 1, 0);
-            if (hostv.nrows > 0) HIP_TRY(hipMemcpy(rp_host.data(), hostv.row_ptr, sizeof(int64_t) * rp_host.size(), hipMemcpyDeviceToHost));
-            hostv.row_ptr = rp_host.data();
-            rc = check_csr(&hostv, false);
-            if (rc) return rc;
-            j0 = rp_host.front(); j1 = rp_host.back();
-        }
+        rc = check_rows_of_device_csr(hostv, rp_host, &rows_on_device, &j0, &j1);
+        if (rc) return rc;
+        hostv.row_ptr = rows_on_device ? nullptr : rp_host.data();      // (rows on the device: nothing below may read rows on the host)
         dev_j0 = j0; dev_j1 = j1;
         if (opt.mutable_values && j1 >= (int64_t)cvr::kNoSource) return fail(CVR_ERR_INVALID, "mutable_values: row_ptr[nrows] must stay below 2^32 - 1");
         rc = check_columns_device(hostv.col_idx, j0, j1, hostv.ncols);
@@ -645,16 +664,19 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     const double t_up0 = now_s();
     if (opt.mutable_values) {
         // the caller's values wait on the device until cvr_preprocess writes them through the map (cvr_update.hip); everything from here to
-        // the image reads CSR positions instead: element i = i + 1 (device memory, also for host arrays -- the host split is not taken)
-        const int64_t nv = rows_on_device ? dev_j1 : nrows ? csr->row_ptr[nrows] : 0;
+        // the image reads CSR positions instead: element i = i + 1 (device memory, also for host arrays -- the host split is not taken).
+        // The CSR of a transposed handle (src) holds A's positions + 1 already, and its values are A's, indexed like A's vals.
+        const int64_t nv = src ? src->nvals : rows_on_device ? dev_j1 : nrows ? csr->row_ptr[nrows] : 0;
         h->mutable_vals = true;
         h->nvals = nv;
         CREATE_TRY(hipMalloc(&h->d_vals0, std::max<size_t>(vsz * (size_t)nv, 16)));
-        CREATE_TRY(hipMalloc(&h->d_idx, std::max<size_t>(vsz * (size_t)nv, 16)));
-        if (nv) CREATE_TRY(hipMemcpyAsync(h->d_vals0, csr->vals, vsz * (size_t)nv, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        CREATE_TRY(cvr::launch_index_values(h->d_idx, (uint64_t)nv, f32, h->stream));
+        if (nv) CREATE_TRY(hipMemcpyAsync(h->d_vals0, src ? src->vals : csr->vals, vsz * (size_t)nv, src ? src->kind : on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        if (!src) {
+            CREATE_TRY(hipMalloc(&h->d_idx, std::max<size_t>(vsz * (size_t)nv, 16)));
+            CREATE_TRY(cvr::launch_index_values(h->d_idx, (uint64_t)nv, f32, h->stream));
+            hostv.vals = h->d_idx;
+        }
         CREATE_TRY(hipStreamSynchronize(h->stream));
-        hostv.vals = h->d_idx;
     }
     // Host arrays of a matrix that may get column panels (x of 24 MB or more -- 12 MB beyond the resident layout --, or panels asked for) are uploaded once, as they
     // are: the panel rule and the split run on that copy (building split arrays on the host means allocating, touching and
@@ -1197,6 +1219,86 @@ int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *
     *out = h;
     return CVR_OK;
 }
+
+// cvr_options.transpose = 1: A checked as ever, T = the CSR of A^T made on the device (cvr_transpose.hip), then the create of T as device
+// arrays with the same options -- the handle is that of T bit for bit; it remembers the option (image-cache key) and counts the transpose
+// as upload time.  T and the transpose's temporaries are freed before this returns (the create of T copies what it keeps).
+static int create_transposed(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *opt_in)
+{
+    if (!out) return fail(CVR_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (opt_in->transpose != 1) return fail(CVR_ERR_INVALID, "transpose takes 0 or 1");
+    Range          range("cvr_create (transpose)");
+    const bool     positions = opt_in->mutable_values != 0;          // (settings the create of T refuses are refused there)
+    TransposedCsr  t;
+    int64_t        j1 = 0;
+    double         tr_s = 0;
+    int            rc = transpose_checked(csr_in, *opt_in, positions, &t, &j1, &tr_s);
+    if (rc) return rc;
+    const cvr_csr_view tv{t.nrows, t.ncols, t.rp, t.ci, t.va, csr_in->is_f32, 1};
+    cvr_options        topt = *opt_in;
+    topt.transpose = 0;
+    const PositionSource ps{csr_in->vals, csr_in->arrays_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, j1};
+    rc = create_impl(out, &tv, &topt, positions ? &ps : nullptr);
+    t.release();
+    if (rc) return rc;
+    (*out)->opt_used.transpose = 1;
+    (*out)->info.upload_s += tr_s;
+    return CVR_OK;
+}
+
+int cvr_create(cvr_handle **out, const cvr_csr_view *csr_in, const cvr_options *opt_in)
+{
+    if (opt_in && opt_in->transpose != 0) return create_transposed(out, csr_in, opt_in);
+    return create_impl(out, csr_in, opt_in, nullptr);
+}
+
+}  // extern "C"
+
+namespace cvrh {
+
+int transpose_checked(const cvr_csr_view *a, const cvr_options &opt, bool positions, TransposedCsr *out, int64_t *j1_out, double *seconds)
+{
+    if (!a) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
+    const bool on_device = a->arrays_on_device != 0;
+    int        rc = on_device ? CVR_OK : check_csr(a);          // host arrays: rejected before any device work, as without the option
+    if (rc) return rc;
+    // the transpose's limits: A's rows are the column indices of A^T (and its x), A's positions the sort's 32-bit values
+    if (a->nrows >= (int64_t)0x7fffffff) return fail(CVR_ERR_INVALID, "transpose: nrows (%lld) must stay below 2^31 - 1: the rows of A are the column indices of A^T", (long long)a->nrows);
+    if ((uint64_t)(a->nrows + 1) * (a->is_f32 ? 4u : 8u) > 0xffffffffull) return fail(CVR_ERR_INVALID, "transpose: x of A^T (nrows + 1 values) exceeds the 4 GiB a buffer descriptor addresses");
+    if (!on_device && a->nrows > 0 && a->row_ptr[a->nrows] >= ((int64_t)1 << 32)) return fail(CVR_ERR_INVALID, "transpose: row_ptr[nrows] must stay below 2^32");
+    if (!on_device && positions && a->nrows > 0 && a->row_ptr[a->nrows] >= (int64_t)cvr::kNoSource) return fail(CVR_ERR_INVALID, "mutable_values: row_ptr[nrows] must stay below 2^32 - 1");
+    const int ndev = cvr_device_count();
+    if (ndev <= 0) return fail(CVR_ERR_NO_DEVICE, "no HIP device visible: libcvr_amd has no CPU fallback");
+    if (opt.device < 0 || opt.device >= ndev) return fail(CVR_ERR_NO_DEVICE, "device %d out of range [0, %d)", opt.device, ndev);
+    HIP_TRY(hipSetDevice(opt.device));
+    int64_t j0 = 0, j1 = 0;
+    if (on_device) {          // A's checks as cvr_create makes them; the column range before any kernel indexes memory by column
+        if (a->nrows < 0 || a->ncols < 0 || (a->nrows > 0 && !a->row_ptr)) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
+        std::vector<int64_t> rp_host;
+        bool                 rows_on_device = false;
+        rc = check_rows_of_device_csr(*a, rp_host, &rows_on_device, &j0, &j1);
+        if (rc) return rc;
+        if (j1 >= ((int64_t)1 << 32)) return fail(CVR_ERR_INVALID, "transpose: row_ptr[nrows] must stay below 2^32");
+        if (positions && j1 >= (int64_t)cvr::kNoSource) return fail(CVR_ERR_INVALID, "mutable_values: row_ptr[nrows] must stay below 2^32 - 1");
+        rc = check_columns_device(a->col_idx, j0, j1, a->ncols);
+        if (rc) return rc;
+    } else if (a->nrows > 0) {
+        j0 = a->row_ptr[0]; j1 = a->row_ptr[a->nrows];
+    }
+    hipStream_t st = nullptr;
+    HIP_TRY(acquire_stream(opt.device, &st));
+    const double t0 = now_s();
+    rc = transpose_csr(*a, j0, j1, positions, st, out);
+    if (seconds) *seconds = now_s() - t0;
+    release_stream(opt.device, st);
+    *j1_out = j1;
+    return rc;
+}
+
+}  // namespace cvrh
+
+extern "C" {
 
 int cvr_preprocess(cvr_handle *h, int keep_csr, double *seconds)
 {

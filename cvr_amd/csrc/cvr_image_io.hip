@@ -81,6 +81,8 @@ void make_key(ImgKey &k, const cvr_source_key *src, const IOpt &o, size_t vsz)
     k.opt[16] = o.nvec >= 2 ? o.nvec : 0;
     // (slot 17, zero before: mutable_values -- such a file also holds the handle's position map)
     k.opt[17] = o.mutable_values ? 1 : 0;
+    // (slot 18, zero before: transpose -- the file of A^T's handle is not that of A's under the same source key)
+    k.opt[18] = o.transpose;
     k.cus = o.cus; k.xcds = o.xcds;
     snprintf(k.lib, sizeof(k.lib), "%s", cvr_version());
 }

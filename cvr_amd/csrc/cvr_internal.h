@@ -232,6 +232,22 @@ int        mutable_tables(cvr_handle *h);
 int        mutable_after_convert(cvr_handle *h, bool keep_csr);
 int        check_csr(const cvr_csr_view *c, bool columns_on_host = true);
 int        check_columns_device(const int32_t *ci_dev, int64_t j0, int64_t j1, int64_t ncols);
+int        check_rows_device(const int64_t *rp_dev, int64_t nrows, int64_t *rp0, int64_t *rpn);
+// ---- cvr_transpose.hip: the CSR of A^T on the device (cvr_options.transpose)
+struct TransposedCsr {
+    void    *arena = nullptr;              // one allocation: T and the transpose's temporaries
+    int64_t *rp = nullptr;                 // T: row_ptr[nrows + 1] (row_ptr[0] = 0), col_idx, vals (or positions + 1) in device memory
+    int32_t *ci = nullptr;
+    void    *va = nullptr;
+    int64_t  nrows = 0, ncols = 0, nnz = 0;
+    void     release();
+};
+// A (a checked CSR, host or device arrays; [j0, j1) = row_ptr[0], row_ptr[nrows]) -> T; positions: T's values are the bits of A's position + 1
+// (mutable handles).  Synchronises st.
+int        transpose_csr(const cvr_csr_view &a, int64_t j0, int64_t j1, bool positions, hipStream_t st, TransposedCsr *out);
+// cvr_capi.hip: A checked as cvr_create checks it (host or device arrays, the transpose's limits), then transposed on opt.device (cvr_create,
+// cvr_tune); *j1 = A's row_ptr[nrows], *seconds = the transpose (A's upload included)
+int        transpose_checked(const cvr_csr_view *a, const cvr_options &opt, bool positions, TransposedCsr *out, int64_t *j1, double *seconds);
 
 // ---- cvr_layout.hip: the layout of one image (chunk length, workgroup shape, LDS budget, column phases, hub tables) and its device side
 // the host side of one image: the chunk plan (from the host planner, or fetched from the device planner) and the per-chunk

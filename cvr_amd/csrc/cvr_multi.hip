@@ -178,6 +178,7 @@ int cvr_create_multi(cvr_multi **out, const cvr_csr_view *csr, const cvr_options
     if (!out) return fail(CVR_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!csr || !devices || ndevices < 1 || ndevices > 64) return fail(CVR_ERR_INVALID, "bad multi-device arguments");
+    if (opt_in && opt_in->transpose != 0) return fail(CVR_ERR_INVALID, "cvr_create_multi: transpose is not offered (row shards of A^T are column shards of A)");
     if (csr->arrays_on_device) return fail(CVR_ERR_INVALID, "cvr_create_multi takes host arrays (one process, several devices)");
     int rc = check_csr(csr);
     if (rc) return rc;

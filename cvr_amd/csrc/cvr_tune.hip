@@ -10,10 +10,37 @@ static int tune_impl(const cvr_csr_view *csr, const cvr_options *opt_in, bool fu
     cvr_options opt;
     if (opt_in) opt = *opt_in; else cvr_default_options(&opt);
     const double t0 = now_s();
+    // transpose = 1: A is transposed once into a device copy of T (the CSR of A^T) and every candidate is built from T; what the rules decide on
+    // host arrays below (the panel count, the resident candidates) is decided on a host copy of T when A came in host arrays
+    const int32_t transpose = opt.transpose;
+    if (transpose != 0 && transpose != 1) return fail(CVR_ERR_INVALID, "transpose takes 0 or 1");
+    struct Transposed { TransposedCsr t; ~Transposed() { t.release(); } } tr;
+    std::vector<int64_t> t_rp;
+    std::vector<int32_t> t_ci;
+    cvr_csr_view         t_host{};
+    if (transpose) {
+        int64_t j1 = 0;
+        int     rc = transpose_checked(csr, opt, false, &tr.t, &j1, nullptr);      // (values, also for mutable handles: the candidates are timed)
+        if (rc) return rc;
+        opt.transpose = 0;
+        if (!csr->arrays_on_device) {
+            t_rp.resize((size_t)tr.t.nrows + 1);
+            t_ci.resize((size_t)std::max<int64_t>(tr.t.nnz, 1));
+            HIP_TRY(hipMemcpy(t_rp.data(), tr.t.rp, sizeof(int64_t) * t_rp.size(), hipMemcpyDeviceToHost));
+            if (tr.t.nnz) HIP_TRY(hipMemcpy(t_ci.data(), tr.t.ci, sizeof(int32_t) * (size_t)tr.t.nnz, hipMemcpyDeviceToHost));
+            t_host = cvr_csr_view{tr.t.nrows, tr.t.ncols, t_rp.data(), t_ci.data(), nullptr, csr->is_f32, 0};
+            if (opt.col_panels < 0) opt.col_panels = auto_panels(t_host, nullptr);      // (decided once, on T)
+        }
+    }
     // host arrays go to the device once; every candidate is then built from the device copy (device-to-device, no PCIe)
     cvr_csr_view view = *csr;
+    if (transpose) {
+        view = cvr_csr_view{tr.t.nrows, tr.t.ncols, tr.t.rp, tr.t.ci, tr.t.va, csr->is_f32, 1};
+        if (!csr->arrays_on_device) csr = &t_host;          // (the rules below read the host copy of T's row pointers)
+        else csr = &view;
+    }
     struct Staged { void *rp = nullptr, *ci = nullptr, *va = nullptr; ~Staged() { (void)hipFree(rp); (void)hipFree(ci); (void)hipFree(va); } } staged;
-    if (!csr->arrays_on_device && cvr_device_count() > 0 && csr->nrows > 0 && csr->row_ptr && csr->row_ptr[csr->nrows] > 0 && csr->col_idx && csr->vals) {
+    if (!transpose && !csr->arrays_on_device && cvr_device_count() > 0 && csr->nrows > 0 && csr->row_ptr && csr->row_ptr[csr->nrows] > 0 && csr->col_idx && csr->vals) {
         int rc = check_csr(csr);
         if (rc) return rc;
         const size_t nz = (size_t)csr->row_ptr[csr->nrows], vs = csr->is_f32 ? 4 : 8;
@@ -80,6 +107,7 @@ static int tune_impl(const cvr_csr_view *csr, const cvr_options *opt_in, bool fu
                 }
         }
     }
+    best.transpose = transpose;
     *best_out = best;
     if (best_spmv_s) *best_spmv_s = best_t;
     if (tuning_s) *tuning_s = now_s() - t0;

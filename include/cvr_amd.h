@@ -126,7 +126,14 @@ typedef struct {
                                   sparsity pattern without converting again.  The value dictionary is then off (value_dict < 0 turns it off, an explicit
                                   value_dict > 0 is refused with CVR_ERR_INVALID), and row_ptr[nrows] must stay below 2^32 - 1 (CVR_ERR_INVALID).
                                   Every other option and rule works as without it.  0 (default): nothing of this; the former reserved[0]     */
-    int32_t reserved[1];       /* 0 */
+    int32_t transpose;         /* 1: cvr_create builds the handle of A^T from the CSR of A it is given (host or device arrays, checked as ever): the CSR T
+                                  of A^T -- row j = A's elements of column j in ascending CSR position (duplicates kept in their order), column index =
+                                  A's row -- is made on the device by a stable sort and exists only there; the handle is then bit for bit the cvr_create
+                                  of T as device arrays with the same options (image, cvr_info but its times, every result).  cvr_info.nrows = A's ncols,
+                                  ncols = A's nrows: x holds nrows(A) + 1 values, y ncols(A).  With mutable_values the handle's map points into A's CSR
+                                  positions: cvr_update_values* take the array indexed like A's vals.  A's nrows must stay below 2^31 - 1 and
+                                  row_ptr[nrows] below 2^32 (CVR_ERR_INVALID before any device work); cvr_create_multi refuses it.  0 (default): A itself.
+                                  Other values: CVR_ERR_INVALID.  The former reserved[1]: no reserved word is left in this struct                   */
 } cvr_options;
 /* Automatic layout: with steps_per_chunk = 0, waves_per_block = 0, x_window < 0 and col_phases < 0 (the defaults) cvr_create
  * looks at the uploaded CSR on the device (are the rows sorted by column? which share of the non-zeros lies near the
@@ -157,7 +164,8 @@ typedef struct {
     int64_t image_bytes;       /* device bytes of the CVR image incl. descriptors                     */
     int64_t yext_elems;        /* y_ext = [y | dump | 2 carry slots per chunk]                        */
     int64_t x_elems;           /* ncols + 1 : x_ext[ncols] must be 0 (pad slot)                       */
-    double  plan_s, upload_s, convert_s;  /* planner (+ panel rule; preprocess_fused: the whole chain up to the converter's end), H2D of the CSR,
+    double  plan_s, upload_s, convert_s;  /* planner (+ panel rule; preprocess_fused: the whole chain up to the converter's end), H2D of the CSR
+                                           * (cvr_options.transpose: + the transpose of A on the device, A's upload included),
                                            * device time of segment table + conversion (preprocess_fused: from the planner's first kernel) */
     int32_t col_panels;        /* 1, or the number of column panels the matrix was cut into                          */
     int32_t value_dict;        /* 0, or the number of dictionary entries (distinct values + the pad slots' 0)         */
@@ -308,7 +316,8 @@ int64_t cvr_row_partition(int64_t nrows, const int64_t *row_ptr, int32_t nparts,
  * (spmv.cvr: CVR_PARTITION=nnz in the environment keeps the reference's rule). */
 #define CVR_ROW_COST_MILLI_DEFAULT 1250
 int64_t cvr_row_partition_cost(int64_t nrows, const int64_t *row_ptr, int32_t nparts, int32_t row_cost_milli, int64_t *bounds);
-/* csr: host arrays of the whole matrix; opt: as for cvr_create (opt->device is ignored); devices[ndevices]: HIP ordinals */
+/* csr: host arrays of the whole matrix; opt: as for cvr_create (opt->device is ignored; opt->transpose != 0 is refused with CVR_ERR_INVALID
+ * before any device work: row shards of A^T would be column shards of A); devices[ndevices]: HIP ordinals */
 int cvr_create_multi(cvr_multi **out, const cvr_csr_view *csr, const cvr_options *opt, const int32_t *devices, int32_t ndevices);
 int cvr_preprocess_multi(cvr_multi *m, int keep_csr, double *seconds);      /* seconds: the slowest shard's conversion + planning */
 /* y = A x through host buffers: x is replicated to every device, every shard computes its rows, the y slices are all-gathered
@@ -440,7 +449,8 @@ int  cvr_mm_read_cached(const char *mtx_path, int mode, cvr_mm_matrix *out, int 
  * pre_processing on every run, spmv.cpp:1857).  The file is keyed by the source file's identity (`key`; NULL = none), the options,
  * the device's CU / XCD counts, the format and library version; cvr_load_image returns CVR_ERR_STATE when any of them differs
  * (the caller then runs cvr_create + cvr_preprocess and saves again).  The loaded handle computes the same y, bit for bit.
- * opt: the options the image must have been built with (NULL = defaults; opt->device = where to load it).  *seconds: load time. */
+ * opt: the options the image must have been built with (NULL = defaults; opt->device = where to load it; a file of A^T's handle loads only with
+ * opt->transpose = 1, one of A's only with 0, else CVR_ERR_STATE).  *seconds: load time. */
 int  cvr_save_image(cvr_handle *h, const char *path, const cvr_source_key *key);
 int  cvr_load_image(cvr_handle **out, const char *path, const cvr_source_key *expect, const cvr_options *opt, double *seconds);
 /* x[j] = 1.0 (mode 0; fill, spmv.cpp:556-563) or splitmix64(0xC0FFEE, j) -> [-1,1) (mode 1) */
