@@ -245,7 +245,9 @@ int cvr_power_iteration(cvr_handle *h, cvr_comm *c, const int64_t *bounds, int i
             cvr::IterEpilogue epi;
             epi.xnext = nxt; epi.prev = it > 0 ? s.partial + (size_t)((it - 1) & 1) * npart : nullptr; epi.out = s.partial + (size_t)(it & 1) * npart; epi.nsets = (uint32_t)nsets;
             if (h->d_map) HIP_TRY(handle_enter(h, st));          // (a mutable handle's image: ordered with its updates, as run_spmv orders it)
-            HIP_TRY(cvr::launch_spmv(h->parts[0].img, cur, s.y, st, true, nullptr, 0, 1, &epi));
+            cvr::SpmvLaunch step;
+            step.epi = &epi;
+            HIP_TRY(cvr::launch_spmv(h->parts[0].img, cur, s.y, st, step));
             if (h->d_map) HIP_TRY(handle_leave(h, st));
             std::swap(cur, nxt);
             if (f32 && it == 0 && iters > 1) {      // the fp32 range check of the unfused loop below

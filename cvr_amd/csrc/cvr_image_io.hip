@@ -342,7 +342,6 @@ int cvr_load_image(cvr_handle **out, const char *path, const cvr_source_key *exp
     (void)hipHostFree(pinned);
     pinned = nullptr;
 #undef LOAD_TRY
-    { const int rcf = setup_fuse(h); if (rcf) { cvr_destroy(h); return rcf; } }          // (the fused combine's tables follow from the chunk tables: made again, not stored)
     if (h->mutable_vals) { const int rcm = mutable_tables(h); if (rcm) { cvr_destroy(h); return rcm; } }
     ilv_runtime_settings(h);
     h->converted = true;

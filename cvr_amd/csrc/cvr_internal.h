@@ -157,12 +157,6 @@ struct cvr_handle {
     cvr::FixPart *d_fixparts = nullptr;   // panels: the fix-up of every panel in one launch
     // panels, one per XCD at a time (cvr_kernels.h: PanelArgs): rounds of eight panels per launch; d_multi[round][8]
     cvr::PanelArgs       *d_multi = nullptr;
-    // the combine pass inside the panel kernel (gang chunks; cvr_kernels.h: FuseArgs): tables in one allocation; null = the combine pass is a launch of its own
-    void                 *fuse_mem = nullptr;
-    cvr::FuseArgs        *d_fuse = nullptr;
-    cvr::FusePanel       *d_fuse_panels = nullptr;
-    uint32_t             *d_fuse_cut = nullptr, *d_fuse_nsub = nullptr;
-    uint32_t              fuse_ncut = 0;
     std::vector<uint32_t> multi_chunks;   // per round: the most chunks any of its panels has
     uint32_t              multi_ystage = 0;
     uint32_t  max_nshared = 0;
@@ -215,12 +209,11 @@ namespace cvrh {
 // whole chip and switch themselves off otherwise.  Cached per device; {256, 8} if the query fails.
 struct Chip { int cus = 256, xcds = 8; };
 Chip       chip_of(int device);
-hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st, const cvr::ScaleEpi *sc = nullptr);      // sc: the scaled product's write-out (not with the fused combine)
-int        setup_fuse(cvr_handle *h);
+hipError_t run_spmv(cvr_handle *h, const void *x, void *y, hipStream_t st, const cvr::ScaleEpi *sc = nullptr);      // y_ext = A x for the whole handle on `st`; sc: the scaled product's write-out
 // The combine pass's bitmap (cvr_kernels.h: launch_combine_bits_build) for a panelled handle with at most 16 panels and half or more of its (row, panel) pairs filled:
 // allocated and filled on the handle's stream behind the combine tables.  nsub = the handle's partial sums (all panels).  CVR_DEBUG=combine_bits=0|1 overrides the rule.
-int        setup_combine_bits(cvr_handle *h, int64_t nsub);                    // the fused combine's tables, for handles whose panels all carry gang chunks and run one per XCD (after d_multi)
-void       ilv_runtime_settings(cvr_handle *h);          // helper wavefronts / sweep direction of interleaved images (launch parameters)      // y_ext = A x for the whole handle on `st`
+int        setup_combine_bits(cvr_handle *h, int64_t nsub);
+void       ilv_runtime_settings(cvr_handle *h);          // helper wavefronts / sweep direction of interleaved images (launch parameters)
 IOpt       make_iopt(const cvr_options *in);
 // The handle's image (column panels' partial sums, hub table's x, a mutable handle's values) is shared by every launch on it: a launch on
 // another stream than the one before waits for that one (the event is recorded when the stream changes).  Around every launch that reads or

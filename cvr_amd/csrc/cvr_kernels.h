@@ -209,11 +209,7 @@ hipError_t launch_dict_scan(const void *vals, int64_t n0, int64_t n1, bool f32, 
 hipError_t launch_window(const DeviceImage &img, const DeviceCsr &csr, hipStream_t st, const uint32_t *nchunks_dev = nullptr);
 
 // column panels, one panel per XCD at a time: what differs between the eight panels of one launch (device array of 8; nchunks = 0: none)
-struct PanelArgs { const uint8_t *stream; const uint4 *desc; const uint8_t *target; void *yext; uint32_t nchunks, ystage; const uint2 *desc2; uint32_t col_base, pad_col; const uint32_t *gbase; uint32_t gang0, pad_; };      // (gang0: the panel's first gang in the numbering of FuseArgs::range)      // (col_base, pad_col: interleaved panels keep panel-local columns)
-// y_ext = A x  (+ the ordered fix-up of rows cut over chunks when img.nshared > 0 and with_fixup)
-// multi != null: eight panels in one launch (plain layout, one chunk per workgroup, no LDS tables): workgroup b takes chunk b >> 3 of
-// panel b & 7 of its round; multi[rounds][8]; multi_chunks = the most chunks any panel has (the rounds follow each other in ONE grid:
-// no launch boundary between them); img = any of the panels (for what they share); y_ext and with_fixup unused
+struct PanelArgs { const uint8_t *stream; const uint4 *desc; const uint8_t *target; void *yext; uint32_t nchunks, ystage; const uint2 *desc2; uint32_t col_base, pad_col; const uint32_t *gbase; uint32_t pad0_, pad1_; };      // (col_base, pad_col: interleaved panels keep panel-local columns; pad0_, pad1_: written 0)
 // The iterative caller's step inside the SpMV kernel's write-out (images with column phases, no rows cut over chunks, square matrix):
 // per workgroup the partial sums of x . y, y . y, x . x over its rows -> out[set * nsets + workgroup], and x_next = y / ||y of the step
 // before|| (prev: that step's partials, null = 1).  cvr_iter.hip's power_step_kernel is the same step as a pass of its own.
@@ -226,23 +222,19 @@ struct ScaleEpi { double alpha = 1, beta = 0; uint32_t nrows = 0, mode = 0; };
 // y[i] = alpha * t[i] + beta * y[i], i < n, by the rule above (mode 1: alpha * t[i]); t == null: beta * y[i] (alpha == 0), or +0 with mode 0 -- the two-pass
 // form of ScaleEpi (layouts whose write-out does not take it, CVR_DEBUG=scaled_two_pass) and the alpha == 0 call.  Asynchronous on st.
 hipError_t launch_axpby(const void *t, void *y, int64_t n, bool f32, const ScaleEpi &sc, hipStream_t st);
-bool       scale_fused_ok(const DeviceImage &img, bool multi);      // launch_spmv honours `sc` for this image (multi: a panel launch, whose output is partial sums)
-// The combine pass of column panels INSIDE the panel kernel (gang chunks; round 6): a gang that has stored its rows' partial sums counts itself in at
-// every block of kCombineRows rows its sub-rows may lie in (range[gang] = {first, last block}; the ranges of a panel's gangs tile all blocks), and the
-// workgroup whose count completes a block -- expect[block] = gangs of all panels that cover it -- adds that block's partial sums, panel by panel in panel
-// order (the order of combine_kernel: the same bits), writes y and resets the counter.  Partial sums are stored and loaded past the non-coherent caches
-// (sc1), as the hand-off between workgroups on different XCDs requires.  Tables made by launch_fuse_setup; y comes with the launch.
-struct FuseArgs { uint32_t *cnt; const uint32_t *expect; const uint2 *range; const struct CombinePanel *panels; const uint32_t *block_off; uint32_t npanels, nblocks, nrows, ngangs; };
-struct FusePanel { const uint4 *desc; const uint2 *desc2; const uint32_t *rows; uint32_t nchunks, gang0; };      // per panel: its chunk tables, the rows of its sub-rows
-// range[] and expect[] of a handle's panels (gw chunks per gang); cnt zeroed.  Asynchronous on st.
-hipError_t launch_fuse_setup(const FusePanel *panels_dev, uint32_t npanels, uint32_t gw, uint32_t ngangs, uint32_t nblocks, uint2 *range, uint32_t *first_last, uint32_t *expect, uint32_t *cnt, hipStream_t st);
-// y[row] of the rows cut over chunks, once more after the fix-up launch has summed their carries (the fused combine read their partial sums too early):
-// rows_list[i] = a global row; per panel the sub-row with that row (binary search), its partial sum added in panel order
-hipError_t launch_fuse_cut_rows(const int64_t *shared, uint32_t nshared, const uint32_t *rows, uint32_t *out, hipStream_t st);      // out[i] = rows[shared[i].row]: the global rows of a panel's cut rows
-hipError_t launch_fuse_patch(const uint32_t *rows_list, uint32_t nlist, const FusePanel *panels_dev, const struct CombinePanel *cpanels, const uint32_t *nsub, uint32_t npanels, void *y, bool f32, hipStream_t st);
-hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, hipStream_t st, bool with_fixup = true, const PanelArgs *multi = nullptr, uint32_t multi_chunks = 0,
-                       uint32_t multi_rounds = 1,
-                       const IterEpilogue *epi = nullptr, const FuseArgs *fuse = nullptr, void *y_fused = nullptr, const ScaleEpi *sc = nullptr);
+// y_ext = A x  (+ the ordered fix-up of rows cut over chunks when img.nshared > 0 and with_fixup).  What a call passes beyond the image and the
+// vectors; the defaults are the plain product of a single image.
+// multi != null: eight panels in one launch (plain layout, one chunk per workgroup, no LDS tables): workgroup b takes chunk b >> 3 of
+// panel b & 7 of its round; multi[multi_rounds][8]; multi_chunks = the most chunks any panel has (the rounds follow each other in ONE grid:
+// no launch boundary between them); img = any of the panels (for what they share); y_ext and with_fixup unused
+struct SpmvLaunch {
+    bool                with_fixup = true;
+    const PanelArgs    *multi = nullptr;
+    uint32_t            multi_chunks = 0, multi_rounds = 1;
+    const IterEpilogue *epi = nullptr;      // (iter_epilogue_ok(img); not with multi)
+    const ScaleEpi     *sc = nullptr;       // (a single image's write-out: not with multi, whose output is partial sums, nor with epi)
+};
+hipError_t launch_spmv(const DeviceImage &img, const void *x_ext, void *y_ext, hipStream_t st, const SpmvLaunch &opt = SpmvLaunch{});
 size_t     spmv_lds_bytes(const DeviceImage &img);      // dynamic LDS of that launch
 // Several vectors (cvr_spmm_device): Y = A X over an image of the plain layout (spmm_plain), X / Y row-major with leading dimensions ldx / ldy (in values),
 // blocks of up to kSpmmBlock vectors per launch, then the cut rows' fix-up per vector.  hipErrorInvalidValue for another layout or an X beyond 4 GiB.

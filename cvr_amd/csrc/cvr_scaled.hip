@@ -1,15 +1,13 @@
 // cvr_scaled.hip -- the C ABI of the scaled product (include/cvr_amd.h: cvr_spmv_scaled_device, cvr_spmv_scaled): y = alpha A x + beta y.
 // The scaling is done where the kernels store a row's final value (cvr_kernels.h: ScaleEpi) -- the SpMV kernel of a single image and its fix-up of
-// rows cut over chunks, or the combine pass of column panels --, so it costs the read of old y and no pass of its own.  The fused combine of
-// CVR_DEBUG=fuse writes cut rows twice and takes the two-pass form instead: the plain product into a buffer of the handle, then an elementwise
-// kernel.  CVR_DEBUG=scaled_two_pass at cvr_create / cvr_load_image forces that form for the handle (a bitwise cross-check of the fused write-outs and a timing baseline).
+// rows cut over chunks, or the combine pass of column panels --, so it costs the read of old y and no pass of its own.
+// CVR_DEBUG=scaled_two_pass at cvr_create / cvr_load_image gives the handle the two-pass form instead: the plain product into a buffer of the handle,
+// then an elementwise kernel (a bitwise cross-check of the fused write-outs and a timing baseline).
 #include "cvr_internal.h"
 
 using namespace cvrh;
 
 namespace {
-
-bool two_pass(const cvr_handle *h) { return h->d_fuse != nullptr || h->scaled_two_pass; }
 
 // the two-pass form's buffer for the plain product: y_ext's size, allocated at the first call that needs it
 hipError_t two_pass_buffer(cvr_handle *h, void **out)
@@ -39,7 +37,7 @@ int scaled_device(cvr_handle *h, double alpha, const void *x, double beta, void 
         HIP_TRY(run_spmv(h, x, y, st));
         return CVR_OK;
     }
-    if (two_pass(h)) {
+    if (h->scaled_two_pass) {
         void *t = nullptr;
         HIP_TRY(two_pass_buffer(h, &t));
         HIP_TRY(handle_enter(h, st));          // (the buffer is the handle's: a call on another stream waits for this one's elementwise pass)

@@ -206,11 +206,11 @@ def test_gang_chunks_fall_back_to_tags_and_fp32_panels():
 
 
 @pytest.mark.parametrize("debug", ["ilv_helpers=2,ilv_flip=1,ilv_stream_nt=1,ilv_ahead=8", "ilv_helpers=1,ilv_per_line=1", "combine_mul=8,combine_batch=9", "combine_mul=8,combine_batch=12",
-                                   "combine_batch=8", "combine_batch=16", "fuse", "combine_bits=0", "combine_bits=1"])
+                                   "combine_batch=8", "combine_batch=16", "combine_bits=0", "combine_bits=1"])
 @pytest.mark.parametrize("gang", [0, 1])
 def test_launch_parameter_paths_on_small_matrices(debug, gang, monkeypatch):
     """The launch parameters that the rules switch on for large handles only -- helper wavefronts, the alternating sweep direction, non-temporal stream loads,
-    the combine pass's wide workgroups and batches, and the combine pass inside the gang kernel (CVR_DEBUG=fuse: measured, not adopted) -- forced onto a small
+    the combine pass's wide workgroups and batches -- forced onto a small
     matrix of interleaved panels, with private chunks and with gang chunks: the same y, bit for bit, as without them, several SpMVs in a row (the sweep alternates)."""
     n, nc, rp, ci, va = synth.livejournal_like(scale=0.02)
     x = O.x_vec_fast(nc, "rand")

@@ -4,7 +4,7 @@
     column panels, interleaved and gang chunks, nvec >= 2, the default options) in fp64 and fp32 over the seeded cases: the first nrows values of
     y are alpha * s + beta * y0 in the handle's type, bit for bit, s = cvr_spmv_device's y of the same handle; the fused write-out is bit for bit
     the two-pass form (CVR_DEBUG=scaled_two_pass); beta = 0 does not read y, alpha = 0 reads neither x nor the matrix; no state is left behind
-  * rows cut over chunks on single images and on panels, both forms of the combine pass, the cut-row fold and CVR_DEBUG=fuse
+  * rows cut over chunks on single images and on panels, both forms of the combine pass and the cut-row fold
   * the fused one-submission handle, torch streams and a captured graph, the image cache, a mutable handle after an update, full-size shapes
 """
 import numpy as np
@@ -189,12 +189,12 @@ def test_combine_pass_forms(which, f32, monkeypatch):
     if which == "cut_fold":
         n, nc, rp, ci, va = _cut_matrix(f32)
         kws = [{"col_panels": 8, "steps_per_chunk": 32}, {"col_panels": 8, "interleave": 1, "gang": 1, "steps_per_chunk": 32, "waves_per_block": 4}]
-        debugs = ["", "no_cut_fold", "combine_bits=0", "combine_bits=1", "fuse"]
+        debugs = ["", "no_cut_fold", "combine_bits=0", "combine_bits=1"]
     else:
         n, nc, rp, ci, va = synth.livejournal_like(scale=0.021)
         va = va.astype(dtype)
         kws = [{"col_panels": 16, "steps_per_chunk": 4}, {"col_panels": 16, "interleave": 1, "gang": 1}]
-        debugs = ["combine_bits=0", "combine_bits=1", "fuse"]
+        debugs = ["combine_bits=0", "combine_bits=1"]
     x = synth.x_rand(nc).astype(dtype)
     for kw in kws:
         ref = None

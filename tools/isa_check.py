@@ -143,8 +143,8 @@ def check(path, expected):
                 ok = in_asm and re.match(r"^\s*buffer_load_dword(x[234])?\b", code) and (first_reg(code) or 0) >= cap
                 if not ok:
                     errors.append(f"{name}: vector-memory instruction inside the ring region that is not a ring load ({path}:{i + 1}): {code.strip()}")
-            # (behind CVR_RING_END the ring is dead and its registers are the compiler's again -- the gang kernel's fused combine uses a few; a value
-            # that lived THROUGH the region in one of them would have been named in front of it, which this rule still catches)
+            # (behind CVR_RING_END the ring is dead and its registers are the compiler's again; a value that lived THROUGH the region in one of them
+            # would have been named in front of it, which this rule still catches)
             if not in_asm and not closed and highest_vreg(code) >= cap:
                 errors.append(f"{name}: the compiler uses a ring register ({path}:{i + 1}): {code.strip()}")
         if not closed or region:
