@@ -74,6 +74,20 @@ class Info(C.Structure):
                 ("hub_select_s", C.c_double), ("probe_s", C.c_double), ("dict_s", C.c_double), ("preprocess_wall_s", C.c_double), ("row_bands", C.c_int32), ("piece_max", C.c_int32), ("spmv_launches", C.c_int32), ("preprocess_fused", C.c_int32), ("interleave", C.c_int32), ("gang", C.c_int32)]
 
 
+class CgOptions(C.Structure):
+    """cvr_cg_options"""
+    _fields_ = [("max_iters", C.c_int32), ("check_every", C.c_int32), ("rtol", C.c_double), ("minv_dev", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class CgResult(C.Structure):
+    """cvr_cg_result"""
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("spmv_count", C.c_int32), ("reserved", C.c_int32),
+                ("residual_norm", C.c_double), ("b_norm", C.c_double), ("seconds", C.c_double)]
+
+
+CG_CONVERGED, CG_MAX_ITERS, CG_BREAKDOWN = 0, 1, 2
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -83,7 +97,7 @@ class MmMatrix(C.Structure):
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
-           "cvr_spmv_scaled_device", "cvr_spmv_scaled",
+           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -130,6 +144,10 @@ def lib():
         L.cvr_spmm_supported.argtypes = [C.c_void_p]
         L.cvr_spmv_scaled_device.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         L.cvr_spmv_scaled.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p]
+        L.cvr_cg_default_options.argtypes = [C.POINTER(CgOptions)]
+        L.cvr_cg_default_options.restype = None
+        L.cvr_cg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_cg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -559,6 +577,46 @@ class CvrMatrix:
         rc = lib().cvr_spmv_scaled_device(self._h, float(alpha), x_ptr, float(beta), y_ptr, stream)
         if rc:
             raise CvrError(rc, "cvr_spmv_scaled_device")
+
+    def _cg_options(self, rtol, max_iters, check_every, minv_ptr):
+        opt = CgOptions()
+        lib().cvr_cg_default_options(C.byref(opt))
+        if rtol is not None:
+            opt.rtol = float(rtol)
+        if max_iters is not None:
+            opt.max_iters = int(max_iters)
+        opt.check_every = int(check_every)
+        opt.minv_dev = minv_ptr
+        return opt
+
+    def cg(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
+        """solves A x = b for a symmetric positive definite A by conjugate gradients on the device (cvr_cg_device): b_ptr and x_ptr are
+        device arrays of nrows values (x: the start vector in, the solution out), minv_ptr an optional diagonal preconditioner (nrows
+        values, z = minv .* r); rtol / max_iters None: the library's defaults.  Returns the CgResult (iterations, status = CG_*,
+        spmv_count, residual_norm, b_norm, seconds); synchronises the stream."""
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
+        rc = lib().cvr_cg_device(self._h, b_ptr, x_ptr, C.byref(opt), C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_cg_device")
+        return res
+
+    def cg_host(self, b, x0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_cg): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device
+        pointer.  Returns (x, CgResult)."""
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        if len(b) < self.nrows:
+            raise ValueError("b is shorter than nrows")
+        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=self.dtype)
+            if len(x0) < self.nrows:
+                raise ValueError("x0 is shorter than nrows")
+            x[: self.nrows] = x0[: self.nrows]
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
+        rc = lib().cvr_cg(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_cg")
+        return x[: self.nrows], res
 
     def spmm(self, X, iters=1):
         """Y = A X for the k columns of X (host array of shape (ncols, k)) in one pass per block of 8 (cvr_spmm); returns (Y of shape

@@ -1,0 +1,422 @@
+// cvr_cg.hip -- conjugate gradients on the device (include/cvr_amd.h: cvr_cg_device, cvr_cg): the solver loop around the handle's SpMV, its fused
+// vector kernels and a stop test without a host round trip per iteration.  Per step, beside the SpMV q = A p (run_spmv: cvr_spmv_device's path):
+//   cg_pq_kernel         the partial sums of p . q
+//   cg_update_kernel     alpha = r.z / p.q from those partials (summed in every workgroup, the same order everywhere: power_step_kernel's pattern);
+//                        x += alpha p, r -= alpha q, z = minv .* r and the partial sums of r . r and r . z in one pass
+//   cg_direction_kernel  r.r and r.z from those partials; the stop test; beta = r.z / r.z of the step before; p = z + beta p
+// about eleven vector passes per step (p q | x p r q x r | z p p), all in 16-byte packets.  Sums are fp64 in a fixed tree (cvr_iter.hip's: strided share
+// per thread, lanes by butterfly, wavefronts in order, workgroups' partials by a fixed tree again); no atomics, so a call gives the same bits every time.
+// The scalars that outlive a kernel sit in a state cell (CgCell) that workgroup 0 writes: a kernel that finds the stop records it there and every later
+// kernel of the batch returns without writing -- the result does not depend on how many steps the host enqueues between two read-backs.
+// (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+#include "cvr_internal.h"
+
+using namespace cvrh;
+
+namespace {
+
+constexpr int kBlocks = 1024, kThreads = 256;          // cvr_iter.hip's grid: the partial count is fixed
+constexpr int kWaves = kThreads / 64;
+static_assert(kBlocks == 4 * kThreads, "sum_partials reads four partials per thread");
+constexpr int kDefaultCheckEvery = 8;
+
+// The state cell.  Written by thread 0 of workgroup 0 only; a value a kernel reads is one that a kernel BEFORE it wrote (r.z of the step before sits
+// in rz[k & 1], this step's goes to rz[(k + 1) & 1]) -- except `stop`, which the other workgroups of the kernel that sets it may or may not see yet:
+// they come to the same decision from the same sums, so either way they return without writing.
+struct CgCell {
+    double  bb, bnorm;         // b . b and its root
+    double  rr, rnorm;         // r . r of the last iterate and its root
+    double  rz[2];
+    int32_t stop;              // != 0: no kernel writes a vector any more
+    int32_t status;            // CVR_CG_*
+    int32_t iters;             // steps applied to x
+    int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
+};
+
+template <typename T> struct Vec;
+template <> struct Vec<double> { typedef double type __attribute__((ext_vector_type(2))); };
+template <> struct Vec<float> { typedef float type __attribute__((ext_vector_type(4))); };
+template <typename T> constexpr int kPack = 16 / (int)sizeof(T);          // values per 16-byte packet
+
+// the packet at p + e: one 16-byte load when it is whole and p is 16-byte aligned (VEC), else its `cnt` values one by one; the rest 0
+template <typename T, bool VEC>
+__device__ __forceinline__ void load_pack(const T *__restrict__ p, long long e, int cnt, T (&v)[kPack<T>])
+{
+    if (VEC && cnt == kPack<T>) {
+        const typename Vec<T>::type t = *reinterpret_cast<const typename Vec<T>::type *>(p + e);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) v[j] = t[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) v[j] = j < cnt ? p[e + j] : (T)0;
+    }
+}
+template <typename T, bool VEC>
+__device__ __forceinline__ void store_pack(T *__restrict__ p, long long e, int cnt, const T (&v)[kPack<T>])
+{
+    if (VEC && cnt == kPack<T>) {
+        typename Vec<T>::type t;
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) t[j] = v[j];
+        *reinterpret_cast<typename Vec<T>::type *>(p + e) = t;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) if (j < cnt) p[e + j] = v[j];
+    }
+}
+
+// s[k] = the sum of the k-th set of kBlocks partials, the same bits in every thread of every workgroup: thread t takes partials t, t + 256, t + 512,
+// t + 768 in that order, the lanes of a wavefront a butterfly, the four wavefronts in order.  Ends behind a barrier (what thread 0 put into LDS
+// before the call is visible after it).
+template <int K>
+__device__ __forceinline__ void sum_partials(const double *__restrict__ part, double (&s)[K], double (&sh)[K][kWaves])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        double a = 0;
+#pragma unroll
+        for (int j = 0; j < kBlocks / kThreads; j++) a += part[(size_t)k * kBlocks + threadIdx.x + j * kThreads];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if ((threadIdx.x & 63u) == 0) sh[k][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        double a = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) a += sh[k][w];
+        s[k] = a;
+    }
+}
+
+// out[k * kBlocks + workgroup] = the workgroup's sum of acc[k]: dot_partial_kernel's tree
+template <int K>
+__device__ __forceinline__ void store_partials(double (&acc)[K], double *__restrict__ out, double (&sh)[K][kWaves])
+{
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+        if ((threadIdx.x & 63u) == 0) sh[k][threadIdx.x >> 6] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            double a = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; w++) a += sh[k][w];
+            out[(size_t)k * kBlocks + blockIdx.x] = a;
+        }
+    }
+}
+
+#define CVR_CG_PACKETS(T, e, cnt)                                                                                                  \
+    for (long long e = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPack<T>, cnt = 0; e < n && ((cnt = n - e < kPack<T> ? n - e : kPack<T>), true); \
+         e += (long long)kBlocks * kThreads * kPack<T>)
+
+// The start: r holds b - A x0 (the scaled product).  z = minv .* r (PRE), p = z (or r), and the partial sums of r . r, r . z (PRE) and b . b.
+// AL: b and minv, the caller's arrays, are 16-byte aligned.
+template <typename T, bool PRE, bool AL>
+__global__ __launch_bounds__(kThreads) void cg_init_kernel(const T *__restrict__ b, const T *__restrict__ minv, const T *__restrict__ r, T *__restrict__ z,
+                                                           T *__restrict__ p, long long n, double *__restrict__ out)
+{
+    __shared__ double sh[3][kWaves];
+    double acc[3] = {0, 0, 0};
+    CVR_CG_PACKETS(T, e, cnt) {
+        T bv[kPack<T>], rv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
+        load_pack<T, AL>(b, e, (int)cnt, bv);
+        load_pack<T, true>(r, e, (int)cnt, rv);
+        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) {
+            zv[j] = PRE ? (T)((double)mv[j] * (double)rv[j]) : rv[j];
+            if (j < cnt) {
+                acc[0] += (double)rv[j] * (double)rv[j];
+                if constexpr (PRE) acc[1] += (double)rv[j] * (double)zv[j];
+                acc[2] += (double)bv[j] * (double)bv[j];
+            }
+        }
+        if constexpr (PRE) store_pack<T, true>(z, e, (int)cnt, zv);
+        store_pack<T, true>(p, e, (int)cnt, zv);
+    }
+    store_partials<3>(acc, out, sh);
+}
+
+// one workgroup: the start's sums into the state cell, and the stop test of the start vector
+__global__ __launch_bounds__(kThreads) void cg_check_kernel(const double *__restrict__ part, int pre, double rtol, CgCell *__restrict__ cell)
+{
+    __shared__ double sh[3][kWaves];
+    double s[3];
+    sum_partials<3>(part, s, sh);
+    if (threadIdx.x != 0) return;
+    CgCell c;
+    c.bb = s[2]; c.bnorm = sqrt(s[2]);
+    c.rr = s[0]; c.rnorm = sqrt(s[0]);
+    c.rz[0] = pre ? s[1] : s[0]; c.rz[1] = 0;
+    c.stop = 0; c.status = CVR_CG_MAX_ITERS; c.iters = 0; c.zero_x = 0;
+    if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
+    else if (c.rnorm <= rtol * c.bnorm) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
+    *cell = c;
+}
+
+// the partial sums of p . q
+template <typename T>
+__global__ __launch_bounds__(kThreads) void cg_pq_kernel(const T *__restrict__ p, const T *__restrict__ q, long long n, double *__restrict__ out,
+                                                         const CgCell *__restrict__ cell)
+{
+    __shared__ double sh[1][kWaves];
+    if (cell->stop) return;          // (no workgroup of this kernel sets it)
+    double acc[1] = {0};
+    CVR_CG_PACKETS(T, e, cnt) {
+        T pv[kPack<T>], qv[kPack<T>];
+        load_pack<T, true>(p, e, (int)cnt, pv);
+        load_pack<T, true>(q, e, (int)cnt, qv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[0] += (double)pv[j] * (double)qv[j];
+    }
+    store_partials<1>(acc, out, sh);
+}
+
+// Step k: alpha = r.z / p.q; x += alpha p, r -= alpha q, z = minv .* r; the partial sums of r . r (set 0) and r . z (set 1, PRE).  p.q <= 0 or not
+// finite: breakdown, recorded, nothing written.  AL: x and minv, the caller's arrays, are 16-byte aligned.
+template <typename T, bool PRE, bool AL>
+__global__ __launch_bounds__(kThreads) void cg_update_kernel(T *__restrict__ x, T *__restrict__ r, T *__restrict__ z, const T *__restrict__ p,
+                                                             const T *__restrict__ q, const T *__restrict__ minv, long long n,
+                                                             const double *__restrict__ part_pq, double *__restrict__ out, CgCell *__restrict__ cell, int k)
+{
+    constexpr int K = PRE ? 2 : 1;
+    __shared__ double shp[1][kWaves];
+    __shared__ double sh[K][kWaves];
+    __shared__ int stopped;
+    if (threadIdx.x == 0) stopped = cell->stop;
+    double pq[1];
+    sum_partials<1>(part_pq, pq, shp);
+    if (stopped) return;
+    if (!(pq[0] > 0) || !(pq[0] <= 1.7976931348623157e308)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { cell->status = CVR_CG_BREAKDOWN; cell->stop = 1; }
+        return;
+    }
+    const double alpha = cell->rz[k & 1] / pq[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) cell->iters = k + 1;
+    double acc[K] = {};
+    CVR_CG_PACKETS(T, e, cnt) {
+        T xv[kPack<T>], rv[kPack<T>], pv[kPack<T>], qv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
+        load_pack<T, AL>(x, e, (int)cnt, xv);
+        load_pack<T, true>(r, e, (int)cnt, rv);
+        load_pack<T, true>(p, e, (int)cnt, pv);
+        load_pack<T, true>(q, e, (int)cnt, qv);
+        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) {
+            xv[j] = (T)((double)xv[j] + alpha * (double)pv[j]);
+            rv[j] = (T)((double)rv[j] - alpha * (double)qv[j]);
+            if constexpr (PRE) zv[j] = (T)((double)mv[j] * (double)rv[j]);
+            if (j < cnt) {
+                acc[0] += (double)rv[j] * (double)rv[j];
+                if constexpr (PRE) acc[1] += (double)rv[j] * (double)zv[j];
+            }
+        }
+        store_pack<T, AL>(x, e, (int)cnt, xv);
+        store_pack<T, true>(r, e, (int)cnt, rv);
+        if constexpr (PRE) store_pack<T, true>(z, e, (int)cnt, zv);
+    }
+    store_partials<K>(acc, out, sh);
+}
+
+// Step k, behind the update: r.r and r.z from its partials into the cell; ||r|| <= rtol ||b||: converged, recorded, nothing written; else
+// p = z + beta p with beta = r.z / r.z of the step before.  z is r without a preconditioner.
+template <typename T, bool PRE>
+__global__ __launch_bounds__(kThreads) void cg_direction_kernel(T *__restrict__ p, const T *__restrict__ z, long long n, const double *__restrict__ part,
+                                                                CgCell *__restrict__ cell, int k, double rtol)
+{
+    constexpr int K = PRE ? 2 : 1;
+    __shared__ double sh[K][kWaves];
+    __shared__ int stopped;
+    if (threadIdx.x == 0) stopped = cell->stop;
+    double s[K];
+    sum_partials<K>(part, s, sh);
+    if (stopped) return;
+    const double rr = s[0], rz = s[K - 1], rnorm = sqrt(rr);
+    const bool   done = rnorm <= rtol * cell->bnorm;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        cell->rr = rr; cell->rnorm = rnorm; cell->rz[(k + 1) & 1] = rz;
+        if (done) { cell->status = CVR_CG_CONVERGED; cell->stop = 1; }
+    }
+    if (done) return;
+    const double beta = rz / cell->rz[k & 1];
+    CVR_CG_PACKETS(T, e, cnt) {
+        T pv[kPack<T>], zv[kPack<T>];
+        load_pack<T, true>(p, e, (int)cnt, pv);
+        load_pack<T, true>(z, e, (int)cnt, zv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) pv[j] = (T)((double)zv[j] + beta * (double)pv[j]);
+        store_pack<T, true>(p, e, (int)cnt, pv);
+    }
+}
+
+#undef CVR_CG_PACKETS
+
+// the library's buffers of one call, one allocation: p (x_ext), q and r (y_ext each: r takes the scaled product), z, the partial sums, the cell
+struct Workspace {
+    uint8_t   *arena = nullptr;
+    void      *p = nullptr, *q = nullptr, *r = nullptr, *z = nullptr;
+    double    *part_pq = nullptr, *part = nullptr;
+    CgCell    *cell = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Workspace()
+    {
+        if (arena) (void)hipFree(arena);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+template <typename T>
+hipError_t launch_init(const Workspace &w, const void *b, const void *minv, long long n, bool al, hipStream_t st)
+{
+#define CVR_CG_INIT(PRE, AL) hipLaunchKernelGGL((cg_init_kernel<T, PRE, AL>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<const T *>(b), static_cast<const T *>(minv), \
+                                                static_cast<const T *>(w.r), static_cast<T *>(w.z), static_cast<T *>(w.p), n, w.part)
+    if (minv) { if (al) CVR_CG_INIT(true, true); else CVR_CG_INIT(true, false); }
+    else      { if (al) CVR_CG_INIT(false, true); else CVR_CG_INIT(false, false); }
+#undef CVR_CG_INIT
+    return hipGetLastError();
+}
+
+// the three vector launches of step k (the SpMV q = A p is enqueued in front of them)
+template <typename T>
+hipError_t launch_step(const Workspace &w, void *x, const void *minv, long long n, bool al, int k, double rtol, hipStream_t st)
+{
+    hipLaunchKernelGGL((cg_pq_kernel<T>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<const T *>(w.p), static_cast<const T *>(w.q), n, w.part_pq, w.cell);
+#define CVR_CG_UPDATE(PRE, AL) hipLaunchKernelGGL((cg_update_kernel<T, PRE, AL>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(x), static_cast<T *>(w.r), \
+                                                  static_cast<T *>(w.z), static_cast<const T *>(w.p), static_cast<const T *>(w.q), static_cast<const T *>(minv), n, w.part_pq, w.part, w.cell, k)
+    if (minv) { if (al) CVR_CG_UPDATE(true, true); else CVR_CG_UPDATE(true, false); }
+    else      { if (al) CVR_CG_UPDATE(false, true); else CVR_CG_UPDATE(false, false); }
+#undef CVR_CG_UPDATE
+    if (minv) hipLaunchKernelGGL((cg_direction_kernel<T, true>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.z), n, w.part, w.cell, k, rtol);
+    else hipLaunchKernelGGL((cg_direction_kernel<T, false>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.r), n, w.part, w.cell, k, rtol);
+    return hipGetLastError();
+}
+
+int check_args(const void *h, const void *b, const void *x, const cvr_cg_options *opt, const cvr_cg_result *res)
+{
+    if (!h || !b || !x || !opt || !res) return fail(CVR_ERR_INVALID, "null argument");
+    if (opt->max_iters < 0 || opt->check_every < 0) return fail(CVR_ERR_INVALID, "max_iters = %d, check_every = %d: must not be negative", opt->max_iters, opt->check_every);
+    if (!(opt->rtol >= 0) || !std::isfinite(opt->rtol)) return fail(CVR_ERR_INVALID, "rtol = %g: must be finite and not negative", opt->rtol);
+    for (int i = 0; i < 4; i++)
+        if (opt->reserved[i] != 0) return fail(CVR_ERR_INVALID, "cvr_cg_options.reserved[%d] = %d: must be 0", i, opt->reserved[i]);
+    return CVR_OK;
+}
+
+// behind the argument checks
+int cg_device(cvr_handle *h, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg before cvr_preprocess");
+    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    Range range("cvr_cg_device");
+    HIP_TRY(hipSetDevice(h->device));
+    const long long n = h->info.nrows;
+    const bool      f32 = h->vsz == 4;
+    const void     *minv = opt->minv_dev;
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
+
+    Workspace w;
+    {
+        auto         up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t np = up(h->vsz * (size_t)std::max<int64_t>(h->info.x_elems, 1)), ny = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
+        const size_t nz = minv ? up(h->vsz * (size_t)std::max<long long>(n, 1)) : 0, npq = up(sizeof(double) * kBlocks), npart = up(sizeof(double) * 3 * kBlocks);
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.arena), np + 2 * ny + nz + npq + npart + up(sizeof(CgCell))));
+        uint8_t *a = w.arena;
+        w.p = a; a += np;
+        w.q = a; a += ny;
+        w.r = a; a += ny;
+        w.z = minv ? a : nullptr; a += nz;
+        w.part_pq = reinterpret_cast<double *>(a); a += npq;
+        w.part = reinterpret_cast<double *>(a); a += npart;
+        w.cell = reinterpret_cast<CgCell *>(a);
+    }
+    HIP_TRY(hipEventCreate(&w.e0));
+    HIP_TRY(hipEventCreate(&w.e1));
+    HIP_TRY(hipEventRecord(w.e0, st));
+
+    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then z, p and the start's sums
+    const size_t vb = h->vsz * (size_t)n;
+    HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.p) + vb, 0, h->vsz, st));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(w.p, x, vb, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.r, b, vb, hipMemcpyDeviceToDevice, st));
+    }
+    { const int rc = spmv_scaled_enqueue(h, -1.0, w.p, 1.0, w.r, st); if (rc) return rc; }
+    int spmvs = 1;
+    HIP_TRY(f32 ? launch_init<float>(w, b, minv, n, al, st) : launch_init<double>(w, b, minv, n, al, st));
+    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, minv ? 1 : 0, opt->rtol, w.cell);
+    HIP_TRY(hipGetLastError());
+
+    CgCell cell{};
+    for (int done = 0;;) {
+        const int batch = std::min(every, opt->max_iters - done);
+        for (int i = 0; i < batch; i++) {
+            HIP_TRY(run_spmv(h, w.p, w.q, st));
+            spmvs++;
+            HIP_TRY(f32 ? launch_step<float>(w, x, minv, n, al, done + i, opt->rtol, st) : launch_step<double>(w, x, minv, n, al, done + i, opt->rtol, st));
+        }
+        done += batch;
+        HIP_TRY(hipMemcpyAsync(&cell, w.cell, sizeof(cell), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (cell.stop || done >= opt->max_iters) break;
+    }
+    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    HIP_TRY(hipEventRecord(w.e1, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
+    memset(res, 0, sizeof(*res));
+    res->iterations = cell.iters;
+    res->status = cell.status;
+    res->spmv_count = spmvs;
+    res->residual_norm = cell.rnorm;
+    res->b_norm = cell.bnorm;
+    res->seconds = (double)ms * 1e-3;
+    return CVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void cvr_cg_default_options(cvr_cg_options *opt)
+{
+    if (!opt) return;
+    memset(opt, 0, sizeof(*opt));
+    opt->max_iters = 1000;
+    opt->check_every = 0;
+    opt->rtol = 1e-8;
+}
+
+int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream)
+{
+    if (const int rc = check_args(h, b_dev, x_dev, opt, res)) return rc;
+    return cg_device(h, b_dev, x_dev, opt, res, (hipStream_t)stream);
+}
+
+int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res)
+{
+    if (const int rc = check_args(h, b_host, x_host, opt, res)) return rc;
+    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg before cvr_preprocess");
+    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t vb = h->vsz * (size_t)h->info.nrows;          // the handle's own vectors carry b and x: d_x has ncols + 1 values, d_y at least nrows
+    if (vb) {
+        HIP_TRY(hipMemcpyAsync(h->d_x, x_host, vb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->d_y, b_host, vb, hipMemcpyHostToDevice, h->stream));
+    }
+    const int rc = cg_device(h, h->d_y, h->d_x, opt, res, h->stream);
+    if (rc) return rc;
+    if (vb) HIP_TRY(hipMemcpyAsync(x_host, h->d_x, vb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return CVR_OK;
+}
+
+}  // extern "C"

@@ -220,6 +220,8 @@ IOpt       make_iopt(const cvr_options *in);
 // writes it: enter before, leave after.
 hipError_t handle_enter(cvr_handle *h, hipStream_t st);
 hipError_t handle_leave(cvr_handle *h, hipStream_t st);
+// ---- cvr_scaled.hip: cvr_spmv_scaled_device behind its argument checks (a preprocessed handle; the conjugate-gradient solver's initial residual)
+int        spmv_scaled_enqueue(cvr_handle *h, double alpha, const void *x, double beta, void *y, hipStream_t st);
 // ---- cvr_update.hip: mutable_values -- the parts table of the update kernels, and what follows a conversion (map on the first, creation values)
 int        mutable_tables(cvr_handle *h);
 int        mutable_after_convert(cvr_handle *h, bool keep_csr);

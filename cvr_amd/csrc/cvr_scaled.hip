@@ -52,6 +52,10 @@ int scaled_device(cvr_handle *h, double alpha, const void *x, double beta, void 
 
 }  // namespace
 
+namespace cvrh {
+int spmv_scaled_enqueue(cvr_handle *h, double alpha, const void *x, double beta, void *y, hipStream_t st) { return scaled_device(h, alpha, x, beta, y, st); }
+}  // namespace cvrh
+
 extern "C" {
 
 int cvr_spmv_scaled_device(cvr_handle *h, double alpha, const void *x_dev, double beta, void *y_dev, void *stream)

@@ -131,6 +131,36 @@ def banded_sym(n, half_band=13, seed=7, dtype=np.float64):
     return n, n, rp, cols.astype(np.int32), vals
 
 
+def spd_from_pattern(n, rp, ci, c=0.5, dscale=None, dtype=np.float64):
+    """A symmetric positive definite matrix with a known condition bound from any square pattern (the solver's test matrices):
+    W = P u P^T without the diagonal and without duplicates, d_i = the degree of vertex i in W, A = I + c D^-1/2 W D^-1/2.  The normalised
+    adjacency has its spectrum in [-1, 1], so A's lies in [1 - c, 1 + c] -- kappa(A) <= 3 for c = 0.5 whatever the degrees, isolated
+    vertices (rows with the diagonal alone) included.  dscale = s (n positive values): S A S instead, badly conditioned as s spreads, whose
+    Jacobi preconditioner 1 / s^2 (the inverse of its diagonal) gives A's spectrum back.  Entries are computed in fp64 and symmetric bit for
+    bit (also after rounding to dtype).  Returns (n, n, row_ptr, col_idx, vals) like the generators above."""
+    rp = np.asarray(rp, dtype=np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    cols = np.asarray(ci[: rp[-1]], dtype=np.int64)
+    off = rows != cols
+    rows, cols = rows[off], cols[off]
+    key = np.unique(np.concatenate([rows * np.int64(n) + cols, cols * np.int64(n) + rows]))
+    wr, wc = key // n, key % n
+    deg = np.bincount(wr, minlength=n).astype(np.float64)
+    wv = c / np.sqrt(deg[wr] * deg[wc])
+    diag = np.arange(n, dtype=np.int64)
+    key = np.concatenate([key, diag * np.int64(n) + diag])
+    val = np.concatenate([wv, np.ones(n)])
+    order = np.argsort(key, kind="stable")
+    key, val = key[order], val[order]
+    r, cc = key // n, key % n
+    if dscale is not None:
+        s = np.asarray(dscale, dtype=np.float64)
+        val = (s[r] * s[cc]) * val
+    out_rp = np.zeros(n + 1, dtype=np.int64)
+    out_rp[1:] = np.cumsum(np.bincount(r, minlength=n))
+    return n, n, out_rp, cc.astype(np.int32), val.astype(dtype)
+
+
 def x_rand(n, dtype=np.float64):
     """splitmix64(0xC0FFEE, j) -> uniform [-1, 1): identical to cvr_fill_x(mode 1) and the oracle's orc_x_rand"""
     j = np.arange(n, dtype=np.uint64)

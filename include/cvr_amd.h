@@ -377,6 +377,64 @@ int cvr_spmv_gather_repeat(cvr_handle *h, cvr_comm *comm, const void *x_dev, voi
 int cvr_power_iteration(cvr_handle *h, cvr_comm *comm, const int64_t *bounds, int iters, void *x_dev, double *lambda,
                         double *seconds_per_iter, void *stream);
 
+/* ---- solving A x = b: conjugate gradients on the device -------------------------------------------------
+ * For a symmetric positive definite A held by a single-GPU handle of a square matrix (any layout; fused-preprocess, image-cache, mutable
+ * and transposed handles included).  The whole loop runs on the device: the scalars live in a small state cell in device memory, every
+ * vector kernel forms the scalar it needs from the partial sums of the kernel before (in every workgroup, in the same order), and the host
+ * reads the cell back once per `check_every` iterations.  (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.) */
+typedef struct {
+    int32_t     max_iters;    /* >= 0; 0: only the initial residual is formed and tested                 */
+    int32_t     check_every;  /* iterations enqueued between two read-backs of the state cell; 0 = default */
+    double      rtol;         /* stop when ||r||_2 <= rtol * ||b||_2 (recurrence residual); finite, >= 0    */
+    const void *minv_dev;     /* NULL, or nrows values of the handle's type: z = minv .* r (Jacobi and the like) */
+    int32_t     reserved[4];  /* must be 0 (CVR_ERR_INVALID otherwise)                                       */
+} cvr_cg_options;
+
+#define CVR_CG_CONVERGED 0
+#define CVR_CG_MAX_ITERS 1
+#define CVR_CG_BREAKDOWN 2    /* p.Ap <= 0 or not finite: A is not positive definite on the Krylov space */
+
+typedef struct {
+    int32_t iterations;       /* CG steps applied to x                                                    */
+    int32_t status;           /* CVR_CG_*                                                                  */
+    int32_t spmv_count;       /* SpMV launches enqueued, incl. the initial residual and any behind the stop */
+    int32_t reserved;
+    double  residual_norm;    /* ||r||_2 of the recurrence at the stop                                     */
+    double  b_norm;
+    double  seconds;          /* HIP events around everything enqueued                                     */
+} cvr_cg_result;
+
+/* max_iters = 1000, check_every = 0 (the default batch: 8 iterations per read-back), rtol = 1e-8, no preconditioner, reserved = 0 */
+void cvr_cg_default_options(cvr_cg_options *opt);
+/* b_dev and x_dev: nrows values each of the handle's type, in the memory of the handle's device; x_dev is the start vector on entry and the
+ * solution on exit.  Neither needs a pad element or a scratch tail: the search direction p (info.x_elems values, p[ncols] == 0) and q = A p
+ * (info.yext_elems values), the residual r and (with minv_dev) z are buffers of the library, allocated per call.
+ * Arithmetic, T = the handle's type, every operation below rounded on its own (no fused multiply-add):
+ *   r = b - A x by one cvr_spmv_scaled_device with alpha = -1, beta = 1 (in T);  z = T(minv * r), or z is r itself without minv_dev;  p = z;
+ *   per step: q = A p through cvr_spmv_device's launch path (bit for bit its y for the same p);  alpha = (r.z) / (p.q);
+ *     x = T(double(x) + alpha * double(p));  r = T(double(r) - alpha * double(q));  z = T(double(minv) * double(r));
+ *     beta = (r.z)_new / (r.z)_old;  p = T(double(z) + beta * double(p)).
+ *   The sums p.q, r.z, r.r and b.b are accumulated in fp64 from the rounded T values in a fixed tree (1024 workgroups of 256 threads, each
+ *   thread over its 16-byte packets in order, then lanes, wavefronts and workgroups in a fixed order; no atomics): a call gives the same bits
+ *   every time, whatever the alignment of b_dev, x_dev and minv_dev (16-byte loads and stores are used where they are 16-byte aligned).
+ *   alpha and beta are fp64 quotients of those sums.
+ * Stop rule, evaluated on the device after every step (and once for the start vector): sqrt(r.r) <= rtol * sqrt(b.b) is CVR_CG_CONVERGED;
+ * p.q <= 0 or not finite is CVR_CG_BREAKDOWN, found before the step is applied, so x stays at the last iterate; max_iters steps without
+ * either is CVR_CG_MAX_ITERS with x the last iterate and residual_norm its recurrence residual.  b == 0: x = 0, 0 iterations, converged.
+ * A start vector within the tolerance: 0 iterations, x untouched.
+ * check_every: the kernel that finds the stop records it in the state cell, and every later vector kernel of the batch returns without
+ * writing, so x, iterations, status and residual_norm are bit for bit the same for every check_every; only spmv_count and seconds differ
+ * (the SpMVs behind the stop write only q).  Three vector launches beside the SpMV per step.
+ * Ordering: everything is enqueued on `stream` (NULL = HIP's null stream) and the stream is synchronised at every read-back and before the
+ * call returns: it cannot be captured in a HIP graph.  A mutable handle's image, column panels' partial sums and a hub table's copy of x are
+ * ordered with other launches of the handle as cvr_spmv_device orders them.  Makes the handle's device current.
+ * Errors: null handle, b, x, opt or res; max_iters or check_every < 0; rtol negative or not finite; a non-zero reserved word: CVR_ERR_INVALID,
+ * before any device work and before the handle is looked at.  nrows != ncols: CVR_ERR_INVALID.  Before cvr_preprocess: CVR_ERR_STATE. */
+int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out): copied up, cvr_cg_device on the handle's stream, x copied back.
+ * opt->minv_dev stays a device pointer. */
+int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
