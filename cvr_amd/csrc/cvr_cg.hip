@@ -157,7 +157,9 @@ __global__ __launch_bounds__(kThreads) void cg_check_kernel(const double *__rest
     c.rz[0] = pre ? s[1] : s[0]; c.rz[1] = 0;
     c.stop = 0; c.status = CVR_CG_MAX_ITERS; c.iters = 0; c.zero_x = 0;
     if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
-    else if (c.rnorm <= rtol * c.bnorm) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
+    // (an Inf in b makes both norms infinite, and Inf <= rtol * Inf holds: a residual that is not finite never counts as converged -- step 0 then
+    // finds p . q not finite and records the breakdown)
+    else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= 1.7976931348623157e308) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
     *cell = c;
 }
 

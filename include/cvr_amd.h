@@ -421,6 +421,8 @@ void cvr_cg_default_options(cvr_cg_options *opt);
  * Stop rule, evaluated on the device after every step (and once for the start vector): sqrt(r.r) <= rtol * sqrt(b.b) is CVR_CG_CONVERGED;
  * p.q <= 0 or not finite is CVR_CG_BREAKDOWN, found before the step is applied, so x stays at the last iterate; max_iters steps without
  * either is CVR_CG_MAX_ITERS with x the last iterate and residual_norm its recurrence residual.  b == 0: x = 0, 0 iterations, converged.
+ * A NaN or an Inf in b or among A's values makes p.q of step 0 not finite: CVR_CG_BREAKDOWN with 0 iterations and x untouched (a residual norm
+ * that is not finite never counts as converged, although Inf <= rtol * Inf holds).
  * A start vector within the tolerance: 0 iterations, x untouched.
  * check_every: the kernel that finds the stop records it in the state cell, and every later vector kernel of the batch returns without
  * writing, so x, iterations, status and residual_norm are bit for bit the same for every check_every; only spmv_count and seconds differ

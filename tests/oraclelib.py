@@ -238,8 +238,40 @@ class Cvr64:
 
 
 def tol_check(y, yref, absy, tol=1e-12):
-    """|y - y_ref| <= tol * sum_j |a_ij x_j| + tiny, per row"""
-    err = np.abs(np.asarray(y, dtype=np.float64) - yref)
-    bound = tol * absy + 1e-300
-    bad = np.nonzero(err > bound)[0]
-    return bad, (err / np.maximum(absy, 1e-300)).max() if len(err) else 0.0
+    """|y - y_ref| <= tol * sum_j |a_ij x_j| + tiny, per row.  A row is good only if that holds, or y and y_ref are both
+    NaN, or both the same signed infinity; every other row is bad -- a NaN in y against a finite y_ref above all (`err > bound` is
+    false for a NaN err: the rule is written as `not (err <= bound)`).  Returns (bad rows, worst err / sum|a x|): inf when a bad row
+    is not finite, never nan."""
+    y = np.asarray(y, dtype=np.float64)
+    yref = np.asarray(yref, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs(y - yref)
+        bound = tol * absy + 1e-300
+        same = (np.isnan(y) & np.isnan(yref)) | (np.isinf(y) & (y == yref))
+        good = ((err <= bound) & np.isfinite(err)) | same          # (an infinite err is never within an infinite bound)
+        rel = err / np.maximum(absy, 1e-300)
+    bad = np.nonzero(~good)[0]
+    if not len(err):
+        return bad, 0.0
+    rel = np.where(np.isnan(rel) | same, np.where(good, 0.0, np.inf), rel)
+    return bad, rel.max()
+
+
+def gang_ystage(info, f32):
+    """accumulators per chunk of a gang handle, from its LDS size: 80 bytes of header, the dictionary table if any, the rest shared by the wavefronts"""
+    vs = 4 if f32 else 8
+    return (info.lds_bytes - 80 - (256 * vs if info.value_dict else 0)) // (info.waves_per_block * vs)
+
+
+def mirror_of_handle(info, f32, nrows, ncols, rp, ci, va, thr=0, S=None):
+    """the CPU mirror of a one-image handle built with the handle's own parameters (cvr_info), and the names of the exported tables that are
+    compared with it bit for bit: gang chunks, interleaved chunks, or the segment layouts (phases, hub table, narrow columns, tags)"""
+    i = info
+    S = i.steps_per_chunk if S is None else S
+    if i.gang:
+        return Cvr64(nrows, ncols, rp, ci, va, S, use_dict=i.value_dict > 0, max_rows=i.chunk_row_cap, tag16=i.row_tags16, gang=i.gang,
+                     ystage=gang_ystage(i, f32)), ("image", "desc", "shared", "gbase")
+    if i.interleave:
+        return Cvr64(nrows, ncols, rp, ci, va, S, use_dict=i.value_dict > 0, max_rows=i.chunk_row_cap, tag16=i.row_tags16, interleave=True), ("image", "desc", "shared")
+    return Cvr64(nrows, ncols, rp, ci, va, S, thr, use_dict=i.value_dict > 0, phases=i.col_phases, max_rows=i.chunk_row_cap, hub_max=i.hub_entries, narrow=i.narrow_cols,
+                 reorder=i.hub_reorder, tag16=i.row_tags16, piece_max=i.piece_max), ("image", "desc", "target", "shared")

@@ -23,7 +23,7 @@ def _check(nrows, ncols, rp, ci, va, S, thr=0):
         y = m.spmv(x)
         bad, worst = O.tol_check(y, yref, absy, tol=1e-5 if f32 else 1e-12)
         if f32:
-            bad = bad[np.abs(np.asarray(y, dtype=np.float64) - yref)[bad] > 1e-6 * np.maximum(1.0, absy[bad])]
+            bad = bad[~(np.abs(np.asarray(y, dtype=np.float64) - yref)[bad] <= 1e-6 * np.maximum(1.0, absy[bad]))]      # (a NaN row stays bad)
         assert len(bad) == 0, (mode, S, worst, bad[:5])
     return m
 
@@ -309,3 +309,73 @@ def test_gang_mirror_fp32_and_limits():
         O.Cvr64(nrows, ncols, rp, ci, va, 16, max_rows=500, tag16=0, gang=8, ystage=8192)
     with pytest.raises(RuntimeError):          # a chunk's rows must leave room for its dump entry
         O.Cvr64(nrows, ncols, rp, ci, va, 16, max_rows=512, tag16=0, gang=4, ystage=512)
+
+
+# ---- non-finite x: a row of y is non-finite exactly when it owns an element in a poisoned column (cases.expected_class) ----
+def _mirror_variants(nrows, ncols, rp, ci):
+    """(name, build(vals) -> Cvr64, wants few distinct values) for every variant of the format the mirror builds"""
+    cap = lambda S: min(64 * S, 2000)          # noqa: E731
+    out = [("plain", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8), False),
+           ("split", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 4, 16), False),
+           ("dict", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 4, use_dict=True), True),
+           ("narrow", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8, narrow=True), False),
+           ("hub", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8, hub_max=300), False),
+           ("hub_reorder", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8, hub_max=300, reorder=True), False),
+           ("interleave", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 16, max_rows=cap(16), tag16=1, interleave=True), False),
+           ("interleave_dict", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 16, use_dict=True, max_rows=cap(16), tag16=1, interleave=True), True)]
+    if ncols >= 320:
+        out += [("phases3", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8, phases=3, max_rows=cap(8)), False),
+                ("tag16", lambda v: O.Cvr64(nrows, ncols, rp, ci, v, 8, phases=3, max_rows=cap(8), tag16=1, piece_max=1), False)]
+
+    def gang(v):
+        try:
+            return O.Cvr64(nrows, ncols, rp, ci, v, 16, max_rows=511, tag16=0, gang=4, ystage=512)
+        except RuntimeError:          # (a column further than 2^17 from its group's first: 16-bit tags, as the product does)
+            return O.Cvr64(nrows, ncols, rp, ci, v, 16, max_rows=511, tag16=1, gang=4, ystage=512)
+    return out + [("gang", gang, False)]
+
+
+def _bits_equal(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_mirror_contains_non_finite_x(name, prec):
+    """Inf / NaN in x reach exactly the rows that own an element in such a column, with the class the terms give; every other row is bit for
+    bit the mirror's y for the same x with those entries set to 0 -- a pad slot, a tail slot or a steal that read a wrong element of x would
+    turn a clean row into NaN.  And x = Inf (NaN) everywhere with no zero value: Inf (NaN) in every row with a non-zero, +0.0 in every empty one."""
+    dtype = np.float64 if prec == "fp64" else np.float32
+    nrows, ncols, rp, ci, va = (CASES if dtype == np.float64 else CASES32)[name]
+    few = (((np.arange(len(va)) % 13) - 3) * 0.5).astype(dtype)
+    x = O.x_vec_fast(ncols, "rand").astype(dtype)
+    patterns = list(K.poison_patterns(nrows, ncols, rp, ci, np.random.default_rng([20261017, sorted(CASES).index(name)])))
+    assert {"last_col", "first_col", "hot", "random2pct"} <= {p[0] for p in patterns}
+    empty = np.diff(rp) == 0
+    built = []
+    for vname, build, wants_few in _mirror_variants(nrows, ncols, rp, ci):
+        v = few if wants_few else va
+        try:
+            mir = build(v)
+        except RuntimeError:          # (a variant the mirror does not build for this matrix, e.g. 16-bit columns over a wide chunk)
+            continue
+        built.append(vname)
+        for pname, cols, fill in patterns:
+            xp, x0 = K.poisoned(x, cols, fill)
+            want = K.expected_class(rp, ci, v, xp)
+            y, y0 = mir.spmv(xp), mir.spmv(x0)
+            assert np.array_equal(K.classify(y), want), (vname, pname, np.flatnonzero(K.classify(y) != want)[:8])
+            fin = want == K.FINITE
+            assert _bits_equal(y[fin], y0[fin]), (vname, pname)
+            assert np.isfinite(y0).all()
+        vpos = (np.abs(v) + dtype(0.25)).astype(dtype)          # no zero value: every term of x = Inf is +Inf
+        mpos = build(vpos)
+        for fillv in (np.inf, np.nan):
+            y = mpos.spmv(np.full(ncols, fillv, dtype=dtype))
+            assert _bits_equal(y[empty], np.zeros(int(empty.sum()), dtype=dtype)), (vname, fillv)          # the bits of +0.0
+            assert np.isnan(y[~empty]).all() if np.isnan(fillv) else np.all(y[~empty] == np.inf), (vname, fillv)
+    assert "plain" in built and "interleave" in built and "gang" in built, built
+    if name == "power_law_3000":
+        assert set(built) >= {"plain", "split", "dict", "hub", "hub_reorder", "interleave", "interleave_dict", "phases3", "tag16", "gang"}, built
+    if name == "uniform_2000":
+        assert "narrow" in built

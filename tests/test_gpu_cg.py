@@ -32,23 +32,8 @@ torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# the layout table of tests/test_gpu_spmv_scaled.py
-LAYOUTS = dict(
-    plain=dict(steps_per_chunk=16, col_panels=1, col_phases=0, hub_table=0, narrow_cols=0, interleave=0, gang=0),
-    narrow=dict(steps_per_chunk=16, col_panels=1, col_phases=0, hub_table=0, narrow_cols=1),
-    window=dict(steps_per_chunk=12, waves_per_block=8, x_window=2048, col_phases=0, col_panels=1),
-    phases=dict(steps_per_chunk=12, waves_per_block=8, x_window=2048, col_phases=6, col_panels=1),
-    phases_tags_pieces=dict(steps_per_chunk=24, waves_per_block=4, x_window=2048, col_phases=4, row_tags16=1, piece_max=8, col_panels=1),
-    hub=dict(hub_table=300, steps_per_chunk=16, col_panels=1),
-    hub_reorder=dict(hub_table=300, hub_reorder=1, steps_per_chunk=16, col_panels=1),
-    panels=dict(col_panels=3, steps_per_chunk=16),
-    interleaved=dict(col_panels=1, interleave=1, steps_per_chunk=32, waves_per_block=4),
-    interleaved_panels=dict(col_panels=8, interleave=1),
-    gang=dict(col_panels=1, interleave=1, steps_per_chunk=32, waves_per_block=4, gang=1),
-    gang_tags=dict(col_panels=1, interleave=1, steps_per_chunk=16, waves_per_block=2, gang=1, row_tags16=1),
-    nvec=dict(nvec=4),
-)
-ALL_LAYOUTS = dict(LAYOUTS, default={})
+LAYOUTS = K.LAYOUTS          # (the shared layout table: tests/cases.py)
+ALL_LAYOUTS = K.ALL_LAYOUTS
 
 RTOL = {np.float64: 1e-10, np.float32: 1e-4}
 BOUND = {np.float64: 19, np.float32: 8}          # steps to rtol for kappa <= 3 (module docstring)

@@ -40,6 +40,24 @@ def _random_case(rng):
     return K.csr_from_lengths(lens, ncols, rng, sort=srt) + (srt,)
 
 
+def _check_non_finite_x(A, nrows, ncols, rp, ci, va, x, seed, case, ctx):
+    """2 % of the columns of x set to +Inf / NaN / -Inf (drawn from a child generator: the loop's own sequence of matrices and options stays what
+    it is): the class of every row is the one its terms give, and the rows classed finite are bit for bit those of the run with these entries of
+    x set to 0 -- their terms are the same in both runs"""
+    if ncols == 0:
+        return
+    child = np.random.default_rng([seed, case])
+    _, cols, fill = [p for p in K.poison_patterns(nrows, ncols, rp, ci, child) if p[0] == "random2pct"][0]
+    xp, x0 = K.poisoned(x, cols, fill)
+    want = K.expected_class(rp, ci, va, xp)
+    yp, _ = A.spmv(xp)
+    y0, _ = A.spmv(x0)
+    got = K.classify(yp)
+    assert np.array_equal(got, want), (ctx, "non-finite x: rows", np.flatnonzero(got != want)[:5])
+    fin = want == K.FINITE
+    assert np.isfinite(y0).all() and np.array_equal(yp[fin].view(np.uint8), y0[fin].view(np.uint8)), (ctx, "non-finite x: finite rows differ")
+
+
 def test_fuzz_parity_through_the_device_planner():
     """the same cases with every matrix planned on the device (cvr_plan_dev.hip; cvr_create uses it from 200 000 rows on):
     the image is still the mirror's bit for bit"""
@@ -52,7 +70,8 @@ def test_fuzz_parity_through_the_device_planner():
 
 def test_fuzz_parity(ncases=None, seed=None):
     ncases = int(os.environ.get("CVR_FUZZ_CASES", "160")) if ncases is None else ncases
-    rng = np.random.default_rng(int(os.environ.get("CVR_FUZZ_SEED", "20261002")) if seed is None else seed)
+    seed = int(os.environ.get("CVR_FUZZ_SEED", "20261002")) if seed is None else seed
+    rng = np.random.default_rng(seed)
     for case in range(ncases):
         nrows, ncols, rp, ci, va, srt = _random_case(rng)
         f32 = bool(rng.integers(0, 4) == 0)
@@ -94,8 +113,7 @@ def test_fuzz_parity(ncases=None, seed=None):
             ph = A.info.col_phases
         ctx["from_dev"] = bool(from_dev)
         if P == 1:
-            mir = O.Cvr64(nrows, ncols, rp, ci, va, S, thr, use_dict=A.info.value_dict > 0, phases=ph, max_rows=A.info.chunk_row_cap, hub_max=A.info.hub_entries, narrow=A.info.narrow_cols, reorder=A.info.hub_reorder,
-                          tag16=A.info.row_tags16, piece_max=A.info.piece_max)
+            mir, _ = O.mirror_of_handle(A.info, f32, nrows, ncols, rp, ci, va, thr=thr, S=S)
             img = A.export_image()
             assert np.array_equal(img["image"], mir.image) and np.array_equal(img["desc"], mir.desc), ctx
             assert np.array_equal(img["target"], mir.target) and np.array_equal(img["shared"], mir.shared), ctx
@@ -106,6 +124,7 @@ def test_fuzz_parity(ncases=None, seed=None):
         assert len(bad) == 0, (ctx, bad[:5], worst)
         y2, _ = A.spmv(x)
         assert np.array_equal(y.view(np.uint8), y2.view(np.uint8)), ctx
+        _check_non_finite_x(A, nrows, ncols, rp, ci, va, x, seed, case, ctx)
         A.close()
 
 
@@ -113,7 +132,8 @@ def test_fuzz_interleaved_chunks():
     """cvr_options.interleave over the same random shapes (sorted or unsorted rows, host or device planner): one image -> the CPU mirror's
     bits (orc_cvr64_build_ilv) and y of the mirror; column panels -> y against the CSR oracle; reruns bit for bit"""
     ncases = int(os.environ.get("CVR_FUZZ_CASES", "120"))
-    rng = np.random.default_rng(int(os.environ.get("CVR_FUZZ_SEED", "20261006")))
+    seed = int(os.environ.get("CVR_FUZZ_SEED", "20261006"))
+    rng = np.random.default_rng(seed)
     for case in range(ncases):
         nrows, ncols, rp, ci, va, srt = _random_case(rng)
         f32 = bool(rng.integers(0, 4) == 0)
@@ -146,12 +166,7 @@ def test_fuzz_interleaved_chunks():
         assert len(bad) == 0, (ctx, bad[:5], worst)
         assert (i.gang > 0) == (gang > 0 and i.waves_per_block >= 2), ctx
         if i.col_panels == 1:
-            if i.gang:
-                vs = 4 if f32 else 8
-                ystage = (i.lds_bytes - 80 - (256 * vs if i.value_dict else 0)) // (i.waves_per_block * vs)
-                mir = O.Cvr64(nrows, ncols, rp, ci, va, i.steps_per_chunk, use_dict=i.value_dict > 0, max_rows=i.chunk_row_cap, tag16=i.row_tags16, gang=i.gang, ystage=ystage)
-            else:
-                mir = O.Cvr64(nrows, ncols, rp, ci, va, i.steps_per_chunk, use_dict=i.value_dict > 0, max_rows=i.chunk_row_cap, tag16=i.row_tags16, interleave=True)
+            mir, _ = O.mirror_of_handle(i, f32, nrows, ncols, rp, ci, va)
             img = A.export_image()
             assert np.array_equal(img["image"], mir.image) and np.array_equal(img["desc"], mir.desc) and np.array_equal(img["shared"], mir.shared), ctx
             if i.gang:
@@ -160,6 +175,7 @@ def test_fuzz_interleaved_chunks():
                 assert np.array_equal(y.view(np.uint8), mir.spmv(x).view(np.uint8)), ctx
         y2, _ = A.spmv(x)
         assert np.array_equal(y.view(np.uint8), y2.view(np.uint8)), ctx
+        _check_non_finite_x(A, nrows, ncols, rp, ci, va, x, seed, case, ctx)
         A.close()
 
 

@@ -56,3 +56,69 @@ def test_oracle64_equals_pinned_oracle_on_the_gpu_box(name):
 @pytest.mark.parametrize("name", NAMES)
 def test_host_csr_loop_equals_reference_on_the_gpu_box(name):
     _host_loop_is_the_reference_loop(name)
+
+
+# ---- the shared row checker (oraclelib.tol_check): non-finite rows ----
+def _tol_check_before(y, yref, absy, tol=1e-12):
+    """the checker as it was (NaN-blind: `err > bound` is false for a NaN err); the new one must equal it on finite data"""
+    err = np.abs(np.asarray(y, dtype=np.float64) - yref)
+    bound = tol * absy + 1e-300
+    bad = np.nonzero(err > bound)[0]
+    return bad, (err / np.maximum(absy, 1e-300)).max() if len(err) else 0.0
+
+
+def test_tol_check_non_finite_rows():
+    nan, inf = np.nan, np.inf
+    absy = np.array([1.0, 2.0, 3.0])
+    bad, worst = O.tol_check([nan, 2, inf], [1, 2, 3], absy)
+    assert bad.tolist() == [0, 2] and worst == inf                       # NaN or Inf against finite is bad
+    bad, worst = O.tol_check([nan, 2.0, 3.0], [nan, 2.0, 3.0], absy)
+    assert bad.tolist() == [] and worst == 0.0                           # NaN against NaN is good
+    bad, worst = O.tol_check([inf, -inf, 3.0], [inf, -inf, 3.0], absy)
+    assert bad.tolist() == [] and worst == 0.0                           # the same signed infinity is good
+    bad, worst = O.tol_check([inf, -inf, 3.0], [-inf, inf, 3.0], absy)
+    assert bad.tolist() == [0, 1] and worst == inf                       # +Inf against -Inf is bad
+    bad, worst = O.tol_check([1.0, nan, inf], [nan, inf, nan], absy)
+    assert bad.tolist() == [0, 1, 2] and worst == inf                    # finite against NaN, NaN against Inf, Inf against NaN
+    # sum |a x| of a poisoned row is itself Inf or NaN: the bound is not finite, the rule still holds
+    for a in (inf, nan):
+        absy = np.array([a, a, a, a, 1.0])
+        bad, worst = O.tol_check([1.0, nan, inf, nan, 5.0], [inf, 1.0, inf, nan, 5.0], absy)
+        assert bad.tolist() == [0, 1] and worst == inf, a
+        bad, worst = O.tol_check([nan, nan, -inf, inf, 5.0], [nan, nan, -inf, inf, 5.0], absy)
+        assert bad.tolist() == [] and not np.isnan(worst), a
+    # a finite wrong row among good non-finite ones: worst is that row's, not nan
+    bad, worst = O.tol_check([nan, 2.5, inf], [nan, 2.0, inf], np.array([1.0, 2.0, 3.0]))
+    assert bad.tolist() == [1] and worst == 0.25
+
+
+def test_tol_check_empty_arrays():
+    e = np.zeros(0)
+    bad, worst = O.tol_check(e, e, e)
+    assert len(bad) == 0 and worst == 0.0
+    bad, worst = O.tol_check(e.astype(np.float32), e, e, tol=1e-5)
+    assert len(bad) == 0 and worst == 0.0
+
+
+def test_tol_check_unchanged_on_finite_data():
+    """finite inputs: the same bad rows and the same worst figure, bit for bit, as before -- random rows, rows exactly at the bound (good),
+    one ulp-scale step beyond it (bad), rows with sum |a x| = 0"""
+    rng = np.random.default_rng(20261017)
+    tol = 2.0 ** -20
+    for n in (1, 7, 1000):
+        yref = rng.integers(-1, 2, size=n).astype(np.float64)
+        absy = np.ones(n)                                                # bound = 2^-20 (+ 1e-300, absorbed): y = yref + 2^-20 is exact
+        step = rng.choice([0.0, 2.0 ** -21, 2.0 ** -20, 2.0 ** -20 + 2.0 ** -50, -(2.0 ** -20), -(2.0 ** -20) - 2.0 ** -50, 2.0 ** -10], size=n)
+        y = yref + step
+        assert np.array_equal(np.abs(y - yref), np.abs(step))            # (the rows at the bound sit exactly on it)
+        got, want = O.tol_check(y, yref, absy, tol=tol), _tol_check_before(y, yref, absy, tol=tol)
+        assert np.array_equal(got[0], want[0]) and got[1] == want[1]
+        assert np.array_equal(got[0], np.flatnonzero(np.abs(step) > tol))
+        for t in (1e-12, 1e-5):                                          # random data at the suite's tolerances, fp32 y included
+            yref = rng.standard_normal(n)
+            absy = np.abs(yref) * rng.uniform(1, 5, n)
+            absy[rng.random(n) < 0.1] = 0.0
+            y = yref + absy * t * rng.choice([0.0, 0.5, 0.999, 1.001, 2.0, -3.0], size=n) + (rng.random(n) < 0.05) * 1e-200
+            for yy in (y, y.astype(np.float32)):
+                got, want = O.tol_check(yy, yref, absy, tol=t), _tol_check_before(yy, yref, absy, tol=t)
+                assert np.array_equal(got[0], want[0]) and got[1] == want[1], (n, t)
