@@ -97,7 +97,7 @@ class MmMatrix(C.Structure):
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
-           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg",
+           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_bicgstab_device", "cvr_bicgstab",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -148,6 +148,8 @@ def lib():
         L.cvr_cg_default_options.restype = None
         L.cvr_cg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_cg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_bicgstab_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_bicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -616,6 +618,34 @@ class CvrMatrix:
         rc = lib().cvr_cg(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
         if rc:
             raise CvrError(rc, "cvr_cg")
+        return x[: self.nrows], res
+
+    def bicgstab(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
+        """solves A x = b for a nonsymmetric A by right-preconditioned BiCGSTAB on the device (cvr_bicgstab_device): the arguments and the
+        CgResult are cg's (minv_ptr: p^ = minv .* p, s^ = minv .* s; a stop at the half step counts as one iteration; two SpMVs per
+        step); synchronises the stream."""
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
+        rc = lib().cvr_bicgstab_device(self._h, b_ptr, x_ptr, C.byref(opt), C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_bicgstab_device")
+        return res
+
+    def bicgstab_host(self, b, x0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_bicgstab): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device
+        pointer.  Returns (x, CgResult)."""
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        if len(b) < self.nrows:
+            raise ValueError("b is shorter than nrows")
+        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=self.dtype)
+            if len(x0) < self.nrows:
+                raise ValueError("x0 is shorter than nrows")
+            x[: self.nrows] = x0[: self.nrows]
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
+        rc = lib().cvr_bicgstab(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_bicgstab")
         return x[: self.nrows], res
 
     def spmm(self, X, iters=1):

@@ -9,16 +9,12 @@
 // The scalars that outlive a kernel sit in a state cell (CgCell) that workgroup 0 writes: a kernel that finds the stop records it there and every later
 // kernel of the batch returns without writing -- the result does not depend on how many steps the host enqueues between two read-backs.
 // (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
-#include "cvr_internal.h"
+#include "cvr_krylov.h"
 
 using namespace cvrh;
+using namespace cvrh::krylov;
 
 namespace {
-
-constexpr int kBlocks = 1024, kThreads = 256;          // cvr_iter.hip's grid: the partial count is fixed
-constexpr int kWaves = kThreads / 64;
-static_assert(kBlocks == 4 * kThreads, "sum_partials reads four partials per thread");
-constexpr int kDefaultCheckEvery = 8;
 
 // The state cell.  Written by thread 0 of workgroup 0 only; a value a kernel reads is one that a kernel BEFORE it wrote (r.z of the step before sits
 // in rz[k & 1], this step's goes to rz[(k + 1) & 1]) -- except `stop`, which the other workgroups of the kernel that sets it may or may not see yet:
@@ -33,89 +29,6 @@ struct CgCell {
     int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
 };
 
-template <typename T> struct Vec;
-template <> struct Vec<double> { typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct Vec<float> { typedef float type __attribute__((ext_vector_type(4))); };
-template <typename T> constexpr int kPack = 16 / (int)sizeof(T);          // values per 16-byte packet
-
-// the packet at p + e: one 16-byte load when it is whole and p is 16-byte aligned (VEC), else its `cnt` values one by one; the rest 0
-template <typename T, bool VEC>
-__device__ __forceinline__ void load_pack(const T *__restrict__ p, long long e, int cnt, T (&v)[kPack<T>])
-{
-    if (VEC && cnt == kPack<T>) {
-        const typename Vec<T>::type t = *reinterpret_cast<const typename Vec<T>::type *>(p + e);
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) v[j] = t[j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) v[j] = j < cnt ? p[e + j] : (T)0;
-    }
-}
-template <typename T, bool VEC>
-__device__ __forceinline__ void store_pack(T *__restrict__ p, long long e, int cnt, const T (&v)[kPack<T>])
-{
-    if (VEC && cnt == kPack<T>) {
-        typename Vec<T>::type t;
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) t[j] = v[j];
-        *reinterpret_cast<typename Vec<T>::type *>(p + e) = t;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) if (j < cnt) p[e + j] = v[j];
-    }
-}
-
-// s[k] = the sum of the k-th set of kBlocks partials, the same bits in every thread of every workgroup: thread t takes partials t, t + 256, t + 512,
-// t + 768 in that order, the lanes of a wavefront a butterfly, the four wavefronts in order.  Ends behind a barrier (what thread 0 put into LDS
-// before the call is visible after it).
-template <int K>
-__device__ __forceinline__ void sum_partials(const double *__restrict__ part, double (&s)[K], double (&sh)[K][kWaves])
-{
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double a = 0;
-#pragma unroll
-        for (int j = 0; j < kBlocks / kThreads; j++) a += part[(size_t)k * kBlocks + threadIdx.x + j * kThreads];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-        if ((threadIdx.x & 63u) == 0) sh[k][threadIdx.x >> 6] = a;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double a = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) a += sh[k][w];
-        s[k] = a;
-    }
-}
-
-// out[k * kBlocks + workgroup] = the workgroup's sum of acc[k]: dot_partial_kernel's tree
-template <int K>
-__device__ __forceinline__ void store_partials(double (&acc)[K], double *__restrict__ out, double (&sh)[K][kWaves])
-{
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
-        if ((threadIdx.x & 63u) == 0) sh[k][threadIdx.x >> 6] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            double a = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; w++) a += sh[k][w];
-            out[(size_t)k * kBlocks + blockIdx.x] = a;
-        }
-    }
-}
-
-#define CVR_CG_PACKETS(T, e, cnt)                                                                                                  \
-    for (long long e = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPack<T>, cnt = 0; e < n && ((cnt = n - e < kPack<T> ? n - e : kPack<T>), true); \
-         e += (long long)kBlocks * kThreads * kPack<T>)
-
 // The start: r holds b - A x0 (the scaled product).  z = minv .* r (PRE), p = z (or r), and the partial sums of r . r, r . z (PRE) and b . b.
 // AL: b and minv, the caller's arrays, are 16-byte aligned.
 template <typename T, bool PRE, bool AL>
@@ -124,7 +37,7 @@ __global__ __launch_bounds__(kThreads) void cg_init_kernel(const T *__restrict__
 {
     __shared__ double sh[3][kWaves];
     double acc[3] = {0, 0, 0};
-    CVR_CG_PACKETS(T, e, cnt) {
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
         T bv[kPack<T>], rv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
         load_pack<T, AL>(b, e, (int)cnt, bv);
         load_pack<T, true>(r, e, (int)cnt, rv);
@@ -171,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void cg_pq_kernel(const T *__restrict__ p
     __shared__ double sh[1][kWaves];
     if (cell->stop) return;          // (no workgroup of this kernel sets it)
     double acc[1] = {0};
-    CVR_CG_PACKETS(T, e, cnt) {
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
         T pv[kPack<T>], qv[kPack<T>];
         load_pack<T, true>(p, e, (int)cnt, pv);
         load_pack<T, true>(q, e, (int)cnt, qv);
@@ -203,7 +116,7 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(T *__restrict__ x, 
     const double alpha = cell->rz[k & 1] / pq[0];
     if (blockIdx.x == 0 && threadIdx.x == 0) cell->iters = k + 1;
     double acc[K] = {};
-    CVR_CG_PACKETS(T, e, cnt) {
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
         T xv[kPack<T>], rv[kPack<T>], pv[kPack<T>], qv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
         load_pack<T, AL>(x, e, (int)cnt, xv);
         load_pack<T, true>(r, e, (int)cnt, rv);
@@ -248,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(T *__restrict__ 
     }
     if (done) return;
     const double beta = rz / cell->rz[k & 1];
-    CVR_CG_PACKETS(T, e, cnt) {
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
         T pv[kPack<T>], zv[kPack<T>];
         load_pack<T, true>(p, e, (int)cnt, pv);
         load_pack<T, true>(z, e, (int)cnt, zv);
@@ -257,8 +170,6 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(T *__restrict__ 
         store_pack<T, true>(p, e, (int)cnt, pv);
     }
 }
-
-#undef CVR_CG_PACKETS
 
 // the library's buffers of one call, one allocation: p (x_ext), q and r (y_ext each: r takes the scaled product), z, the partial sums, the cell
 struct Workspace {
@@ -299,16 +210,6 @@ hipError_t launch_step(const Workspace &w, void *x, const void *minv, long long 
     if (minv) hipLaunchKernelGGL((cg_direction_kernel<T, true>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.z), n, w.part, w.cell, k, rtol);
     else hipLaunchKernelGGL((cg_direction_kernel<T, false>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.r), n, w.part, w.cell, k, rtol);
     return hipGetLastError();
-}
-
-int check_args(const void *h, const void *b, const void *x, const cvr_cg_options *opt, const cvr_cg_result *res)
-{
-    if (!h || !b || !x || !opt || !res) return fail(CVR_ERR_INVALID, "null argument");
-    if (opt->max_iters < 0 || opt->check_every < 0) return fail(CVR_ERR_INVALID, "max_iters = %d, check_every = %d: must not be negative", opt->max_iters, opt->check_every);
-    if (!(opt->rtol >= 0) || !std::isfinite(opt->rtol)) return fail(CVR_ERR_INVALID, "rtol = %g: must be finite and not negative", opt->rtol);
-    for (int i = 0; i < 4; i++)
-        if (opt->reserved[i] != 0) return fail(CVR_ERR_INVALID, "cvr_cg_options.reserved[%d] = %d: must be 0", i, opt->reserved[i]);
-    return CVR_OK;
 }
 
 // behind the argument checks
@@ -399,13 +300,13 @@ void cvr_cg_default_options(cvr_cg_options *opt)
 
 int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream)
 {
-    if (const int rc = check_args(h, b_dev, x_dev, opt, res)) return rc;
+    if (const int rc = check_solver_args(h, b_dev, x_dev, opt, res)) return rc;
     return cg_device(h, b_dev, x_dev, opt, res, (hipStream_t)stream);
 }
 
 int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res)
 {
-    if (const int rc = check_args(h, b_host, x_host, opt, res)) return rc;
+    if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
     if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg before cvr_preprocess");
     if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
     HIP_TRY(hipSetDevice(h->device));

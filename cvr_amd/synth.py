@@ -161,6 +161,35 @@ def spd_from_pattern(n, rp, ci, c=0.5, dscale=None, dtype=np.float64):
     return n, n, out_rp, cc.astype(np.int32), val.astype(dtype)
 
 
+def nonsym_from_pattern(n, rp, ci, c=0.5, rscale=None, seed=3, dtype=np.float64):
+    """A nonsymmetric, strictly diagonally dominant matrix from any square pattern (the BiCGSTAB solver's test matrices): W = the pattern as
+    it is (not symmetrised) without the diagonal and without duplicates, with seeded weights in [0.5, 1.5) and each row scaled to the absolute
+    sum c; A = I - W.  Gershgorin puts A's spectrum into the disc |z - 1| <= c, so A is nonsingular for c < 1, and it is nonsymmetric in
+    pattern (wherever the pattern is) and in values; rows without an off-diagonal entry hold the diagonal alone.  rscale = s (n positive
+    values): diag(s) A instead, badly scaled by rows as s spreads, whose Jacobi preconditioner is 1 / s (the inverse of its diagonal).
+    Entries are computed in fp64, then rounded to dtype.  Returns (n, n, row_ptr, col_idx, vals) like the generators above."""
+    rp = np.asarray(rp, dtype=np.int64)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    cols = np.asarray(ci[: rp[-1]], dtype=np.int64)
+    off = rows != cols
+    key = np.unique(rows[off] * np.int64(n) + cols[off])
+    wr = key // n
+    w = 0.5 + np.random.default_rng(seed).random(len(key))
+    rowsum = np.bincount(wr, weights=w, minlength=n)
+    wv = -c * w / rowsum[wr]
+    diag = np.arange(n, dtype=np.int64)
+    key = np.concatenate([key, diag * np.int64(n) + diag])
+    val = np.concatenate([wv, np.ones(n)])
+    order = np.argsort(key, kind="stable")
+    key, val = key[order], val[order]
+    r, cc = key // n, key % n
+    if rscale is not None:
+        val = np.asarray(rscale, dtype=np.float64)[r] * val
+    out_rp = np.zeros(n + 1, dtype=np.int64)
+    out_rp[1:] = np.cumsum(np.bincount(r, minlength=n))
+    return n, n, out_rp, cc.astype(np.int32), val.astype(dtype)
+
+
 def x_rand(n, dtype=np.float64):
     """splitmix64(0xC0FFEE, j) -> uniform [-1, 1): identical to cvr_fill_x(mode 1) and the oracle's orc_x_rand"""
     j = np.arange(n, dtype=np.uint64)

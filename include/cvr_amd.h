@@ -377,29 +377,32 @@ int cvr_spmv_gather_repeat(cvr_handle *h, cvr_comm *comm, const void *x_dev, voi
 int cvr_power_iteration(cvr_handle *h, cvr_comm *comm, const int64_t *bounds, int iters, void *x_dev, double *lambda,
                         double *seconds_per_iter, void *stream);
 
-/* ---- solving A x = b: conjugate gradients on the device -------------------------------------------------
- * For a symmetric positive definite A held by a single-GPU handle of a square matrix (any layout; fused-preprocess, image-cache, mutable
- * and transposed handles included).  The whole loop runs on the device: the scalars live in a small state cell in device memory, every
+/* ---- solving A x = b on the device: conjugate gradients and BiCGSTAB ----------------------------------
+ * cvr_cg_device / cvr_cg for a symmetric positive definite A, cvr_bicgstab_device / cvr_bicgstab for any nonsingular A, nonsymmetric ones included,
+ * held by a single-GPU handle of a square matrix (any layout; fused-preprocess, image-cache, mutable and transposed handles included).  Both
+ * solvers share the options, the result and the status codes below.  The whole loop runs on the device: the scalars live in a small state cell in device memory, every
  * vector kernel forms the scalar it needs from the partial sums of the kernel before (in every workgroup, in the same order), and the host
  * reads the cell back once per `check_every` iterations.  (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.) */
 typedef struct {
     int32_t     max_iters;    /* >= 0; 0: only the initial residual is formed and tested                 */
     int32_t     check_every;  /* iterations enqueued between two read-backs of the state cell; 0 = default */
     double      rtol;         /* stop when ||r||_2 <= rtol * ||b||_2 (recurrence residual); finite, >= 0    */
-    const void *minv_dev;     /* NULL, or nrows values of the handle's type: z = minv .* r (Jacobi and the like) */
+    const void *minv_dev;     /* NULL, or nrows values of the handle's type: z = minv .* r (Jacobi and the like);
+                                 BiCGSTAB: the right preconditioner, p^ = minv .* p and s^ = minv .* s             */
     int32_t     reserved[4];  /* must be 0 (CVR_ERR_INVALID otherwise)                                       */
 } cvr_cg_options;
 
 #define CVR_CG_CONVERGED 0
 #define CVR_CG_MAX_ITERS 1
-#define CVR_CG_BREAKDOWN 2    /* p.Ap <= 0 or not finite: A is not positive definite on the Krylov space */
+#define CVR_CG_BREAKDOWN 2    /* CG: p.Ap <= 0 or not finite: A is not positive definite on the Krylov space;
+                                 BiCGSTAB: r^.v, t.t, omega or r^.r zero or not finite                       */
 
 typedef struct {
-    int32_t iterations;       /* CG steps applied to x                                                    */
+    int32_t iterations;       /* steps applied to x (BiCGSTAB: a stop at the half step counts as one)     */
     int32_t status;           /* CVR_CG_*                                                                  */
     int32_t spmv_count;       /* SpMV launches enqueued, incl. the initial residual and any behind the stop */
     int32_t reserved;
-    double  residual_norm;    /* ||r||_2 of the recurrence at the stop                                     */
+    double  residual_norm;    /* ||r||_2 of the recurrence at the stop (||s||_2 at a BiCGSTAB half step)   */
     double  b_norm;
     double  seconds;          /* HIP events around everything enqueued                                     */
 } cvr_cg_result;
@@ -436,6 +439,36 @@ int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_op
 /* the same with host b and x (nrows values each; x in and out): copied up, cvr_cg_device on the handle's stream, x copied back.
  * opt->minv_dev stays a device pointer. */
 int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
+
+/* BiCGSTAB for a nonsymmetric A (needs no A^T): right-preconditioned, shadow residual r^ = r0, two SpMVs per step.  b_dev, x_dev, the options, the
+ * result, the ordering and the errors are cvr_cg_device's; the buffers of the call are the library's, allocated per call: p, s (and with minv_dev
+ * p^, s^) of info.x_elems values whose element ncols stays 0, v, t and r of info.yext_elems values, r^ of nrows values.
+ * Arithmetic, T = the handle's type, every operation below rounded on its own (no fused multiply-add), M = diag(minv), p^ is p and s^ is s without
+ * minv_dev (no extra buffer, no extra pass):
+ *   r = b - A x by one cvr_spmv_scaled_device with alpha = -1, beta = 1 (in T);  r^ = r;  p = r;  p^ = T(minv * p);  rho = r^.r;
+ *   per step: v = A p^ through cvr_spmv_device's launch path (bit for bit its y for the same p^);  alpha = rho / (r^.v);
+ *     s = T(double(r) - alpha * double(v));  s^ = T(double(minv) * double(s));
+ *     if sqrt(s.s) <= rtol * sqrt(b.b):  x = T(double(x) + alpha * double(p^)), CVR_CG_CONVERGED at the half step (counts as one step; residual_norm
+ *       is sqrt(s.s)); the test is made behind t = A s^, so that SpMV is enqueued in any case;
+ *     t = A s^ (the same path);  omega = (t.s) / (t.t);
+ *     x = T((double(x) + alpha * double(p^)) + omega * double(s^));  r = T(double(s) - omega * double(t));
+ *     if sqrt(r.r) <= rtol * sqrt(b.b):  CVR_CG_CONVERGED;
+ *     rho' = r^.r;  beta = (rho' / rho) * (alpha / omega);  p = T(double(r) + beta * (double(p) - omega * double(v)));  p^ = T(double(minv) * double(p));
+ *     rho = rho'.
+ *   The sums r^.v, s.s, t.s, t.t, r.r, r^.r and b.b are accumulated in fp64 from the rounded T values in cvr_cg_device's fixed tree (1024 workgroups
+ *   of 256 threads, each thread over its 16-byte packets in order, then lanes, wavefronts and workgroups in a fixed order; no atomics): a call gives
+ *   the same bits every time, whatever the alignment of b_dev, x_dev and minv_dev.  alpha, omega and beta are fp64 quotients of those sums.
+ * Stop rule, evaluated on the device after every half step and step (and once for the start vector): the two tests above are CVR_CG_CONVERGED;
+ * r^.v, t.t, omega or rho' zero or not finite is CVR_CG_BREAKDOWN, found before the step or half step is applied (rho': before the next one), so x
+ * stays at the last iterate; max_iters steps without either is CVR_CG_MAX_ITERS with x the last iterate and residual_norm its recurrence residual.
+ * b == 0: x = 0, 0 iterations, converged.  A start vector within the tolerance: 0 iterations, x untouched.  A residual norm that is not finite
+ * never counts as converged: a NaN or an Inf in b makes r^.v of step 0 not finite, CVR_CG_BREAKDOWN with 0 iterations and x untouched.
+ * max_iters = 0: the initial residual is formed and tested (spmv_count == 1).
+ * check_every: as for cvr_cg_device -- x, iterations, status and residual_norm are bit for bit the same for every check_every; only spmv_count
+ * (1 + 2 per step enqueued) and seconds differ.  Five vector launches beside the two SpMVs per step. */
+int cvr_bicgstab_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg.  opt->minv_dev stays a device pointer. */
+int cvr_bicgstab(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
 
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
