@@ -97,7 +97,7 @@ class MmMatrix(C.Structure):
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
-           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_bicgstab_device", "cvr_bicgstab",
+           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -148,6 +148,8 @@ def lib():
         L.cvr_cg_default_options.restype = None
         L.cvr_cg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_cg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_cg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_cg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_bicgstab_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_bicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -619,6 +621,37 @@ class CvrMatrix:
         if rc:
             raise CvrError(rc, "cvr_cg")
         return x[: self.nrows], res
+
+    def cg_multi(self, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
+        """solves A X = B for 1 <= nvec <= 8 right-hand sides at once by conjugate gradients on the device (cvr_cg_multi_device): B_ptr and
+        X_ptr are row-major device blocks of nrows rows of ldb / ldx values (X: the start block in, the solutions out), minv_ptr one
+        preconditioner for all columns.  Column j is bit for bit cg()'s result for B[:, j] and X[:, j].  Needs a handle of the plain layout
+        (nvec >= 2 at creation) unless nvec == ldb == ldx == 1.  Returns a list of nvec CgResult; synchronises the stream."""
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), (CgResult * max(int(nvec), 1))()
+        rc = lib().cvr_cg_multi_device(self._h, B_ptr, ldb, X_ptr, ldx, nvec, C.byref(opt), res, stream)
+        if rc:
+            raise CvrError(rc, "cvr_cg_multi_device")
+        return list(res)
+
+    def cg_multi_host(self, B, X0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_cg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec); minv_ptr stays a
+        device pointer.  Returns (X of shape (nrows, nvec), list of CgResult)."""
+        B = np.ascontiguousarray(B, dtype=self.dtype)
+        if B.ndim != 2 or B.shape[0] < self.nrows:
+            raise ValueError("B must be 2-D with at least nrows rows")
+        B = np.ascontiguousarray(B[: self.nrows])
+        k = B.shape[1]
+        X = np.zeros((max(self.nrows, 1), k), dtype=self.dtype)
+        if X0 is not None:
+            X0 = np.asarray(X0, dtype=self.dtype)
+            if X0.ndim != 2 or X0.shape[0] < self.nrows or X0.shape[1] != k:
+                raise ValueError("X0 must have B's shape")
+            X[: self.nrows] = X0[: self.nrows]
+        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), (CgResult * max(k, 1))()
+        rc = lib().cvr_cg_multi(self._h, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)
+        if rc:
+            raise CvrError(rc, "cvr_cg_multi")
+        return X[: self.nrows], list(res)
 
     def bicgstab(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
         """solves A x = b for a nonsymmetric A by right-preconditioned BiCGSTAB on the device (cvr_bicgstab_device): the arguments and the

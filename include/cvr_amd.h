@@ -440,6 +440,37 @@ int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_op
  * opt->minv_dev stays a device pointer. */
 int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* Conjugate gradients for several right-hand sides at once: A X = B for 1 <= nvec <= 8 columns, one cvr_spmm_device pass over the image per
+ * step for all of them, four launches per step instead of four per column, one read-back for the block.  (16 columns: two calls.)
+ * B_dev and X_dev: row-major blocks of exactly nrows rows of ldb / ldx values of the handle's type (row i holds b_0[i] .. b_{nvec-1}[i]), as
+ * cvr_spmm_device's, but without a pad row or a scratch tail; values at positions >= nvec of a row are neither read nor written; any alignment
+ * of the element type.  X_dev is the start block on entry and the solution block on exit.  opt->minv_dev is one preconditioner of nrows values,
+ * shared by all columns; rtol, max_iters and check_every hold for every column.  res: nvec results.
+ * The contract, for every column j: column j of X and res[j].iterations, .status, .residual_norm and .b_norm are bit for bit what cvr_cg_device
+ * on the same handle returns for b = B[:, j] and x0 = X[:, j] with the same options -- for every check_every, ldb, ldx and alignment.  The
+ * arithmetic is cvr_cg_device's per column (the initial residual is r = T(b - q) with Q = A X0 from the k-wide product, which is what the scaled
+ * product with alpha = -1, beta = 1 stores); in the sums the thread that owns a 16-byte packet of rows of a single vector owns those rows of
+ * every column and adds each column's terms in the same order, and every (sum, column) has its own 1024 partials in the same tree.
+ * res[j].spmv_count is the number of k-wide products the call enqueued, the initial one included, and res[j].seconds the time of the whole
+ * call: both are the same in every res[j].
+ * Columns are independent: each has its own state cell and stops on its own -- converged, breakdown (p.q <= 0 or not finite; a NaN or an Inf
+ * in its b: at step 0 with x untouched), or b == 0 (x = 0).  From then on no kernel writes its slices of X or of the library's blocks; the
+ * other columns go on (the product keeps computing all nvec columns; a stopped column's q is written and ignored).  The host loop ends when
+ * every column has stopped or at max_iters.
+ * Handles: nvec >= 2, or any leading dimension other than 1, needs cvr_spmm_supported(h) (a handle created with cvr_options.nvec >= 2), else
+ * CVR_ERR_STATE; nvec = 1 with ldb = ldx = 1 runs on every single-GPU handle through cvr_spmv_device's launch path.  A mutable handle's image
+ * is ordered with its updates as cvr_spmm_device orders it.  Ordering otherwise as cvr_cg_device: `stream` is synchronised at every read-back
+ * and before the call returns; not capturable in a HIP graph.  The library's blocks (P of ncols + 1 rows with a zero last row, Q and R of
+ * info.yext_elems rows, Z with minv_dev; nvec values per row) are allocated per call.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; nvec outside 1..8,
+ * ldb < nvec or ldx < nvec: CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols: CVR_ERR_INVALID; a handle that
+ * does not take the block (above): CVR_ERR_STATE; (ncols + 1) * nvec values beyond 4 GiB: CVR_ERR_INVALID. */
+int cvr_cg_multi_device(cvr_handle *h, const void *B_dev, int64_t ldb, void *X_dev, int64_t ldx, int32_t nvec, const cvr_cg_options *opt,
+                        cvr_cg_result *res, void *stream);
+/* the same with host B and X (nrows x nvec each, row-major, ld = nvec; X in and out): copied up, cvr_cg_multi_device on the handle's stream,
+ * X copied back.  opt->minv_dev stays a device pointer. */
+int cvr_cg_multi(cvr_handle *h, const void *B_host, void *X_host, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* BiCGSTAB for a nonsymmetric A (needs no A^T): right-preconditioned, shadow residual r^ = r0, two SpMVs per step.  b_dev, x_dev, the options, the
  * result, the ordering and the errors are cvr_cg_device's; the buffers of the call are the library's, allocated per call: p, s (and with minv_dev
  * p^, s^) of info.x_elems values whose element ncols stays 0, v, t and r of info.yext_elems values, r^ of nrows values.
