@@ -99,7 +99,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
-           "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
+           "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
            "cvr_tune_steps", "cvr_tune", "cvr_auto_panels", "cvr_power_iteration", "cvr_comm_unique_id", "cvr_comm_create", "cvr_comm_destroy", "cvr_comm_all_gather", "cvr_spmv_gather_repeat",
            "cvr_source_key_of", "cvr_mm_write_bin_keyed", "cvr_mm_read_bin_keyed", "cvr_mm_read_cached", "cvr_save_image", "cvr_load_image",
@@ -165,6 +165,7 @@ def lib():
         L.cvr_device_copy_bench.argtypes = [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double)]
         L.cvr_plan_selfcheck.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_plan_selfcheck.restype = C.c_int
+        L.cvr_power_step_selfcheck.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_plan_bound.argtypes = [C.c_int64, C.c_int64, C.c_int32]
         L.cvr_plan_bound.restype = C.c_int64
         L.cvr_plan_chunks.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 4
@@ -339,6 +340,19 @@ def plan_selfcheck(row_ptr, S, thr=0, max_rows=0, device=0):
     if rc:
         raise CvrError(rc, "cvr_plan_selfcheck")
     return dict(host_s=hs.value, device_s=ds.value, nchunks=n.value)
+
+
+def power_step_selfcheck(n, is_f32, x_ptr, y_ptr, partial_ptr, prev_ptr=None, bounds=None, max_rows=0, dense_ptr=None, stream=None, device=0):
+    """one power-iteration step's vector work on the caller's device arrays (cvr_power_step_selfcheck): x_ptr is updated in place, partial_ptr
+    (3 * 1024 doubles) receives the step's partial sums; bounds (nparts + 1 row offsets): y_ptr is the padded all-gather layout of nparts * max_rows
+    values and dense_ptr, if given, receives y in row order.  Returns the sums (x.y, y.y, x.x) as three float64."""
+    b = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.int64)
+    sums = np.zeros(3, dtype=np.float64)
+    rc = lib().cvr_power_step_selfcheck(device, n, int(is_f32), x_ptr, y_ptr, prev_ptr, partial_ptr, None if b is None else b.ctypes.data,
+                                        0 if b is None else len(b) - 1, max_rows, dense_ptr, sums.ctypes.data, stream)
+    if rc:
+        raise CvrError(rc, "cvr_power_step_selfcheck")
+    return sums
 
 
 def auto_panels(nrows, ncols, row_ptr, col_idx, is_f32=False):

@@ -166,6 +166,27 @@ int cvr_spmv_gather_repeat(cvr_handle *h, cvr_comm *c, const void *x_dev, void *
     return CVR_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// the shards of the iterative caller: 1 .. kIterMaxParts row blocks whose bounds run from 0 to n and never decrease; fills bd and the longest block
+// (the one check of cvr_power_iteration and cvr_power_step_selfcheck)
+int iter_shards(const int64_t *bounds, int nparts, int64_t n, cvr::IterBounds &bd, int64_t &widest)
+{
+    if (nparts < 1 || nparts > cvr::kIterMaxParts) return fail(CVR_ERR_INVALID, "%d shards: 1 .. %d", nparts, cvr::kIterMaxParts);
+    if (bounds[0] != 0 || bounds[nparts] != n) return fail(CVR_ERR_INVALID, "bounds must run from 0 to ncols = %lld (square matrix)", (long long)n);
+    widest = 0;
+    for (int p = 0; p < nparts; p++) {
+        if (bounds[p + 1] < bounds[p]) return fail(CVR_ERR_INVALID, "bounds decrease");
+        widest = std::max(widest, bounds[p + 1] - bounds[p]);
+    }
+    for (int p = 0; p <= nparts; p++) bd.b[p] = bounds[p];
+    return CVR_OK;
+}
+}  // namespace
+
+extern "C" {
+
 // ---- the iterative caller: power iteration x <- A x / ||A x||, everything on the device ------------------------------
 int cvr_power_iteration(cvr_handle *h, cvr_comm *c, const int64_t *bounds, int iters, void *x_dev, double *lambda,
                         double *seconds_per_iter, void *stream)
@@ -176,17 +197,11 @@ int cvr_power_iteration(cvr_handle *h, cvr_comm *c, const int64_t *bounds, int i
     const int     nparts = c ? c->nranks : 1;
     const int64_t n = h->info.ncols;                    // the whole (square) matrix has n rows and n columns
     if (c && !bounds) return fail(CVR_ERR_INVALID, "a communicator needs the row bounds of the shards");
-    if (nparts > cvr::kIterMaxParts) return fail(CVR_ERR_INVALID, "more than %d shards", cvr::kIterMaxParts);
     cvr::IterBounds bd;
     int64_t         max_rows = 0;
     if (c) {
+        if (const int rc = iter_shards(bounds, nparts, n, bd, max_rows)) return rc;
         if (c->device != h->device) return fail(CVR_ERR_INVALID, "communicator on device %d, matrix on device %d", c->device, h->device);
-        if (bounds[0] != 0 || bounds[nparts] != n) return fail(CVR_ERR_INVALID, "bounds must run from 0 to ncols = %lld (square matrix)", (long long)n);
-        for (int p = 0; p < nparts; p++) {
-            if (bounds[p + 1] < bounds[p]) return fail(CVR_ERR_INVALID, "bounds decrease");
-            max_rows = std::max(max_rows, bounds[p + 1] - bounds[p]);
-        }
-        for (int p = 0; p <= nparts; p++) bd.b[p] = bounds[p];
         if (bounds[c->rank + 1] - bounds[c->rank] != h->info.nrows) return fail(CVR_ERR_INVALID, "this rank's bounds do not match its %lld rows", (long long)h->info.nrows);
     } else if (h->info.nrows != n) {
         return fail(CVR_ERR_INVALID, "power iteration needs a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)n);
@@ -318,6 +333,30 @@ int cvr_power_iteration(cvr_handle *h, cvr_comm *c, const int64_t *bounds, int i
     HIP_TRY(hipEventElapsedTime(&ms, s.e0, s.e1));
     if (lambda) *lambda = iters > 0 && cells[2] > 0 ? cells[0] / cells[2] : 0.0;      // Rayleigh quotient of the last step's x
     if (seconds_per_iter) *seconds_per_iter = iters > 0 ? (double)ms * 1e-3 / iters : 0.0;
+    return CVR_OK;
+}
+
+// ---- diagnostics: one step's vector work of the loop above on the caller's arrays, the sharded (padded) form without a communicator ----
+int cvr_power_step_selfcheck(int device, int64_t n, int is_f32, void *x_dev, const void *y_dev, const double *prev_dev, double *partial_dev,
+                             const int64_t *bounds, int nparts, int64_t max_rows, void *dense_dev, double *sums, void *stream)
+{
+    if (n < 0 || !x_dev || !y_dev || !partial_dev || !sums) return fail(CVR_ERR_INVALID, "null argument");
+    cvr::IterBounds bd{};
+    if (bounds) {
+        int64_t widest = 0;
+        if (const int rc = iter_shards(bounds, nparts, n, bd, widest)) return rc;
+        if (widest > max_rows) return fail(CVR_ERR_INVALID, "max_rows %lld < the %lld rows of the longest shard", (long long)max_rows, (long long)widest);      // (the loop takes max_rows = widest itself)
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const bool        f32 = is_f32 != 0;
+    HIP_TRY(hipSetDevice(device));
+    struct Cells { double *p = nullptr; ~Cells() { (void)hipFree(p); } } cells;
+    HIP_TRY(hipMalloc(&cells.p, sizeof(double) * 3));
+    if (bounds && dense_dev) HIP_TRY(cvr::launch_unpad(dense_dev, y_dev, bd, nparts, max_rows, f32, st));
+    HIP_TRY(cvr::launch_power_step(x_dev, y_dev, n, f32, prev_dev, partial_dev, st, bounds ? &bd : nullptr, nparts, max_rows));
+    HIP_TRY(cvr::launch_power_sums(partial_dev, cells.p, st));
+    HIP_TRY(hipMemcpyAsync(sums, cells.p, sizeof(double) * 3, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return CVR_OK;
 }
 

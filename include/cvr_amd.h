@@ -373,7 +373,35 @@ int cvr_spmv_gather_repeat(cvr_handle *h, cvr_comm *comm, const void *x_dev, voi
  * it -- the one setting where the exchange step is on the critical path.  On one GPU with an image of the resident layout (column
  * phases, no row cut over chunks) the step's dot products and the next iterate come out of the SpMV kernel's write-out: one launch per
  * iteration (web-Google shape: 26 us per iteration, SpMV alone 21).  Synchronises `stream` before returning.
- * (The reference has no such loop: its Ntimes loop, spmv.cpp:1024, recomputes one y.) */
+ * (The reference has no such loop: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+ *
+ * Arithmetic, T = the handle's type, n = ncols, every operation rounded on its own (no fused multiply-add).  A sum's terms are
+ * double(a_i) * double(b_i), each rounded once, added in fp64 in one of the trees below.  inv(s) = 1 / sqrt(s) in fp64 (a correctly
+ * rounded square root, then a correctly rounded quotient) where s > 0, and 0 where s is not > 0 (0, negative, NaN).
+ *   Start:   x <- T(double(x) * inv(x.x)), the sum by the dense tree.  An all-zero x stays 0 (and every later x, and lambda).
+ *   Step k = 0 .. iters-1:  y = A x through cvr_spmv_device's launch path (bit for bit its y for the same x); the three sums x.y, y.y, x.x
+ *            of this x and y; then x <- T(double(y) * inv_k) with inv_0 = 1 and inv_k = inv(y.y of step k-1).
+ *   Last step (k = iters-1), instead:  x <- T(double(y) * inv(y.y of this step)).
+ *   *lambda = x.y / x.x of the last step; 0 for iters == 0 or an x.x that is not > 0.
+ *   fp32 handles with iters > 1, after the sums of step 0:  est = sqrt(y.y / x.x) (0 where x.x is not > 0) is read back once.  Unless
+ *            1e-15 < est < 1e15 (both strict), the exact mode is entered: x <- T(double(y) * inv(y.y of step 0)) now, and every later step
+ *            is y = A x, x.y, x.x, y.y, x <- T(double(y) * inv(y.y of this step)), each sum by the dense tree (three times per step).
+ *            fp64 handles and iters <= 1 never enter it.
+ *   Dense tree (the start, the exact mode, the sharded loop, and the one-GPU loop where the fused tree below does not apply): thread
+ *            g = 256 * workgroup + thread of a 1024 x 256 grid adds the terms g, g + 262 144, ... in order, starting from +0; the 64 lanes
+ *            of a wavefront combine by the xor butterfly a += a[lane ^ o], o = 32, 16, 8, 4, 2, 1; thread 0 adds the workgroup's four
+ *            wavefronts in order, from +0: 1024 partials.  Of those, lane t of one wavefront adds t, t + 64, ..., t + 960 in order from +0,
+ *            and the lanes combine by the same butterfly.
+ *   Fused tree (comm == NULL, column phases > 1, not interleaved, no row cut over chunks (info.nshared == 0), no hub table, no column
+ *            panels, at most 1024 workgroups = ceil(nchunks / waves_per_block), and CVR_DEBUG=iter_unfused not set): the sums of every
+ *            step that is not in the exact mode.  A chunk holds consecutive rows (cvr_export_image: desc[k][0] is its first; every row,
+ *            empty ones included, belongs to exactly one chunk).  Lane l of the chunk's wavefront adds the terms of the chunk's rows
+ *            l, l + 64, ... in order from +0; the lanes combine by the butterfly; a workgroup adds its wavefronts that have a chunk
+ *            (chunks blk * waves_per_block ...) in chunk order, from +0, into cell blk of 1024 cells, the other cells being +0; the
+ *            sum over the 1024 cells is the dense tree's last stage.  x itself is the same T(double(y) * inv_k).
+ *   The sharded loop reads y as all-gathered, shard p's rows at y[p * max_rows ...] with max_rows the longest shard (row i belongs to the
+ *            LAST p with bounds[p] <= i: empty shards own nothing), in the element order of the dense tree: the same bits as one GPU's
+ *            dense loop over the same y.  At most 64 shards (CVR_ERR_INVALID beyond). */
 int cvr_power_iteration(cvr_handle *h, cvr_comm *comm, const int64_t *bounds, int iters, void *x_dev, double *lambda,
                         double *seconds_per_iter, void *stream);
 
@@ -541,6 +569,15 @@ int64_t cvr_plan_chunks(int64_t nrows, const int64_t *row_ptr, int32_t S, int64_
  * compares the two plans field by field (CVR_OK = identical); seconds of both, chunk count. */
 int cvr_plan_selfcheck(int device, int64_t nrows, const int64_t *row_ptr, int32_t S, int64_t split_threshold, int64_t max_rows,
                        double *host_seconds, double *device_seconds, int64_t *nchunks);
+/* diagnostics (needs a device): the vector work of one cvr_power_iteration step on the caller's device arrays, so that the sharded form can be
+ * checked on one GPU without a communicator.  x_dev: n values of T (float if is_f32, else double), in: x, out: T(double(y) * inv) with inv = 1 for
+ * prev_dev == NULL, else inv(y.y) of the partial sums a call before left in its partial_dev.  partial_dev: 3 * 1024 doubles, out: this step's partial
+ * sums (x.y, y.y, x.x; dense tree), sums[3] (host): their totals.  bounds == NULL: y_dev holds n values (the dense step).  bounds[nparts + 1]
+ * (host; 0 .. n, not decreasing, 1 <= nparts <= 64, every shard <= max_rows): y_dev holds nparts * max_rows values, shard p's rows at
+ * y_dev[p * max_rows ...] (the padded step), and dense_dev, where not NULL, receives the n rows in row order (the un-padding pass of the last
+ * step).  Synchronises `stream`. */
+int cvr_power_step_selfcheck(int device, int64_t n, int is_f32, void *x_dev, const void *y_dev, const double *prev_dev, double *partial_dev,
+                             const int64_t *bounds, int nparts, int64_t max_rows, void *dense_dev, double *sums, void *stream);
 
 /* ---- host side of the reference program ------------------------------------------------------ */
 #define CVR_MM_REFCOMPAT 0   /* the reference loader's arrays bit for bit (quirks Q1-Q9)           */

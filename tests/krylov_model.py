@@ -43,23 +43,27 @@ def _f64(a):
     return np.asarray(a).astype(np.float64)
 
 
-def _lanes_then_waves(a):
-    """a: (..., WAVES, LANES) -> (...): the butterfly a += a[lane ^ o] for o = 32 .. 1 (every lane ends with the same bits, fp addition being
-    commutative: lane l < o adds lane l + o), then the wavefronts in order from +0"""
+def butterfly(a):
+    """a: (..., LANES) -> (...): a += a[lane ^ o] for o = 32 .. 1 (every lane ends with the same bits, fp addition being commutative: lane l < o adds
+    lane l + o)"""
     for o in (32, 16, 8, 4, 2, 1):
         a = a[..., :o] + a[..., o:2 * o]
-    a = a[..., 0]
+    return a[..., 0]
+
+
+def _lanes_then_waves(a):
+    """a: (..., WAVES, LANES) -> (...): the butterfly in every wavefront, then the wavefronts in order from +0"""
+    a = butterfly(a)
     s = np.zeros(a.shape[:-1])
     for w in range(WAVES):
         s = s + a[..., w]
     return s
 
 
-def tree_sum(terms, pack):
-    """the documented tree over fp64 terms, bit for bit: thread g = workgroup * 256 + thread of a 1024 x 256 grid adds its packets g, g + 262 144, ...
-    in order, each packet's `pack` values in order, from +0; lanes by butterfly, the four wavefronts in order from +0; of the 1024 partials thread t
-    adds t, t + 256, t + 512, t + 768 in order from +0, then the same butterfly and wavefronts.  (A value that does not exist adds nothing; +0 added
-    to a sum that started from +0 changes no bit, so the missing values are padded with +0.)"""
+def tree_partials(terms, pack):
+    """the 1024 workgroup partials of the documented tree over fp64 terms, bit for bit: thread g = workgroup * 256 + thread of a 1024 x 256 grid adds
+    its packets g, g + 262 144, ... in order, each packet's `pack` values in order, from +0; lanes by butterfly, the four wavefronts in order from +0.
+    (A value that does not exist adds nothing; +0 added to a sum that started from +0 changes no bit, so the missing values are padded with +0.)"""
     t = np.ascontiguousarray(terms, dtype=np.float64).reshape(-1)
     n = t.size
     trips = trips_of(n, pack)
@@ -74,6 +78,14 @@ def tree_sum(terms, pack):
                 acc = acc + buf[trip, :, j]
         part = np.zeros(BLOCKS)
         part[: threads // THREADS] = _lanes_then_waves(acc.reshape(-1, WAVES, LANES))
+    return part
+
+
+def tree_sum(terms, pack):
+    """the documented tree over fp64 terms, bit for bit: the partials of `tree_partials`; of those thread t adds t, t + 256, t + 512, t + 768 in order
+    from +0, then the same butterfly and wavefronts"""
+    part = tree_partials(terms, pack)
+    with np.errstate(all="ignore"):
         a = np.zeros(THREADS)
         for j in range(BLOCKS // THREADS):
             a = a + part[j * THREADS:(j + 1) * THREADS]
