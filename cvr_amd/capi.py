@@ -97,7 +97,7 @@ class MmMatrix(C.Structure):
 # every symbol include/cvr_amd.h declares (tests check the library exports all of them)
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
-           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab",
+           "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -152,6 +152,8 @@ def lib():
         L.cvr_cg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_bicgstab_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_bicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_gmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_gmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -693,6 +695,42 @@ class CvrMatrix:
         rc = lib().cvr_bicgstab(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
         if rc:
             raise CvrError(rc, "cvr_bicgstab")
+        return x[: self.nrows], res
+
+    def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
+        """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device
+        arrays (anything with data_ptr() and new_zeros()) of nrows values of the handle's type: x0 is the start vector and is overwritten with the
+        solution (None: a new zero array), minv the optional right preconditioner.  options: rtol, max_iters (None: the library's defaults),
+        check_every.  Returns (x, CgResult); synchronises the stream."""
+        rtol, max_iters, check_every = options.pop("rtol", None), options.pop("max_iters", None), options.pop("check_every", 0)
+        if options:
+            raise TypeError(f"gmres: unknown options {sorted(options)}")
+        x = b.new_zeros(max(self.nrows, 1)) if x0 is None else x0
+        opt, res = self._cg_options(rtol, max_iters, check_every, None if minv is None else minv.data_ptr()), CgResult()
+        rc = lib().cvr_gmres_device(self._h, b.data_ptr(), x.data_ptr(), int(restart), C.byref(opt), C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_gmres_device")
+        return (x[: self.nrows] if x0 is None else x), res
+
+    def gmres_host(self, b, x0=None, restart=30, minv=None, **options):
+        """the same through host arrays (cvr_gmres): b and the start vector x0 (None: zero) of nrows values; minv stays a device array.
+        Returns (x, CgResult)."""
+        rtol, max_iters, check_every = options.pop("rtol", None), options.pop("max_iters", None), options.pop("check_every", 0)
+        if options:
+            raise TypeError(f"gmres_host: unknown options {sorted(options)}")
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        if len(b) < self.nrows:
+            raise ValueError("b is shorter than nrows")
+        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=self.dtype)
+            if len(x0) < self.nrows:
+                raise ValueError("x0 is shorter than nrows")
+            x[: self.nrows] = x0[: self.nrows]
+        opt, res = self._cg_options(rtol, max_iters, check_every, None if minv is None else minv.data_ptr()), CgResult()
+        rc = lib().cvr_gmres(self._h, b.ctypes.data, x.ctypes.data, int(restart), C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_gmres")
         return x[: self.nrows], res
 
     def spmm(self, X, iters=1):

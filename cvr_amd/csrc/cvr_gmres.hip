@@ -1,0 +1,596 @@
+// cvr_gmres.hip -- restarted GMRES(m) on the device for any nonsingular A (include/cvr_amd.h: cvr_gmres_device, cvr_gmres): cvr_bicgstab.hip's plan with
+// an Arnoldi basis.  Right-preconditioned; per step one SpMV through run_spmv (cvr_spmv_device's path) and five vector launches, whatever the column j:
+//   w = A z_j                  (z_j = minv .* v_j, written with v_j; v_j itself without a preconditioner)
+//   gmres_dots_kernel          the partial sums of v_i . w for i = 0..j, the columns in compile-time groups of up to 8 with w's packet loaded once per group
+//   gmres_update_kernel        h_i from those partials (summed in every workgroup, the same order everywhere); w -= sum h_i v_i in one pass over the basis
+//   gmres_dots_kernel          the same on the new w (classical Gram-Schmidt, applied twice)
+//   gmres_update_kernel        d_i, w -= sum d_i v_i and the partial sums of w . w; workgroup 0: H_i = h_i + d_i and the earlier rotations on the column
+//   gmres_finish_kernel        H_(j+1) = sqrt(w . w), the new rotation, the stop test into the state cell; v_(j+1) = w / H_(j+1) (and z_(j+1))
+// so a step reads the basis four times and w seven times over (w once per group of 8 columns in the dots), in 16-byte packets.  x is formed once per
+// cycle (gmres_x_kernel: the small triangular solve is one thread's work in the kernel that finds the need), behind which the next cycle starts from the true
+// residual (the scaled product, gmres_rr_kernel, gmres_begin_kernel).  The sums, the grid and the packet helpers are cvr_krylov.h's; every sum has its
+// own 1024 partials, so its bits do not depend on the group it was formed in.  The scalars sit in a state cell (GmresCell) under BiCell's rule: thread 0
+// of workgroup 0 writes it, and a value a kernel reads is one that a kernel BEFORE it wrote.  The kernel that finds a stop records it and every later
+// kernel of the batch returns without writing, so the result does not depend on how many steps the host enqueues between two read-backs.
+// (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+#include "cvr_krylov.h"
+
+using namespace cvrh;
+using namespace cvrh::krylov;
+
+namespace {
+
+constexpr double kDblMax = 1.7976931348623157e308;
+constexpr int    kMaxM = CVR_GMRES_MAX_RESTART;
+constexpr int    kGroup = 8;          // columns per compile-time group: 16 accumulator VGPRs in fp64, and the group's packets in flight together
+
+// what the host reads back
+struct GmresHead {
+    double  bb, bnorm;         // b . b and its root
+    double  rnorm;             // residual_norm: the true ||r|| at a cycle's start, the estimate |g_(j+1)| behind a step, |g_j| at a breakdown
+    double  hrot;              // H_j of the step under way behind the earlier rotations (the second gmres_update_kernel writes it, gmres_finish_kernel reads it)
+    int32_t stop;              // != 0: no kernel writes a vector any more (gmres_x_kernel apart: see owed)
+    int32_t status;            // CVR_CG_*
+    int32_t iters;             // steps counted
+    int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
+    int32_t owed;              // columns of the current cycle that x is still owed (y holds their coefficients); 0: none
+    int32_t owed_at;           // k + 1 of the step k whose gmres_finish_kernel set `owed`: a gmres_x_kernel acts when its range of steps (lo, hi] holds it, so
+                               // nobody has to clear `owed` in the kernel that reads it
+};
+
+// The state cell.  g[i] is final (behind rotation i), gbar[i] the running value in front of it: rotation j reads gbar[j] and writes g[j] and gbar[j + 1], never
+// what another workgroup of the same kernel may be reading.  R is column-major: R_(i,l) at R[l * kMaxM + i].
+struct GmresCell {
+    GmresHead hd;
+    double    g[kMaxM], gbar[kMaxM + 1], cs[kMaxM], sn[kMaxM];
+    double    h[kMaxM];          // pass 1's h_i of the step under way
+    double    y[kMaxM];
+    double    R[kMaxM * kMaxM];
+};
+
+__device__ __forceinline__ bool usable(double v) { return v != 0 && fabs(v) <= kDblMax; }          // neither zero nor Inf nor NaN
+
+// hs[s] = the sum of the s-th set of kBlocks partials for s < nsets, in LDS: sum_partials' tree set by set (the same bits as sum_partials<1> of that set), the
+// same in every workgroup.  Ends behind a barrier.
+__device__ __forceinline__ void sum_sets(const double *__restrict__ part, int nsets, double *__restrict__ hs, double (*__restrict__ sh)[kWaves])
+{
+    for (int s = 0; s < nsets; s++) {
+        double a = 0;
+#pragma unroll
+        for (int j = 0; j < kBlocks / kThreads; j++) a += part[(size_t)s * kBlocks + threadIdx.x + j * kThreads];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        if ((threadIdx.x & 63u) == 0) sh[s][threadIdx.x >> 6] = a;
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < nsets; s += kThreads) {
+        double a = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; w++) a += sh[s][w];
+        hs[s] = a;
+    }
+    __syncthreads();
+}
+
+// the partial sums of V_c . w for the C columns at V (one pass over w and over each of them)
+template <typename T, int C>
+__device__ __forceinline__ void dot_group(const T *__restrict__ V, long long stride, const T *__restrict__ w, long long n, double *__restrict__ out,
+                                          double (&sh)[kGroup][kWaves])
+{
+    double acc[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) acc[c] = 0;
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T wv[kPack<T>], vv[C][kPack<T>];
+        load_pack<T, true>(w, e, (int)cnt, wv);
+#pragma unroll
+        for (int c = 0; c < C; c++) load_pack<T, true>(V + c * stride, e, (int)cnt, vv[c]);
+#pragma unroll
+        for (int c = 0; c < C; c++)
+#pragma unroll
+            for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[c] += (double)vv[c][j] * (double)wv[j];
+    }
+    store_partials<C>(acc, out, reinterpret_cast<double (&)[C][kWaves]>(sh));
+}
+
+// set i of `out` = the partial sums of v_i . w for i < ncols, v_i at V + i * stride
+template <typename T>
+__global__ __launch_bounds__(kThreads) void gmres_dots_kernel(const T *__restrict__ V, long long stride, const T *__restrict__ w, long long n, int ncols,
+                                                              double *__restrict__ out, const GmresCell *__restrict__ cell)
+{
+    __shared__ double sh[kGroup][kWaves];
+    if (cell->hd.stop) return;          // (no workgroup of this kernel sets it)
+    int c0 = 0;
+    for (; c0 + kGroup <= ncols; c0 += kGroup) {
+        dot_group<T, kGroup>(V + c0 * stride, stride, w, n, out + (size_t)c0 * kBlocks, sh);
+        __syncthreads();          // thread 0 has read sh before the next group writes it
+    }
+    const T *Vr = V + c0 * stride;
+    double  *outr = out + (size_t)c0 * kBlocks;
+    switch (ncols - c0) {
+    case 1: dot_group<T, 1>(Vr, stride, w, n, outr, sh); break;
+    case 2: dot_group<T, 2>(Vr, stride, w, n, outr, sh); break;
+    case 3: dot_group<T, 3>(Vr, stride, w, n, outr, sh); break;
+    case 4: dot_group<T, 4>(Vr, stride, w, n, outr, sh); break;
+    case 5: dot_group<T, 5>(Vr, stride, w, n, outr, sh); break;
+    case 6: dot_group<T, 6>(Vr, stride, w, n, outr, sh); break;
+    case 7: dot_group<T, 7>(Vr, stride, w, n, outr, sh); break;
+    default: break;
+    }
+}
+
+// t = t - hs[c] * double(V_c) for c = 0 .. C - 1 in that order, the C packets loaded together
+template <typename T, int C>
+__device__ __forceinline__ void sub_group(const T *__restrict__ V, long long stride, long long e, int cnt, const double *__restrict__ hs, double (&t)[kPack<T>])
+{
+    T vv[C][kPack<T>];
+#pragma unroll
+    for (int c = 0; c < C; c++) load_pack<T, true>(V + c * stride, e, cnt, vv[c]);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const double hc = hs[c];
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) t[j] = t[j] - hc * (double)vv[c][j];
+    }
+}
+
+// u = u + ys[c] * double(V_c), the same way
+template <typename T, int C>
+__device__ __forceinline__ void add_group(const T *__restrict__ V, long long stride, long long e, int cnt, const double *__restrict__ ys, double (&u)[kPack<T>])
+{
+    T vv[C][kPack<T>];
+#pragma unroll
+    for (int c = 0; c < C; c++) load_pack<T, true>(V + c * stride, e, cnt, vv[c]);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        const double yc = ys[c];
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) u[j] = u[j] + yc * (double)vv[c][j];
+    }
+}
+
+#define CVR_GMRES_GROUPS(fn, ncols, coef, acc)                                                              \
+    do {                                                                                                    \
+        int c0_ = 0;                                                                                        \
+        for (; c0_ + kGroup <= (ncols); c0_ += kGroup) fn<T, kGroup>(V + c0_ * stride, stride, e, (int)cnt, (coef) + c0_, acc); \
+        const T *Vr_ = V + c0_ * stride;                                                                    \
+        switch ((ncols) - c0_) {                                                                            \
+        case 1: fn<T, 1>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 2: fn<T, 2>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 3: fn<T, 3>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 4: fn<T, 4>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 5: fn<T, 5>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 6: fn<T, 6>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        case 7: fn<T, 7>(Vr_, stride, e, (int)cnt, (coef) + c0_, acc); break;                               \
+        default: break;                                                                                     \
+        }                                                                                                   \
+    } while (0)
+
+// Step with column j, one Gram-Schmidt pass: the coefficients c_i = v_i . w (i = 0..j) from the partials of the dots in front; per value
+// t = double(w), t = t - c_0 double(v_0), ..., t = t - c_j double(v_j), w = T(t).  Workgroup 0 keeps the coefficients: pass 1 (!SECOND) stores h_i; pass 2
+// forms H_i = h_i + d_i, applies the rotations 0 .. j - 1 to the column, stores R_(i,j) for i < j and the rotated H_j (hrot) -- and every workgroup adds the
+// partial sums of w . w of the new w.
+template <typename T, bool SECOND>
+__global__ __launch_bounds__(kThreads) void gmres_update_kernel(const T *__restrict__ V, long long stride, T *__restrict__ w, long long n, int j,
+                                                                const double *__restrict__ part, double *__restrict__ out_ww, GmresCell *__restrict__ cell)
+{
+    __shared__ double shs[kMaxM][kWaves];
+    __shared__ double hs[kMaxM];
+    __shared__ double shw[1][kWaves];
+    __shared__ int    stopped;
+    if (threadIdx.x == 0) stopped = cell->hd.stop;
+    sum_sets(part, j + 1, hs, shs);
+    if (stopped) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if constexpr (!SECOND) {
+            for (int i = 0; i <= j; i++) cell->h[i] = hs[i];
+        } else {
+            double cur = cell->h[0] + hs[0];          // H_i in front of rotation i
+            for (int i = 0; i < j; i++) {
+                const double nxt = cell->h[i + 1] + hs[i + 1], cs = cell->cs[i], sn = cell->sn[i];
+                const double t = cs * cur + sn * nxt;
+                const double u = cs * nxt - sn * cur;
+                cell->R[j * kMaxM + i] = t;
+                cur = u;
+            }
+            cell->hd.hrot = cur;
+        }
+    }
+    double acc[1] = {0};
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T      wv[kPack<T>];
+        double t[kPack<T>];
+        load_pack<T, true>(w, e, (int)cnt, wv);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) t[l] = (double)wv[l];
+        CVR_GMRES_GROUPS(sub_group, j + 1, hs, t);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) {
+            wv[l] = (T)t[l];
+            if constexpr (SECOND) if (l < cnt) acc[0] += (double)wv[l] * (double)wv[l];
+        }
+        store_pack<T, true>(w, e, (int)cnt, wv);
+    }
+    if constexpr (SECOND) store_partials<1>(acc, out_ww, shw);
+}
+
+// y of the q columns of the cycle by back substitution, descending, each row's terms ascending (one thread)
+__device__ void solve_y(GmresCell *__restrict__ cell, int q)
+{
+    for (int i = q - 1; i >= 0; i--) {
+        double t = cell->g[i];
+        for (int l = i + 1; l < q; l++) t = t - cell->R[l * kMaxM + i] * cell->y[l];
+        cell->y[i] = t / cell->R[i * kMaxM + i];
+    }
+}
+
+// Step k with column j, behind the second pass: H_(j+1) = sqrt(w . w), rho, the rotation and the stop test (the same decision in every workgroup, from the
+// same sums; workgroup 0 records it); a cycle that goes on gets v_(j+1) = T(double(w) / H_(j+1)) and, with a preconditioner, z_(j+1).  AL: minv is aligned.
+template <typename T, bool PRE, bool AL>
+__global__ __launch_bounds__(kThreads) void gmres_finish_kernel(const T *__restrict__ w, const T *__restrict__ minv, T *__restrict__ vnext, T *__restrict__ z,
+                                                                long long n, const double *__restrict__ part_ww, GmresCell *__restrict__ cell, int j, int k, int m,
+                                                                int max_iters, double rtol)
+{
+    __shared__ double sh[1][kWaves];
+    __shared__ int    stopped;
+    if (threadIdx.x == 0) stopped = cell->hd.stop;
+    double s[1];
+    sum_partials<1>(part_ww, s, sh);
+    if (stopped) return;
+    const bool   first = blockIdx.x == 0 && threadIdx.x == 0;
+    const double hn = sqrt(s[0]), hj = cell->hd.hrot, gj = cell->gbar[j];
+    const double rho = sqrt(hj * hj + hn * hn);
+    if (!usable(rho)) {          // found before the step is counted: x from the j columns before it
+        if (first) {
+            cell->hd.rnorm = fabs(gj);
+            cell->hd.status = CVR_CG_BREAKDOWN;
+            solve_y(cell, j);
+            cell->hd.owed = j; cell->hd.owed_at = k + 1;
+            cell->hd.stop = 1;
+        }
+        return;
+    }
+    const double cs = hj / rho, sn = hn / rho;
+    const double gn = -(sn * gj), est = fabs(gn);
+    const bool   done = est <= rtol * cell->hd.bnorm && est <= kDblMax;
+    const bool   last = k + 1 == max_iters, full = j + 1 == m;
+    if (first) {
+        cell->cs[j] = cs; cell->sn[j] = sn;
+        cell->R[j * kMaxM + j] = rho;
+        cell->g[j] = cs * gj; cell->gbar[j + 1] = gn;
+        cell->hd.iters = k + 1; cell->hd.rnorm = est;
+        if (done || last || full) {
+            solve_y(cell, j + 1);
+            cell->hd.owed = j + 1; cell->hd.owed_at = k + 1;
+        }
+        if (done) { cell->hd.status = CVR_CG_CONVERGED; cell->hd.stop = 1; }
+    }
+    if (done || last || full) return;
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T wv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
+        load_pack<T, true>(w, e, (int)cnt, wv);
+        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) {
+            wv[l] = (T)((double)wv[l] / hn);
+            if constexpr (PRE) zv[l] = (T)((double)mv[l] * (double)wv[l]);
+        }
+        store_pack<T, true>(vnext, e, (int)cnt, wv);
+        if constexpr (PRE) store_pack<T, true>(z, e, (int)cnt, zv);
+    }
+}
+
+// A cycle's start: r holds b - A x (the scaled product).  The partial sums of r . r (set 0) and, at the call's start (FIRST), of b . b (set 1).
+// AL: b, the caller's array, is 16-byte aligned.
+template <typename T, bool FIRST, bool AL>
+__global__ __launch_bounds__(kThreads) void gmres_rr_kernel(const T *__restrict__ r, const T *__restrict__ b, long long n, double *__restrict__ out,
+                                                            const GmresCell *__restrict__ cell)
+{
+    __shared__ double sh[2][kWaves];
+    if constexpr (!FIRST) if (cell->hd.stop) return;
+    double acc[2] = {0, 0};
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T rv[kPack<T>], bv[kPack<T>];
+        load_pack<T, true>(r, e, (int)cnt, rv);
+        if constexpr (FIRST) load_pack<T, AL>(b, e, (int)cnt, bv);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++)
+            if (l < cnt) {
+                acc[0] += (double)rv[l] * (double)rv[l];
+                if constexpr (FIRST) acc[1] += (double)bv[l] * (double)bv[l];
+            }
+    }
+    store_partials<2>(acc, out, sh);          // (a later cycle's set 1 is +0 and nobody reads it)
+}
+
+// A cycle's start, behind gmres_rr_kernel: the stop test on the true residual (`first`: the call's start, which fills the cell); a cycle that starts gets
+// g_0 = ||r||, v_0 = T(double(r) / ||r||) and, with a preconditioner, z_0.  AL: minv is aligned.
+template <typename T, bool PRE, bool AL>
+__global__ __launch_bounds__(kThreads) void gmres_begin_kernel(const T *__restrict__ r, const T *__restrict__ minv, T *__restrict__ v0, T *__restrict__ z, long long n,
+                                                               const double *__restrict__ part, double rtol, int first, GmresCell *__restrict__ cell)
+{
+    __shared__ double sh[2][kWaves];
+    __shared__ int    stopped;
+    if (threadIdx.x == 0) stopped = first ? 0 : cell->hd.stop;
+    double s[2];
+    sum_partials<2>(part, s, sh);
+    if (stopped) return;
+    const double bb = first ? s[1] : cell->hd.bb, bnorm = first ? sqrt(s[1]) : cell->hd.bnorm;
+    const double rnorm = sqrt(s[0]);
+    const bool   zero = first && bb == 0;
+    const bool   done = !zero && rnorm <= rtol * bnorm && rnorm <= kDblMax;
+    const bool   broken = !zero && !done && !(rnorm <= kDblMax);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (first) {
+            GmresHead hd;
+            hd.bb = bb; hd.bnorm = bnorm; hd.rnorm = zero ? 0 : rnorm; hd.hrot = 0;
+            hd.stop = zero || done || broken; hd.status = broken ? CVR_CG_BREAKDOWN : zero || done ? CVR_CG_CONVERGED : CVR_CG_MAX_ITERS;
+            hd.iters = 0; hd.zero_x = zero; hd.owed = 0; hd.owed_at = 0;
+            cell->hd = hd;
+        } else {
+            cell->hd.rnorm = rnorm;
+            cell->hd.owed = 0;
+            if (done) { cell->hd.status = CVR_CG_CONVERGED; cell->hd.stop = 1; }
+            if (broken) { cell->hd.status = CVR_CG_BREAKDOWN; cell->hd.stop = 1; }
+        }
+        cell->gbar[0] = rnorm;
+    }
+    if (zero || done || broken) return;
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T rv[kPack<T>], mv[kPack<T>], zv[kPack<T>];
+        load_pack<T, true>(r, e, (int)cnt, rv);
+        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) {
+            rv[l] = (T)((double)rv[l] / rnorm);
+            if constexpr (PRE) zv[l] = (T)((double)mv[l] * (double)rv[l]);
+        }
+        store_pack<T, true>(v0, e, (int)cnt, rv);
+        if constexpr (PRE) store_pack<T, true>(z, e, (int)cnt, zv);
+    }
+}
+
+// x from the columns the cell says are owed, when the step that said so lies in (lo, hi]: per value u = +0, u = u + y_i double(v_i) for i ascending,
+// x = T(double(x) + double(minv) * u), or T(double(x) + u) without a preconditioner.  Reads the cell only.  AL: x and minv are aligned.
+template <typename T, bool PRE, bool AL>
+__global__ __launch_bounds__(kThreads) void gmres_x_kernel(T *__restrict__ x, const T *__restrict__ minv, const T *__restrict__ V, long long stride, long long n,
+                                                           const GmresCell *__restrict__ cell, int lo, int hi)
+{
+    __shared__ double ys[kMaxM];
+    const int q = cell->hd.owed, at = cell->hd.owed_at;
+    if (q <= 0 || at <= lo || at > hi) return;
+    for (int i = threadIdx.x; i < q; i += kThreads) ys[i] = cell->y[i];
+    __syncthreads();
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T      xv[kPack<T>], mv[kPack<T>];
+        double u[kPack<T>];
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) u[l] = 0;
+        load_pack<T, AL>(x, e, (int)cnt, xv);
+        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
+        CVR_GMRES_GROUPS(add_group, q, ys, u);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) {
+            if constexpr (PRE) xv[l] = (T)((double)xv[l] + (double)mv[l] * u[l]);
+            else xv[l] = (T)((double)xv[l] + u[l]);
+        }
+        store_pack<T, AL>(x, e, (int)cnt, xv);
+    }
+}
+
+#undef CVR_GMRES_GROUPS
+#undef CVR_KRYLOV_PACKETS
+
+// the library's buffers of one call, one allocation: restart + 1 basis vectors and (with a preconditioner) z (x_ext each: SpMV inputs), w and r (y_ext
+// each: r takes the scaled product), the partial sums of the dots (one set per column) and of r . r, b . b and w . w, the cell
+struct Workspace {
+    uint8_t   *arena = nullptr;
+    void      *V = nullptr, *z = nullptr, *w = nullptr, *r = nullptr;
+    double    *part_h = nullptr, *part_s = nullptr;
+    GmresCell *cell = nullptr;
+    long long  stride = 0;          // of the basis, in values
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Workspace()
+    {
+        if (arena) (void)hipFree(arena);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+#define CVR_GMRES_LAUNCH(kernel, ...) hipLaunchKernelGGL((kernel), dim3(kBlocks), dim3(kThreads), 0, st, __VA_ARGS__)
+// the instantiation by preconditioner and alignment of the caller's arrays
+#define CVR_GMRES_PRE_AL(name, ...)                                                                                                             \
+    do {                                                                                                                                        \
+        if (minv) { if (al) CVR_GMRES_LAUNCH((name<T, true, true>), __VA_ARGS__); else CVR_GMRES_LAUNCH((name<T, true, false>), __VA_ARGS__); } \
+        else      { if (al) CVR_GMRES_LAUNCH((name<T, false, true>), __VA_ARGS__); else CVR_GMRES_LAUNCH((name<T, false, false>), __VA_ARGS__); } \
+    } while (0)
+
+template <typename T> const T *basis(const Workspace &w, int i) { return static_cast<const T *>(w.V) + (long long)i * w.stride; }
+template <typename T> T       *basis_mut(const Workspace &w, int i) { return static_cast<T *>(w.V) + (long long)i * w.stride; }
+
+// behind the scaled product r = b - A x: the sums and the cycle's start
+template <typename T>
+hipError_t launch_begin(const Workspace &w, const void *b, const void *minv, long long n, bool al, double rtol, bool first, hipStream_t st)
+{
+    if (first) {
+        if (al) CVR_GMRES_LAUNCH((gmres_rr_kernel<T, true, true>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
+        else CVR_GMRES_LAUNCH((gmres_rr_kernel<T, true, false>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
+    } else CVR_GMRES_LAUNCH((gmres_rr_kernel<T, false, true>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
+    CVR_GMRES_PRE_AL(gmres_begin_kernel, static_cast<const T *>(w.r), static_cast<const T *>(minv), basis_mut<T>(w, 0), static_cast<T *>(w.z), n, w.part_s, rtol,
+                     first ? 1 : 0, w.cell);
+    return hipGetLastError();
+}
+
+// step k with column j behind w = A z_j: the two Gram-Schmidt passes and the finish
+template <typename T>
+hipError_t launch_step(const Workspace &w, const void *minv, long long n, bool al, int j, int k, int m, int max_iters, double rtol, hipStream_t st)
+{
+    const T *V = basis<T>(w, 0);
+    T       *wv = static_cast<T *>(w.w);
+    CVR_GMRES_LAUNCH((gmres_dots_kernel<T>), V, w.stride, wv, n, j + 1, w.part_h, w.cell);
+    CVR_GMRES_LAUNCH((gmres_update_kernel<T, false>), V, w.stride, wv, n, j, w.part_h, w.part_s, w.cell);
+    CVR_GMRES_LAUNCH((gmres_dots_kernel<T>), V, w.stride, wv, n, j + 1, w.part_h, w.cell);
+    CVR_GMRES_LAUNCH((gmres_update_kernel<T, true>), V, w.stride, wv, n, j, w.part_h, w.part_s, w.cell);
+    // (v_(j+1) and z_(j+1) are written only when j + 1 < m: basis vector m is never a column; it carries x into the scaled product)
+    if (minv) {
+        if (al) CVR_GMRES_LAUNCH((gmres_finish_kernel<T, true, true>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
+        else CVR_GMRES_LAUNCH((gmres_finish_kernel<T, true, false>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
+    } else CVR_GMRES_LAUNCH((gmres_finish_kernel<T, false, true>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_x(const Workspace &w, void *x, const void *minv, long long n, bool al, int lo, int hi, hipStream_t st)
+{
+    CVR_GMRES_PRE_AL(gmres_x_kernel, static_cast<T *>(x), static_cast<const T *>(minv), basis<T>(w, 0), w.stride, n, w.cell, lo, hi);
+    return hipGetLastError();
+}
+
+int check_restart(int32_t restart)
+{
+    if (restart < 1 || restart > kMaxM) return fail(CVR_ERR_INVALID, "restart = %d: must be in 1 .. %d", restart, kMaxM);
+    return CVR_OK;
+}
+
+int check_handle(const cvr_handle *h)
+{
+    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_gmres before cvr_preprocess");
+    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "GMRES needs a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    return CVR_OK;
+}
+
+// behind the argument checks
+int gmres_device(cvr_handle *h, const void *b, void *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    if (const int rc = check_handle(h)) return rc;
+    Range range("cvr_gmres_device");
+    HIP_TRY(hipSetDevice(h->device));
+    const long long n = h->info.nrows;
+    const bool      f32 = h->vsz == 4;
+    const void     *minv = opt->minv_dev;
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
+
+    Workspace w;
+    size_t    nx = 0;
+    {
+        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        nx = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.x_elems, n + 1), 1));
+        const size_t ny = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
+        const size_t nh = minv ? nx : 0, nph = up(sizeof(double) * (size_t)m * kBlocks), nps = up(sizeof(double) * 2 * kBlocks);
+        const size_t total = (size_t)(m + 1) * nx + nh + 2 * ny + nph + nps + up(sizeof(GmresCell));
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&w.arena), total);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            w.arena = nullptr;
+            return fail(CVR_ERR_NOMEM, "cvr_gmres: no device memory for %d basis vectors (%zu bytes)", m + 1, total);
+        }
+        HIP_TRY(e);
+        uint8_t *a = w.arena;
+        w.V = a; a += (size_t)(m + 1) * nx;
+        w.z = minv ? a : nullptr; a += nh;
+        w.w = a; a += ny;
+        w.r = a; a += ny;
+        w.part_h = reinterpret_cast<double *>(a); a += nph;
+        w.part_s = reinterpret_cast<double *>(a); a += nps;
+        w.cell = reinterpret_cast<GmresCell *>(a);
+        w.stride = (long long)(nx / h->vsz);
+    }
+    HIP_TRY(hipEventCreate(&w.e0));
+    HIP_TRY(hipEventCreate(&w.e1));
+    HIP_TRY(hipEventRecord(w.e0, st));
+
+    // the pad slots of the SpMV inputs; basis vector 1 carries x into the scaled product (it is a column only from step 1 of a cycle on), r = b;
+    // r = b - A x; then the sums, the stop test and v_0
+    const size_t vb = h->vsz * (size_t)n;
+    uint8_t     *xin = static_cast<uint8_t *>(w.V) + nx;
+    for (int i = 0; i <= m; i++) HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.V) + (size_t)i * nx + vb, 0, h->vsz, st));
+    if (w.z) HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.z) + vb, 0, h->vsz, st));
+    auto residual = [&](bool first) -> int {
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(xin, x, vb, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(w.r, b, vb, hipMemcpyDeviceToDevice, st));
+        }
+        if (const int rc = spmv_scaled_enqueue(h, -1.0, xin, 1.0, w.r, st)) return rc;
+        HIP_TRY(f32 ? launch_begin<float>(w, b, minv, n, al, opt->rtol, first, st) : launch_begin<double>(w, b, minv, n, al, opt->rtol, first, st));
+        return CVR_OK;
+    };
+    if (const int rc = residual(true)) return rc;
+    int spmvs = 1;
+
+    GmresHead hd{};
+    int       x_lo = 0;          // the steps whose finish a gmres_x_kernel has looked at
+    auto form_x = [&](int hi) -> int {
+        if (hi > x_lo) HIP_TRY(f32 ? launch_x<float>(w, x, minv, n, al, x_lo, hi, st) : launch_x<double>(w, x, minv, n, al, x_lo, hi, st));
+        x_lo = hi;
+        return CVR_OK;
+    };
+    for (int done = 0;;) {
+        const int batch = std::min(every, opt->max_iters - done);
+        for (int i = 0; i < batch; i++) {
+            const int k = done + i, j = k % m;
+            if (j == 0 && k > 0) {          // the cycle before is full: its x, then the next one from the true residual
+                if (const int rc = form_x(k)) return rc;
+                if (const int rc = residual(false)) return rc;
+                spmvs++;
+            }
+            const void *zin = minv ? w.z : static_cast<const void *>(static_cast<const uint8_t *>(w.V) + (size_t)j * nx);
+            HIP_TRY(run_spmv(h, zin, w.w, st));
+            HIP_TRY(f32 ? launch_step<float>(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st) : launch_step<double>(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st));
+            spmvs++;
+        }
+        done += batch;
+        if (const int rc = form_x(done)) return rc;
+        HIP_TRY(hipMemcpyAsync(&hd, &w.cell->hd, sizeof(hd), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (hd.stop || done >= opt->max_iters) break;
+    }
+    if (hd.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    HIP_TRY(hipEventRecord(w.e1, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
+    memset(res, 0, sizeof(*res));
+    res->iterations = hd.iters;
+    res->status = hd.status;
+    res->spmv_count = spmvs;
+    res->residual_norm = hd.rnorm;
+    res->b_norm = hd.bnorm;
+    res->seconds = (double)ms * 1e-3;
+    return CVR_OK;
+}
+
+#undef CVR_GMRES_PRE_AL
+#undef CVR_GMRES_LAUNCH
+
+}  // namespace
+
+extern "C" {
+
+int cvr_gmres_device(cvr_handle *h, const void *b_dev, void *x_dev, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res, void *stream)
+{
+    if (const int rc = check_solver_args(h, b_dev, x_dev, opt, res)) return rc;
+    if (const int rc = check_restart(restart)) return rc;
+    return gmres_device(h, b_dev, x_dev, restart, opt, res, (hipStream_t)stream);
+}
+
+int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res)
+{
+    if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
+    if (const int rc = check_restart(restart)) return rc;
+    if (const int rc = check_handle(h)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t vb = h->vsz * (size_t)h->info.nrows;          // the handle's own vectors carry b and x: d_x has ncols + 1 values, d_y at least nrows
+    if (vb) {
+        HIP_TRY(hipMemcpyAsync(h->d_x, x_host, vb, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->d_y, b_host, vb, hipMemcpyHostToDevice, h->stream));
+    }
+    const int rc = gmres_device(h, h->d_y, h->d_x, restart, opt, res, h->stream);
+    if (rc) return rc;
+    if (vb) HIP_TRY(hipMemcpyAsync(x_host, h->d_x, vb, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return CVR_OK;
+}
+
+}  // extern "C"

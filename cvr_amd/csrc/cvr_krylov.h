@@ -1,4 +1,4 @@
-// cvr_krylov.h -- what the Krylov solvers' vector kernels share (cvr_cg.hip, cvr_cg_multi.hip, cvr_bicgstab.hip): the fixed grid, the 16-byte packet helpers, the
+// cvr_krylov.h -- what the Krylov solvers' vector kernels share (cvr_cg.hip, cvr_cg_multi.hip, cvr_bicgstab.hip, cvr_gmres.hip): the fixed grid, the 16-byte packet helpers, the
 // fixed-tree fp64 sums and the argument checks of their entry points.  Every translation unit that includes it gets the same code, so a sum has
 // the same bits whichever solver forms it.
 #pragma once

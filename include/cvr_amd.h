@@ -405,9 +405,10 @@ int cvr_spmv_gather_repeat(cvr_handle *h, cvr_comm *comm, const void *x_dev, voi
 int cvr_power_iteration(cvr_handle *h, cvr_comm *comm, const int64_t *bounds, int iters, void *x_dev, double *lambda,
                         double *seconds_per_iter, void *stream);
 
-/* ---- solving A x = b on the device: conjugate gradients and BiCGSTAB ----------------------------------
- * cvr_cg_device / cvr_cg for a symmetric positive definite A, cvr_bicgstab_device / cvr_bicgstab for any nonsingular A, nonsymmetric ones included,
- * held by a single-GPU handle of a square matrix (any layout; fused-preprocess, image-cache, mutable and transposed handles included).  Both
+/* ---- solving A x = b on the device: conjugate gradients, BiCGSTAB and GMRES(m) ------------------------
+ * cvr_cg_device / cvr_cg for a symmetric positive definite A, cvr_bicgstab_device / cvr_bicgstab and cvr_gmres_device / cvr_gmres for any nonsingular A,
+ * nonsymmetric ones included,
+ * held by a single-GPU handle of a square matrix (any layout; fused-preprocess, image-cache, mutable and transposed handles included).  The
  * solvers share the options, the result and the status codes below.  The whole loop runs on the device: the scalars live in a small state cell in device memory, every
  * vector kernel forms the scalar it needs from the partial sums of the kernel before (in every workgroup, in the same order), and the host
  * reads the cell back once per `check_every` iterations.  (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.) */
@@ -423,7 +424,8 @@ typedef struct {
 #define CVR_CG_CONVERGED 0
 #define CVR_CG_MAX_ITERS 1
 #define CVR_CG_BREAKDOWN 2    /* CG: p.Ap <= 0 or not finite: A is not positive definite on the Krylov space;
-                                 BiCGSTAB: r^.v, t.t, omega or r^.r zero or not finite                       */
+                                 BiCGSTAB: r^.v, t.t, omega or r^.r zero or not finite;
+                                 GMRES: a cycle's start residual not finite, or rho zero or not finite          */
 
 typedef struct {
     int32_t iterations;       /* steps applied to x (BiCGSTAB: a stop at the half step counts as one)     */
@@ -528,6 +530,52 @@ int cvr_cg_multi(cvr_handle *h, const void *B_host, void *X_host, int32_t nvec, 
 int cvr_bicgstab_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg.  opt->minv_dev stays a device pointer. */
 int cvr_bicgstab(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
+
+/* Restarted GMRES(m) for any nonsingular A: never breaks down on one, its residual estimate never grows, and a cycle of m steps is bounded.  Right-
+ * preconditioned (M = diag(minv_dev)), classical Gram-Schmidt applied twice, Givens rotations; one SpMV per step, one more per restart.  `restart` = m,
+ * 1 .. CVR_GMRES_MAX_RESTART (an argument: cvr_cg_options.reserved stays 0).  The handles, b_dev, x_dev, the options, the result, the status codes, the
+ * ordering ("not capturable in a HIP graph", makes the handle's device current) are cvr_bicgstab_device's.  The buffers of the call are the library's,
+ * allocated per call: restart + 1 basis vectors and (with minv_dev) z of info.x_elems values whose element ncols stays 0, w and r of info.yext_elems
+ * values.
+ * Arithmetic, T = the handle's type; every operation below is rounded on its own (no fused multiply-add); scalars are fp64.  Every sum a.b is
+ * cvr_cg_device's fixed tree over the terms double(a_i) * double(b_i), and each sum has its own 1024 partials, so its bits do not depend on how many
+ * sums a kernel forms at once.  k = steps done in the call, j = k mod m the step within the cycle.
+ *   Start of the call and of every cycle: r = b - A x by one cvr_spmv_scaled_device with alpha = -1, beta = 1 (in T);  bb = b.b (once), rr = r.r,
+ *     bnorm = sqrt(bb), rnorm = sqrt(rr).  At the call's start bb == 0: x = 0, CVR_CG_CONVERGED, 0 iterations.  rnorm finite and
+ *     rnorm <= rtol * bnorm: CVR_CG_CONVERGED, x untouched by this test, iterations = the steps so far, residual_norm = rnorm.  rnorm not finite:
+ *     CVR_CG_BREAKDOWN, x untouched by this cycle (a NaN or an Inf in b: 0 iterations, x untouched), residual_norm = rnorm.  Otherwise
+ *     v_0 = T(double(r) / rnorm) and g_0 = rnorm.
+ *   Step j: z = T(double(minv) * double(v_j)), or v_j itself without minv_dev (no buffer, no pass);  w = A z through cvr_spmv_device's launch path
+ *     (bit for bit its y).
+ *     Pass 1: h_i = v_i . w for i = 0..j, all on the same w;  then t = double(w), t = t - h_0 * double(v_0), ..., t = t - h_j * double(v_j) in that
+ *       order, w = T(t) (one rounding to T).
+ *     Pass 2, the same on the new w: d_i = v_i . w, the same update with d;  then H_i = h_i + d_i.  Always two passes.
+ *     ww = w.w;  H_(j+1) = sqrt(ww).
+ *     The earlier rotations, i = 0..j-1 in order: t = cs_i * H_i + sn_i * H_(i+1);  H_(i+1) = cs_i * H_(i+1) - sn_i * H_i;  H_i = t.
+ *     rho = sqrt(H_j * H_j + H_(j+1) * H_(j+1)).
+ *     rho zero or not finite: CVR_CG_BREAKDOWN, found before the step is counted; x is formed from the j columns before it (below; j = 0: x is the
+ *       cycle's start); residual_norm = |g_j|.
+ *     Otherwise cs_j = H_j / rho, sn_j = H_(j+1) / rho;  R_(i,j) = H_i for i < j, R_(j,j) = rho;  g_(j+1) = -(sn_j * g_j), then g_j = cs_j * g_j.
+ *       The step now counts: iterations = k + 1, and the estimate is e = |g_(j+1)|.
+ *     e finite and e <= rtol * bnorm: x is formed from j + 1 columns, CVR_CG_CONVERGED with residual_norm = e (H_(j+1) == 0, the lucky breakdown,
+ *       gives e == 0 and ends here: v_(j+1) is never formed).
+ *     Else, k + 1 == max_iters: x is formed from j + 1 columns, CVR_CG_MAX_ITERS with residual_norm = e.
+ *     Else, j + 1 == m: x is formed from m columns and the next cycle starts (above: from the true residual of that x).
+ *     Else v_(j+1) = T(double(w) / H_(j+1)) with the unrotated H_(j+1) = sqrt(ww).
+ *   Forming x from q columns (q = 0: nothing): for i = q-1 down to 0: t = g_i; for l = i+1..q-1 ascending t = t - R_(i,l) * y_l; y_i = t / R_(i,i).
+ *     Per element u = +0; for i = 0..q-1: u = u + y_i * double(v_i);  x = T(double(x) + double(minv) * u), or T(double(x) + u) without minv_dev.
+ * max_iters = 0: the start only (spmv_count == 1).  spmv_count = 1 + the steps enqueued + the restarts enqueued (a restart is enqueued in front of the
+ * first step of a later cycle, not behind the last step of the call).
+ * check_every: x, iterations, status, residual_norm and b_norm are bit for bit the same for every value (a batch may run across a cycle's end, the
+ * restart's scaled product included; kernels behind a stop return without writing); only spmv_count and seconds differ.  Five vector launches beside
+ * the SpMV per step, whatever j: the sums v_i . w of a pass in one launch, the update of a pass in one launch, and the finish.
+ * Errors, in this order, before any device work and before the handle is looked at: cvr_cg_device's argument checks; restart < 1 or
+ * restart > CVR_GMRES_MAX_RESTART: CVR_ERR_INVALID ("restart" in cvr_last_error).  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols:
+ * CVR_ERR_INVALID; no device memory for the call's buffers: CVR_ERR_NOMEM, nothing allocated. */
+#define CVR_GMRES_MAX_RESTART 64
+int cvr_gmres_device(cvr_handle *h, const void *b_dev, void *x_dev, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg.  opt->minv_dev stays a device pointer. */
+int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
 
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
