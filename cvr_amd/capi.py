@@ -609,20 +609,16 @@ class CvrMatrix:
         opt.minv_dev = minv_ptr
         return opt
 
-    def cg(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
-        """solves A x = b for a symmetric positive definite A by conjugate gradients on the device (cvr_cg_device): b_ptr and x_ptr are
-        device arrays of nrows values (x: the start vector in, the solution out), minv_ptr an optional diagonal preconditioner (nrows
-        values, z = minv .* r); rtol / max_iters None: the library's defaults.  Returns the CgResult (iterations, status = CG_*,
-        spmv_count, residual_norm, b_norm, seconds); synchronises the stream."""
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
-        rc = lib().cvr_cg_device(self._h, b_ptr, x_ptr, C.byref(opt), C.byref(res), stream)
+    def _solve(self, symbol, opt, head, tail=()):
+        """one single-vector solver call: symbol(handle, *head, &opt, &res, *tail); returns the CgResult"""
+        res = CgResult()
+        rc = getattr(lib(), symbol)(self._h, *head, C.byref(opt), C.byref(res), *tail)
         if rc:
-            raise CvrError(rc, "cvr_cg_device")
+            raise CvrError(rc, symbol)
         return res
 
-    def cg_host(self, b, x0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
-        """the same through host arrays (cvr_cg): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device
-        pointer.  Returns (x, CgResult)."""
+    def _host_vectors(self, b, x0):
+        """a host solver's b, contiguous in the handle's type, and its x: x0 (None: zero) in a new array of at least one value"""
         b = np.ascontiguousarray(b, dtype=self.dtype)
         if len(b) < self.nrows:
             raise ValueError("b is shorter than nrows")
@@ -632,10 +628,26 @@ class CvrMatrix:
             if len(x0) < self.nrows:
                 raise ValueError("x0 is shorter than nrows")
             x[: self.nrows] = x0[: self.nrows]
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
-        rc = lib().cvr_cg(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
-        if rc:
-            raise CvrError(rc, "cvr_cg")
+        return b, x
+
+    def _gmres_options(self, name, options, minv):
+        rtol, max_iters, check_every = options.pop("rtol", None), options.pop("max_iters", None), options.pop("check_every", 0)
+        if options:
+            raise TypeError(f"{name}: unknown options {sorted(options)}")
+        return self._cg_options(rtol, max_iters, check_every, None if minv is None else minv.data_ptr())
+
+    def cg(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
+        """solves A x = b for a symmetric positive definite A by conjugate gradients on the device (cvr_cg_device): b_ptr and x_ptr are
+        device arrays of nrows values (x: the start vector in, the solution out), minv_ptr an optional diagonal preconditioner (nrows
+        values, z = minv .* r); rtol / max_iters None: the library's defaults.  Returns the CgResult (iterations, status = CG_*,
+        spmv_count, residual_norm, b_norm, seconds); synchronises the stream."""
+        return self._solve("cvr_cg_device", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b_ptr, x_ptr), (stream,))
+
+    def cg_host(self, b, x0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_cg): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device
+        pointer.  Returns (x, CgResult)."""
+        b, x = self._host_vectors(b, x0)
+        res = self._solve("cvr_cg", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b.ctypes.data, x.ctypes.data))
         return x[: self.nrows], res
 
     def cg_multi(self, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
@@ -673,28 +685,13 @@ class CvrMatrix:
         """solves A x = b for a nonsymmetric A by right-preconditioned BiCGSTAB on the device (cvr_bicgstab_device): the arguments and the
         CgResult are cg's (minv_ptr: p^ = minv .* p, s^ = minv .* s; a stop at the half step counts as one iteration; two SpMVs per
         step); synchronises the stream."""
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
-        rc = lib().cvr_bicgstab_device(self._h, b_ptr, x_ptr, C.byref(opt), C.byref(res), stream)
-        if rc:
-            raise CvrError(rc, "cvr_bicgstab_device")
-        return res
+        return self._solve("cvr_bicgstab_device", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b_ptr, x_ptr), (stream,))
 
     def bicgstab_host(self, b, x0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
         """the same through host arrays (cvr_bicgstab): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device
         pointer.  Returns (x, CgResult)."""
-        b = np.ascontiguousarray(b, dtype=self.dtype)
-        if len(b) < self.nrows:
-            raise ValueError("b is shorter than nrows")
-        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
-        if x0 is not None:
-            x0 = np.asarray(x0, dtype=self.dtype)
-            if len(x0) < self.nrows:
-                raise ValueError("x0 is shorter than nrows")
-            x[: self.nrows] = x0[: self.nrows]
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), CgResult()
-        rc = lib().cvr_bicgstab(self._h, b.ctypes.data, x.ctypes.data, C.byref(opt), C.byref(res))
-        if rc:
-            raise CvrError(rc, "cvr_bicgstab")
+        b, x = self._host_vectors(b, x0)
+        res = self._solve("cvr_bicgstab", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b.ctypes.data, x.ctypes.data))
         return x[: self.nrows], res
 
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
@@ -702,36 +699,17 @@ class CvrMatrix:
         arrays (anything with data_ptr() and new_zeros()) of nrows values of the handle's type: x0 is the start vector and is overwritten with the
         solution (None: a new zero array), minv the optional right preconditioner.  options: rtol, max_iters (None: the library's defaults),
         check_every.  Returns (x, CgResult); synchronises the stream."""
-        rtol, max_iters, check_every = options.pop("rtol", None), options.pop("max_iters", None), options.pop("check_every", 0)
-        if options:
-            raise TypeError(f"gmres: unknown options {sorted(options)}")
+        opt = self._gmres_options("gmres", options, minv)
         x = b.new_zeros(max(self.nrows, 1)) if x0 is None else x0
-        opt, res = self._cg_options(rtol, max_iters, check_every, None if minv is None else minv.data_ptr()), CgResult()
-        rc = lib().cvr_gmres_device(self._h, b.data_ptr(), x.data_ptr(), int(restart), C.byref(opt), C.byref(res), stream)
-        if rc:
-            raise CvrError(rc, "cvr_gmres_device")
+        res = self._solve("cvr_gmres_device", opt, (b.data_ptr(), x.data_ptr(), int(restart)), (stream,))
         return (x[: self.nrows] if x0 is None else x), res
 
     def gmres_host(self, b, x0=None, restart=30, minv=None, **options):
         """the same through host arrays (cvr_gmres): b and the start vector x0 (None: zero) of nrows values; minv stays a device array.
         Returns (x, CgResult)."""
-        rtol, max_iters, check_every = options.pop("rtol", None), options.pop("max_iters", None), options.pop("check_every", 0)
-        if options:
-            raise TypeError(f"gmres_host: unknown options {sorted(options)}")
-        b = np.ascontiguousarray(b, dtype=self.dtype)
-        if len(b) < self.nrows:
-            raise ValueError("b is shorter than nrows")
-        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
-        if x0 is not None:
-            x0 = np.asarray(x0, dtype=self.dtype)
-            if len(x0) < self.nrows:
-                raise ValueError("x0 is shorter than nrows")
-            x[: self.nrows] = x0[: self.nrows]
-        opt, res = self._cg_options(rtol, max_iters, check_every, None if minv is None else minv.data_ptr()), CgResult()
-        rc = lib().cvr_gmres(self._h, b.ctypes.data, x.ctypes.data, int(restart), C.byref(opt), C.byref(res))
-        if rc:
-            raise CvrError(rc, "cvr_gmres")
-        return x[: self.nrows], res
+        opt = self._gmres_options("gmres_host", options, minv)
+        b, x = self._host_vectors(b, x0)
+        return x[: self.nrows], self._solve("cvr_gmres", opt, (b.ctypes.data, x.ctypes.data, int(restart)))
 
     def spmm(self, X, iters=1):
         """Y = A X for the k columns of X (host array of shape (ncols, k)) in one pass per block of 8 (cvr_spmm); returns (Y of shape

@@ -12,6 +12,7 @@
 // the packet helpers are cvr_krylov.h's, so a call gives the same bits every time.  The scalars that outlive a kernel sit in a state cell (BiCell) that
 // workgroup 0 writes: the kernel that finds a stop records it there and every later kernel of the batch returns without writing -- the result does not
 // depend on how many steps the host enqueues between two read-backs.
+// The host side is cvr_krylov.h's driver: this file adds the cell, the kernels, the step and the read-back.
 // (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 
@@ -19,8 +20,6 @@ using namespace cvrh;
 using namespace cvrh::krylov;
 
 namespace {
-
-constexpr double kDblMax = 1.7976931348623157e308;
 
 // The state cell.  Written by thread 0 of workgroup 0 only; a value a kernel reads is one that a kernel BEFORE it wrote (rho of this step sits in
 // rho[k & 1], the next one's goes to rho[(k + 1) & 1]) -- except `stop`, which the other workgroups of the kernel that sets it may or may not see
@@ -38,8 +37,6 @@ struct BiCell {
     int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
     int32_t pad;
 };
-
-__device__ __forceinline__ bool usable(double v) { return v != 0 && fabs(v) <= kDblMax; }          // neither zero nor Inf nor NaN
 
 // The start: r holds b - A x0 (the scaled product).  r^ = r, p = r, p^ = minv .* p (PRE), and the partial sums of r . r (= r^ . r) and b . b.
 // AL: b and minv, the caller's arrays, are 16-byte aligned.
@@ -281,70 +278,89 @@ __global__ __launch_bounds__(kThreads) void bicg_direction_kernel(T *__restrict_
 
 #undef CVR_KRYLOV_PACKETS
 
-// the library's buffers of one call, one allocation: p and s (x_ext each: SpMV inputs without a preconditioner), p^ and s^ (x_ext each, with one),
+// the library's buffers of one call: p and s (x_ext each: SpMV inputs without a preconditioner), p^ and s^ (x_ext each, with one),
 // v, t and r (y_ext each: r takes the scaled product), r^, two sets of partial sums that the kernels use in turn, the cell
+template <typename T>
 struct Workspace {
-    uint8_t   *arena = nullptr;
-    void      *p = nullptr, *s = nullptr, *phat = nullptr, *shat = nullptr, *v = nullptr, *t = nullptr, *r = nullptr, *rhat = nullptr;
-    double    *part_a = nullptr, *part_b = nullptr;
-    BiCell    *cell = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Workspace()
-    {
-        if (arena) (void)hipFree(arena);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
+    T      *p, *s, *phat, *shat, *v, *t, *r, *rhat;
+    double *part_a, *part_b;
+    BiCell *cell;
 };
 
-#define CVR_BICG_LAUNCH(kernel, ...) hipLaunchKernelGGL((kernel), dim3(kBlocks), dim3(kThreads), 0, st, __VA_ARGS__)
-// the instantiation by preconditioner and alignment; without a preconditioner `al_pre` alone decides (a kernel whose only caller's array is minv: true)
-#define CVR_BICG_PRE_AL(name, al_pre, al_plain, ...)                                                                                                  \
-    do {                                                                                                                                              \
-        if (minv) { if (al_pre) CVR_BICG_LAUNCH((name<T, true, true>), __VA_ARGS__); else CVR_BICG_LAUNCH((name<T, true, false>), __VA_ARGS__); }      \
-        else      { if (al_plain) CVR_BICG_LAUNCH((name<T, false, true>), __VA_ARGS__); else CVR_BICG_LAUNCH((name<T, false, false>), __VA_ARGS__); } \
-    } while (0)
-
+// step k up to the second SpMV: r^ . v, then alpha and s (the SpMV v = A p^ is enqueued in front).  (A kernel whose only caller's array is minv
+// has no <T, false, false> form: AL || !PRE.)
 template <typename T>
-hipError_t launch_init(const Workspace &w, const void *b, const void *minv, long long n, bool al, hipStream_t st)
+hipError_t launch_first_half(const Workspace<T> &w, const T *minv, long long n, bool al, int k, hipStream_t st)
 {
-    CVR_BICG_PRE_AL(bicg_init_kernel, al, al, static_cast<const T *>(b), static_cast<const T *>(minv), static_cast<const T *>(w.r), static_cast<T *>(w.rhat),
-                    static_cast<T *>(w.p), static_cast<T *>(w.phat), n, w.part_b);
-    return hipGetLastError();
-}
-
-// step k up to the second SpMV: r^ . v, then alpha and s (the SpMV v = A p^ is enqueued in front)
-template <typename T>
-hipError_t launch_first_half(const Workspace &w, const void *minv, long long n, bool al, int k, hipStream_t st)
-{
-    CVR_BICG_LAUNCH((bicg_rv_kernel<T>), static_cast<const T *>(w.rhat), static_cast<const T *>(w.v), n, w.part_a, w.cell);
-    if (minv) {
-        if (al) CVR_BICG_LAUNCH((bicg_s_kernel<T, true, true>), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), static_cast<T *>(w.s), static_cast<T *>(w.shat), n, w.part_a, w.part_b, w.cell, k);
-        else CVR_BICG_LAUNCH((bicg_s_kernel<T, true, false>), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), static_cast<T *>(w.s), static_cast<T *>(w.shat), n, w.part_a, w.part_b, w.cell, k);
-    } else CVR_BICG_LAUNCH((bicg_s_kernel<T, false, true>), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), static_cast<T *>(w.s), static_cast<T *>(w.shat), n, w.part_a, w.part_b, w.cell, k);
+    launch(bicg_rv_kernel<T>, st, w.rhat, w.v, n, w.part_a, w.cell);
+    with_flags([&](auto PRE, auto AL) { launch(bicg_s_kernel<T, PRE, AL || !PRE>, st, w.r, w.v, minv, w.s, w.shat, n, w.part_a, w.part_b, w.cell, k); }, minv != nullptr, al);
     return hipGetLastError();
 }
 
 // the rest of step k (the SpMV t = A s^ is enqueued in front): the half-step test, the update, the stop test and the new direction
 template <typename T>
-hipError_t launch_second_half(const Workspace &w, void *x, const void *minv, long long n, bool al, int k, double rtol, hipStream_t st)
+hipError_t launch_second_half(const Workspace<T> &w, T *x, const T *minv, long long n, bool al, int k, double rtol, hipStream_t st)
 {
-    const T *ph = static_cast<const T *>(minv ? w.phat : w.p), *sh = static_cast<const T *>(minv ? w.shat : w.s);
-    if (al) CVR_BICG_LAUNCH((bicg_half_kernel<T, true>), static_cast<T *>(x), ph, static_cast<const T *>(w.s), static_cast<const T *>(w.t), n, w.part_b, w.part_a, w.cell, k, rtol);
-    else CVR_BICG_LAUNCH((bicg_half_kernel<T, false>), static_cast<T *>(x), ph, static_cast<const T *>(w.s), static_cast<const T *>(w.t), n, w.part_b, w.part_a, w.cell, k, rtol);
-    CVR_BICG_PRE_AL(bicg_update_kernel, al, al, static_cast<T *>(x), static_cast<T *>(w.r), ph, sh, static_cast<const T *>(w.s), static_cast<const T *>(w.t),
-                    static_cast<const T *>(w.rhat), n, w.part_a, w.part_b, w.cell, k);
-    if (minv) {
-        if (al) CVR_BICG_LAUNCH((bicg_direction_kernel<T, true, true>), static_cast<T *>(w.p), static_cast<T *>(w.phat), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), n, w.part_b, w.cell, k, rtol);
-        else CVR_BICG_LAUNCH((bicg_direction_kernel<T, true, false>), static_cast<T *>(w.p), static_cast<T *>(w.phat), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), n, w.part_b, w.cell, k, rtol);
-    } else CVR_BICG_LAUNCH((bicg_direction_kernel<T, false, true>), static_cast<T *>(w.p), static_cast<T *>(w.phat), static_cast<const T *>(w.r), static_cast<const T *>(w.v), static_cast<const T *>(minv), n, w.part_b, w.cell, k, rtol);
+    const T *ph = minv ? w.phat : w.p, *sh = minv ? w.shat : w.s;
+    with_flags([&](auto AL) { launch(bicg_half_kernel<T, AL>, st, x, ph, w.s, w.t, n, w.part_b, w.part_a, w.cell, k, rtol); }, al);
+    with_flags([&](auto PRE, auto AL) { launch(bicg_update_kernel<T, PRE, AL>, st, x, w.r, ph, sh, w.s, w.t, w.rhat, n, w.part_a, w.part_b, w.cell, k); }, minv != nullptr, al);
+    with_flags([&](auto PRE, auto AL) { launch(bicg_direction_kernel<T, PRE, AL || !PRE>, st, w.p, w.phat, w.r, w.v, minv, n, w.part_b, w.cell, k, rtol); }, minv != nullptr, al);
     return hipGetLastError();
 }
 
-int check_handle(const cvr_handle *h)
+int check_handle(const cvr_handle *h) { return check_square_preprocessed(h, "cvr_bicgstab", "BiCGSTAB needs"); }
+
+// cvr_krylov.h's driver with BiCGSTAB's start, step and cell
+template <typename T>
+int bicgstab_solve(cvr_handle *h, const T *b, T *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
-    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_bicgstab before cvr_preprocess");
-    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "BiCGSTAB needs a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    const long long n = h->info.nrows;
+    const size_t    vb = sizeof(T) * (size_t)n;
+    const T        *minv = static_cast<const T *>(opt->minv_dev);
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+
+    Arena        a;
+    const size_t nx = x_ext_bytes(h), ny = y_ext_bytes(h), nh = minv ? nx : 0, npart = sizeof(double) * 2 * kBlocks;
+    const size_t op = a.add(nx), os = a.add(nx), ophat = a.add(nh), oshat = a.add(nh), ov = a.add(ny), ot = a.add(ny), orr = a.add(ny), orhat = a.add(vec_bytes(h));
+    const size_t oa = a.add(npart), ob = a.add(npart), ocell = a.add(sizeof(BiCell));
+    HIP_TRY(a.alloc());
+    const Workspace<T> w{a.at<T>(op), a.at<T>(os), minv ? a.at<T>(ophat) : nullptr, minv ? a.at<T>(oshat) : nullptr, a.at<T>(ov), a.at<T>(ot), a.at<T>(orr), a.at<T>(orhat),
+                         a.at<double>(oa), a.at<double>(ob), a.at<BiCell>(ocell)};
+    if (const int rc = a.begin(st)) return rc;
+
+    // the pad slots of the SpMV inputs; p = x0 for the moment, r = b; r = b - A x0; then r^, p, p^ and the start's sums
+    for (T *q : {w.p, w.s, w.phat, w.shat})
+        if (q)
+            if (const int rc = zero_pad_slot(q, vb, sizeof(T), st)) return rc;
+    if (const int rc = start_residual(h, w.p, w.r, x, b, n, st)) return rc;
+    int spmvs = 1;
+    with_flags([&](auto PRE, auto AL) { launch(bicg_init_kernel<T, PRE, AL>, st, b, minv, w.r, w.rhat, w.p, w.phat, n, w.part_b); }, minv != nullptr, al);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(bicg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part_b, opt->rtol, w.cell);
+    HIP_TRY(hipGetLastError());
+
+    const T  *ph = minv ? w.phat : w.p, *sh = minv ? w.shat : w.s;
+    BiCell    cell{};
+    const int rc = run_batches(
+        opt,
+        [&](int k) -> int {
+            HIP_TRY(run_spmv(h, ph, w.v, st));
+            HIP_TRY(launch_first_half(w, minv, n, al, k, st));
+            HIP_TRY(run_spmv(h, sh, w.t, st));
+            HIP_TRY(launch_second_half(w, x, minv, n, al, k, opt->rtol, st));
+            spmvs += 2;
+            return CVR_OK;
+        },
+        [&](int, bool *stopped) -> int {
+            if (const int rc = read_cell(&cell, w.cell, sizeof(cell), st)) return rc;
+            *stopped = cell.stop || cell.half;
+            return CVR_OK;
+        });
+    if (rc) return rc;
+    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
     return CVR_OK;
 }
 
@@ -354,83 +370,8 @@ int bicgstab_device(cvr_handle *h, const void *b, void *x, const cvr_cg_options 
     if (const int rc = check_handle(h)) return rc;
     Range range("cvr_bicgstab_device");
     HIP_TRY(hipSetDevice(h->device));
-    const long long n = h->info.nrows;
-    const bool      f32 = h->vsz == 4;
-    const void     *minv = opt->minv_dev;
-    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
-    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
-
-    Workspace w;
-    {
-        auto         up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t nx = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.x_elems, n + 1), 1));
-        const size_t ny = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
-        const size_t nh = minv ? nx : 0, nn = up(h->vsz * (size_t)std::max<long long>(n, 1)), npart = up(sizeof(double) * 2 * kBlocks);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.arena), 2 * nx + 2 * nh + 3 * ny + nn + 2 * npart + up(sizeof(BiCell))));
-        uint8_t *a = w.arena;
-        w.p = a; a += nx;
-        w.s = a; a += nx;
-        w.phat = minv ? a : nullptr; a += nh;
-        w.shat = minv ? a : nullptr; a += nh;
-        w.v = a; a += ny;
-        w.t = a; a += ny;
-        w.r = a; a += ny;
-        w.rhat = a; a += nn;
-        w.part_a = reinterpret_cast<double *>(a); a += npart;
-        w.part_b = reinterpret_cast<double *>(a); a += npart;
-        w.cell = reinterpret_cast<BiCell *>(a);
-    }
-    HIP_TRY(hipEventCreate(&w.e0));
-    HIP_TRY(hipEventCreate(&w.e1));
-    HIP_TRY(hipEventRecord(w.e0, st));
-
-    // the pad slots of the SpMV inputs; p = x0 for the moment, r = b; r = b - A x0; then r^, p, p^ and the start's sums
-    const size_t vb = h->vsz * (size_t)n;
-    for (void *q : {w.p, w.s, w.phat, w.shat})
-        if (q) HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(q) + vb, 0, h->vsz, st));
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(w.p, x, vb, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(w.r, b, vb, hipMemcpyDeviceToDevice, st));
-    }
-    { const int rc = spmv_scaled_enqueue(h, -1.0, w.p, 1.0, w.r, st); if (rc) return rc; }
-    int spmvs = 1;
-    HIP_TRY(f32 ? launch_init<float>(w, b, minv, n, al, st) : launch_init<double>(w, b, minv, n, al, st));
-    hipLaunchKernelGGL(bicg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part_b, opt->rtol, w.cell);
-    HIP_TRY(hipGetLastError());
-
-    const void *ph = minv ? w.phat : w.p, *sh = minv ? w.shat : w.s;
-    BiCell      cell{};
-    for (int done = 0;;) {
-        const int batch = std::min(every, opt->max_iters - done);
-        for (int i = 0; i < batch; i++) {
-            HIP_TRY(run_spmv(h, ph, w.v, st));
-            HIP_TRY(f32 ? launch_first_half<float>(w, minv, n, al, done + i, st) : launch_first_half<double>(w, minv, n, al, done + i, st));
-            HIP_TRY(run_spmv(h, sh, w.t, st));
-            HIP_TRY(f32 ? launch_second_half<float>(w, x, minv, n, al, done + i, opt->rtol, st) : launch_second_half<double>(w, x, minv, n, al, done + i, opt->rtol, st));
-            spmvs += 2;
-        }
-        done += batch;
-        HIP_TRY(hipMemcpyAsync(&cell, w.cell, sizeof(cell), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (cell.stop || cell.half || done >= opt->max_iters) break;
-    }
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    HIP_TRY(hipEventRecord(w.e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
-    memset(res, 0, sizeof(*res));
-    res->iterations = cell.iters;
-    res->status = cell.status;
-    res->spmv_count = spmvs;
-    res->residual_norm = cell.rnorm;
-    res->b_norm = cell.bnorm;
-    res->seconds = (double)ms * 1e-3;
-    return CVR_OK;
+    return with_value_type(h, [&](auto t) { return bicgstab_solve(h, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
 }
-
-#undef CVR_BICG_PRE_AL
-#undef CVR_BICG_LAUNCH
 
 }  // namespace
 
@@ -446,17 +387,7 @@ int cvr_bicgstab(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_o
 {
     if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
     if (const int rc = check_handle(h)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t vb = h->vsz * (size_t)h->info.nrows;          // the handle's own vectors carry b and x: d_x has ncols + 1 values, d_y at least nrows
-    if (vb) {
-        HIP_TRY(hipMemcpyAsync(h->d_x, x_host, vb, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->d_y, b_host, vb, hipMemcpyHostToDevice, h->stream));
-    }
-    const int rc = bicgstab_device(h, h->d_y, h->d_x, opt, res, h->stream);
-    if (rc) return rc;
-    if (vb) HIP_TRY(hipMemcpyAsync(x_host, h->d_x, vb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return CVR_OK;
+    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return bicgstab_device(h, b, x, opt, res, st); });
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // per thread, lanes by butterfly, wavefronts in order, workgroups' partials by a fixed tree again); no atomics, so a call gives the same bits every time.
 // The scalars that outlive a kernel sit in a state cell (CgCell) that workgroup 0 writes: a kernel that finds the stop records it there and every later
 // kernel of the batch returns without writing -- the result does not depend on how many steps the host enqueues between two read-backs.
+// The host side is cvr_krylov.h's driver: this file adds the cell, the kernels, the step and the read-back.
 // (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void cg_check_kernel(const double *__rest
     if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
     // (an Inf in b makes both norms infinite, and Inf <= rtol * Inf holds: a residual that is not finite never counts as converged -- step 0 then
     // finds p . q not finite and records the breakdown)
-    else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= 1.7976931348623157e308) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
+    else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= kDblMax) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
     *cell = c;
 }
 
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(T *__restrict__ x, 
     double pq[1];
     sum_partials<1>(part_pq, pq, shp);
     if (stopped) return;
-    if (!(pq[0] > 0) || !(pq[0] <= 1.7976931348623157e308)) {
+    if (!(pq[0] > 0) || !(pq[0] <= kDblMax)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { cell->status = CVR_CG_BREAKDOWN; cell->stop = 1; }
         return;
     }
@@ -171,118 +172,78 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(T *__restrict__ 
     }
 }
 
-// the library's buffers of one call, one allocation: p (x_ext), q and r (y_ext each: r takes the scaled product), z, the partial sums, the cell
+// the library's buffers of one call: p (x_ext), q and r (y_ext each: r takes the scaled product), z, the partial sums, the cell
+template <typename T>
 struct Workspace {
-    uint8_t   *arena = nullptr;
-    void      *p = nullptr, *q = nullptr, *r = nullptr, *z = nullptr;
-    double    *part_pq = nullptr, *part = nullptr;
-    CgCell    *cell = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Workspace()
-    {
-        if (arena) (void)hipFree(arena);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
+    T      *p, *q, *r, *z;
+    double *part_pq, *part;
+    CgCell *cell;
 };
 
+// the three vector launches of step k (the SpMV q = A p is enqueued in front of them); without a preconditioner z is r
 template <typename T>
-hipError_t launch_init(const Workspace &w, const void *b, const void *minv, long long n, bool al, hipStream_t st)
+hipError_t launch_step(const Workspace<T> &w, T *x, const T *minv, long long n, bool al, int k, double rtol, hipStream_t st)
 {
-#define CVR_CG_INIT(PRE, AL) hipLaunchKernelGGL((cg_init_kernel<T, PRE, AL>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<const T *>(b), static_cast<const T *>(minv), \
-                                                static_cast<const T *>(w.r), static_cast<T *>(w.z), static_cast<T *>(w.p), n, w.part)
-    if (minv) { if (al) CVR_CG_INIT(true, true); else CVR_CG_INIT(true, false); }
-    else      { if (al) CVR_CG_INIT(false, true); else CVR_CG_INIT(false, false); }
-#undef CVR_CG_INIT
+    launch(cg_pq_kernel<T>, st, w.p, w.q, n, w.part_pq, w.cell);
+    with_flags([&](auto PRE, auto AL) { launch(cg_update_kernel<T, PRE, AL>, st, x, w.r, w.z, w.p, w.q, minv, n, w.part_pq, w.part, w.cell, k); }, minv != nullptr, al);
+    with_flags([&](auto PRE) { launch(cg_direction_kernel<T, PRE>, st, w.p, PRE ? w.z : w.r, n, w.part, w.cell, k, rtol); }, minv != nullptr);
     return hipGetLastError();
 }
 
-// the three vector launches of step k (the SpMV q = A p is enqueued in front of them)
+// cvr_krylov.h's driver with CG's start, step and cell
 template <typename T>
-hipError_t launch_step(const Workspace &w, void *x, const void *minv, long long n, bool al, int k, double rtol, hipStream_t st)
+int cg_solve(cvr_handle *h, const T *b, T *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
-    hipLaunchKernelGGL((cg_pq_kernel<T>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<const T *>(w.p), static_cast<const T *>(w.q), n, w.part_pq, w.cell);
-#define CVR_CG_UPDATE(PRE, AL) hipLaunchKernelGGL((cg_update_kernel<T, PRE, AL>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(x), static_cast<T *>(w.r), \
-                                                  static_cast<T *>(w.z), static_cast<const T *>(w.p), static_cast<const T *>(w.q), static_cast<const T *>(minv), n, w.part_pq, w.part, w.cell, k)
-    if (minv) { if (al) CVR_CG_UPDATE(true, true); else CVR_CG_UPDATE(true, false); }
-    else      { if (al) CVR_CG_UPDATE(false, true); else CVR_CG_UPDATE(false, false); }
-#undef CVR_CG_UPDATE
-    if (minv) hipLaunchKernelGGL((cg_direction_kernel<T, true>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.z), n, w.part, w.cell, k, rtol);
-    else hipLaunchKernelGGL((cg_direction_kernel<T, false>), dim3(kBlocks), dim3(kThreads), 0, st, static_cast<T *>(w.p), static_cast<const T *>(w.r), n, w.part, w.cell, k, rtol);
-    return hipGetLastError();
+    const long long n = h->info.nrows;
+    const size_t    vb = sizeof(T) * (size_t)n;
+    const T        *minv = static_cast<const T *>(opt->minv_dev);
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+
+    Arena        a;
+    const size_t op = a.add(x_ext_bytes(h)), oq = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h)), oz = a.add(minv ? vec_bytes(h) : 0);
+    const size_t opq = a.add(sizeof(double) * kBlocks), opart = a.add(sizeof(double) * 3 * kBlocks), ocell = a.add(sizeof(CgCell));
+    HIP_TRY(a.alloc());
+    const Workspace<T> w{a.at<T>(op), a.at<T>(oq), a.at<T>(orr), minv ? a.at<T>(oz) : nullptr, a.at<double>(opq), a.at<double>(opart), a.at<CgCell>(ocell)};
+    if (const int rc = a.begin(st)) return rc;
+
+    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then z, p and the start's sums
+    if (const int rc = zero_pad_slot(w.p, vb, sizeof(T), st)) return rc;
+    if (const int rc = start_residual(h, w.p, w.r, x, b, n, st)) return rc;
+    int spmvs = 1;
+    with_flags([&](auto PRE, auto AL) { launch(cg_init_kernel<T, PRE, AL>, st, b, minv, w.r, w.z, w.p, n, w.part); }, minv != nullptr, al);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, minv ? 1 : 0, opt->rtol, w.cell);
+    HIP_TRY(hipGetLastError());
+
+    CgCell cell{};
+    const int rc = run_batches(
+        opt,
+        [&](int k) -> int {
+            HIP_TRY(run_spmv(h, w.p, w.q, st));
+            spmvs++;
+            HIP_TRY(launch_step(w, x, minv, n, al, k, opt->rtol, st));
+            return CVR_OK;
+        },
+        [&](int, bool *stopped) -> int {
+            if (const int rc = read_cell(&cell, w.cell, sizeof(cell), st)) return rc;
+            *stopped = cell.stop != 0;
+            return CVR_OK;
+        });
+    if (rc) return rc;
+    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
+    return CVR_OK;
 }
 
 // behind the argument checks
 int cg_device(cvr_handle *h, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
-    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg before cvr_preprocess");
-    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    if (const int rc = check_square_preprocessed(h, "cvr_cg", "conjugate gradients need")) return rc;
     Range range("cvr_cg_device");
     HIP_TRY(hipSetDevice(h->device));
-    const long long n = h->info.nrows;
-    const bool      f32 = h->vsz == 4;
-    const void     *minv = opt->minv_dev;
-    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
-    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
-
-    Workspace w;
-    {
-        auto         up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t np = up(h->vsz * (size_t)std::max<int64_t>(h->info.x_elems, 1)), ny = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
-        const size_t nz = minv ? up(h->vsz * (size_t)std::max<long long>(n, 1)) : 0, npq = up(sizeof(double) * kBlocks), npart = up(sizeof(double) * 3 * kBlocks);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.arena), np + 2 * ny + nz + npq + npart + up(sizeof(CgCell))));
-        uint8_t *a = w.arena;
-        w.p = a; a += np;
-        w.q = a; a += ny;
-        w.r = a; a += ny;
-        w.z = minv ? a : nullptr; a += nz;
-        w.part_pq = reinterpret_cast<double *>(a); a += npq;
-        w.part = reinterpret_cast<double *>(a); a += npart;
-        w.cell = reinterpret_cast<CgCell *>(a);
-    }
-    HIP_TRY(hipEventCreate(&w.e0));
-    HIP_TRY(hipEventCreate(&w.e1));
-    HIP_TRY(hipEventRecord(w.e0, st));
-
-    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then z, p and the start's sums
-    const size_t vb = h->vsz * (size_t)n;
-    HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.p) + vb, 0, h->vsz, st));
-    if (n) {
-        HIP_TRY(hipMemcpyAsync(w.p, x, vb, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(w.r, b, vb, hipMemcpyDeviceToDevice, st));
-    }
-    { const int rc = spmv_scaled_enqueue(h, -1.0, w.p, 1.0, w.r, st); if (rc) return rc; }
-    int spmvs = 1;
-    HIP_TRY(f32 ? launch_init<float>(w, b, minv, n, al, st) : launch_init<double>(w, b, minv, n, al, st));
-    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, minv ? 1 : 0, opt->rtol, w.cell);
-    HIP_TRY(hipGetLastError());
-
-    CgCell cell{};
-    for (int done = 0;;) {
-        const int batch = std::min(every, opt->max_iters - done);
-        for (int i = 0; i < batch; i++) {
-            HIP_TRY(run_spmv(h, w.p, w.q, st));
-            spmvs++;
-            HIP_TRY(f32 ? launch_step<float>(w, x, minv, n, al, done + i, opt->rtol, st) : launch_step<double>(w, x, minv, n, al, done + i, opt->rtol, st));
-        }
-        done += batch;
-        HIP_TRY(hipMemcpyAsync(&cell, w.cell, sizeof(cell), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (cell.stop || done >= opt->max_iters) break;
-    }
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    HIP_TRY(hipEventRecord(w.e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
-    memset(res, 0, sizeof(*res));
-    res->iterations = cell.iters;
-    res->status = cell.status;
-    res->spmv_count = spmvs;
-    res->residual_norm = cell.rnorm;
-    res->b_norm = cell.bnorm;
-    res->seconds = (double)ms * 1e-3;
-    return CVR_OK;
+    return with_value_type(h, [&](auto t) { return cg_solve(h, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
 }
 
 }  // namespace
@@ -307,19 +268,8 @@ int cvr_cg_device(cvr_handle *h, const void *b_dev, void *x_dev, const cvr_cg_op
 int cvr_cg(cvr_handle *h, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res)
 {
     if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
-    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg before cvr_preprocess");
-    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t vb = h->vsz * (size_t)h->info.nrows;          // the handle's own vectors carry b and x: d_x has ncols + 1 values, d_y at least nrows
-    if (vb) {
-        HIP_TRY(hipMemcpyAsync(h->d_x, x_host, vb, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->d_y, b_host, vb, hipMemcpyHostToDevice, h->stream));
-    }
-    const int rc = cg_device(h, h->d_y, h->d_x, opt, res, h->stream);
-    if (rc) return rc;
-    if (vb) HIP_TRY(hipMemcpyAsync(x_host, h->d_x, vb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return CVR_OK;
+    if (const int rc = check_square_preprocessed(h, "cvr_cg", "conjugate gradients need")) return rc;
+    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return cg_device(h, b, x, opt, res, st); });
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 // unrolled over the kSpmmBlock columns there can be, so a column's accumulators and scalars are registers; nvec itself is a runtime argument.
 // Every column has its own state cell.  A column that has stopped is not written any more (its bit in the kernels' `live` mask is clear; its
 // values are still loaded and computed with where they share a sub-block with a live column, and dropped); the others go on.
+// The host side is cvr_krylov.h's driver: this file adds the cells, the kernels, the step and the read-back of all columns.
 #include "cvr_krylov.h"
 
 using namespace cvrh;
@@ -18,7 +19,6 @@ namespace {
 
 constexpr int kCols = cvr::kSpmmBlock;          // columns per call
 constexpr int kSets = 3;                        // partial-sum sets per column in `part`: column c's begin at part + c * kSets * kBlocks
-constexpr double kDblMax = 1.7976931348623157e308;
 
 // a column's state cell: cvr_cg.hip's CgCell, member for member
 struct CgCell {
@@ -272,64 +272,34 @@ __global__ __launch_bounds__(kThreads) void cgm_direction_kernel(T *__restrict__
     }
 }
 
-// the library's blocks of one call, one allocation: P (x_ext rows, ld = nvec), Q and R (y_ext rows each), Z, the partial sums, the cells
+// the library's blocks of one call: P (x_ext rows, ld = nvec), Q and R (y_ext rows each), Z, the partial sums, the cells
+template <typename T>
 struct Workspace {
-    uint8_t   *arena = nullptr;
-    void      *p = nullptr, *q = nullptr, *r = nullptr, *z = nullptr;
-    double    *part_pq = nullptr, *part = nullptr;
-    CgCell    *cells = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Workspace()
-    {
-        if (arena) (void)hipFree(arena);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
+    T      *p, *q, *r, *z;
+    double *part_pq, *part;
+    CgCell *cells;
 };
 
-// what the vector launches of a call share
+// what the vector launches of a call share.  lv: the library's blocks take 16-byte packets; al: so do the caller's
+template <typename T>
 struct Call {
-    const void *b; long long ldb;
-    void       *x; long long ldx;
-    const void *minv;
-    long long   n;
-    int         nvec;
-    bool        lv, al;
-    double      rtol;
+    const T  *b; long long ldb;
+    T        *x; long long ldx;
+    const T  *minv;
+    long long n;
+    int       nvec;
+    bool      lv, al;
+    double    rtol;
 };
 
-const dim3 kGrid(kBlocks), kBlock(kThreads);
-
+// the three vector launches of step k (the product Q = A P is enqueued in front of them); without a preconditioner z is r
 template <typename T>
-hipError_t launch_init(const Workspace &w, const Call &c, hipStream_t st)
+hipError_t launch_step(const Workspace<T> &w, const Call<T> &c, int k, hipStream_t st)
 {
-#define CVR_CGM_INIT(PRE, LV, AL) hipLaunchKernelGGL((cgm_init_kernel<T, PRE, LV, AL>), kGrid, kBlock, 0, st, static_cast<const T *>(c.b), c.ldb, static_cast<const T *>(c.minv), \
-                                                     static_cast<const T *>(w.q), static_cast<T *>(w.r), static_cast<T *>(w.z), static_cast<T *>(w.p), c.n, c.nvec, w.part)
-#define CVR_CGM_INIT2(PRE) do { if (c.lv) { if (c.al) CVR_CGM_INIT(PRE, true, true); else CVR_CGM_INIT(PRE, true, false); } \
-                                else      { if (c.al) CVR_CGM_INIT(PRE, false, true); else CVR_CGM_INIT(PRE, false, false); } } while (0)
-    if (c.minv) CVR_CGM_INIT2(true); else CVR_CGM_INIT2(false);
-#undef CVR_CGM_INIT2
-#undef CVR_CGM_INIT
-    return hipGetLastError();
-}
-
-// the three vector launches of step k (the product Q = A P is enqueued in front of them)
-template <typename T>
-hipError_t launch_step(const Workspace &w, const Call &c, int k, hipStream_t st)
-{
-    if (c.lv) hipLaunchKernelGGL((cgm_pq_kernel<T, true>), kGrid, kBlock, 0, st, static_cast<const T *>(w.p), static_cast<const T *>(w.q), c.n, c.nvec, w.part_pq, w.cells);
-    else      hipLaunchKernelGGL((cgm_pq_kernel<T, false>), kGrid, kBlock, 0, st, static_cast<const T *>(w.p), static_cast<const T *>(w.q), c.n, c.nvec, w.part_pq, w.cells);
-#define CVR_CGM_UPDATE(PRE, LV, AL) hipLaunchKernelGGL((cgm_update_kernel<T, PRE, LV, AL>), kGrid, kBlock, 0, st, static_cast<T *>(c.x), c.ldx, static_cast<T *>(w.r), static_cast<T *>(w.z), \
-                                                       static_cast<const T *>(w.p), static_cast<const T *>(w.q), static_cast<const T *>(c.minv), c.n, c.nvec, w.part_pq, w.part, w.cells, k)
-#define CVR_CGM_UPDATE2(PRE) do { if (c.lv) { if (c.al) CVR_CGM_UPDATE(PRE, true, true); else CVR_CGM_UPDATE(PRE, true, false); } \
-                                  else      { if (c.al) CVR_CGM_UPDATE(PRE, false, true); else CVR_CGM_UPDATE(PRE, false, false); } } while (0)
-    if (c.minv) CVR_CGM_UPDATE2(true); else CVR_CGM_UPDATE2(false);
-#undef CVR_CGM_UPDATE2
-#undef CVR_CGM_UPDATE
-#define CVR_CGM_DIR(PRE, LV, Z) hipLaunchKernelGGL((cgm_direction_kernel<T, PRE, LV>), kGrid, kBlock, 0, st, static_cast<T *>(w.p), static_cast<const T *>(Z), c.n, c.nvec, w.part, w.cells, k, c.rtol)
-    if (c.minv) { if (c.lv) CVR_CGM_DIR(true, true, w.z); else CVR_CGM_DIR(true, false, w.z); }
-    else        { if (c.lv) CVR_CGM_DIR(false, true, w.r); else CVR_CGM_DIR(false, false, w.r); }
-#undef CVR_CGM_DIR
+    with_flags([&](auto LV) { launch(cgm_pq_kernel<T, LV>, st, w.p, w.q, c.n, c.nvec, w.part_pq, w.cells); }, c.lv);
+    with_flags([&](auto PRE, auto LV, auto AL) { launch(cgm_update_kernel<T, PRE, LV, AL>, st, c.x, c.ldx, w.r, w.z, w.p, w.q, c.minv, c.n, c.nvec, w.part_pq, w.part, w.cells, k); },
+               c.minv != nullptr, c.lv, c.al);
+    with_flags([&](auto PRE, auto LV) { launch(cgm_direction_kernel<T, PRE, LV>, st, w.p, PRE ? w.z : w.r, c.n, c.nvec, w.part, w.cells, k, c.rtol); }, c.minv != nullptr, c.lv);
     return hipGetLastError();
 }
 
@@ -344,8 +314,7 @@ int check_block_args(int32_t nvec, int64_t ldb, int64_t ldx)
 // what is asked of the handle; single: one vector of stride 1, which goes through run_spmv on any layout
 int check_handle(const cvr_handle *h, int32_t nvec, bool single)
 {
-    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_cg_multi before cvr_preprocess");
-    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "conjugate gradients need a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    if (const int rc = check_square_preprocessed(h, "cvr_cg_multi", "conjugate gradients need")) return rc;
     if (single) return CVR_OK;
     if (!cvr_spmm_supported(h)) return fail(CVR_ERR_STATE, "cvr_cg_multi: this handle's image is not the plain layout; create it with cvr_options.nvec >= 2 for several right-hand sides");
     if ((uint64_t)(h->info.ncols + 1) * (uint64_t)nvec * h->vsz > 0xffffffffull)
@@ -354,7 +323,8 @@ int check_handle(const cvr_handle *h, int32_t nvec, bool single)
 }
 
 // Q = A P for all columns
-int product(cvr_handle *h, bool single, const Workspace &w, int nvec, hipStream_t st)
+template <typename T>
+int product(cvr_handle *h, bool single, const Workspace<T> &w, int nvec, hipStream_t st)
 {
     if (single) {
         HIP_TRY(run_spmv(h, w.p, w.q, st));
@@ -366,6 +336,60 @@ int product(cvr_handle *h, bool single, const Workspace &w, int nvec, hipStream_
     return CVR_OK;
 }
 
+// cvr_krylov.h's driver with the block's start, step and cells
+template <typename T>
+int cg_multi_solve(cvr_handle *h, bool single, const T *B, int64_t ldb, T *X, int64_t ldx, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    const long long n = h->info.nrows;
+    Call<T>         c{B, ldb, X, ldx, static_cast<const T *>(opt->minv_dev), n, nvec, false, false, opt->rtol};
+    c.lv = nvec % kPack<T> == 0;
+    c.al = (((uintptr_t)B | (uintptr_t)X | (uintptr_t)c.minv) & 15u) == 0 && ldb % kPack<T> == 0 && ldx % kPack<T> == 0;
+
+    Arena        a;
+    const size_t op = a.add(x_ext_bytes(h, nvec)), oq = a.add(y_ext_bytes(h, nvec)), orr = a.add(y_ext_bytes(h, nvec)), oz = a.add(c.minv ? vec_bytes(h, nvec) : 0);
+    const size_t opq = a.add(sizeof(double) * kCols * kBlocks), opart = a.add(sizeof(double) * kCols * kSets * kBlocks), ocells = a.add(sizeof(CgCell) * kCols);
+    HIP_TRY(a.alloc());
+    const Workspace<T> w{a.at<T>(op), a.at<T>(oq), a.at<T>(orr), c.minv ? a.at<T>(oz) : nullptr, a.at<double>(opq), a.at<double>(opart), a.at<CgCell>(ocells)};
+    if (const int rc = a.begin(st)) return rc;
+
+    // P = X0 for the moment (with its zero row), Q = A X0; then R, Z, P and the start's sums
+    launch(cgm_start_kernel<T>, st, X, (long long)ldx, w.p, n, nvec);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = product(h, single, w, nvec, st)) return rc;
+    int spmms = 1;
+    with_flags([&](auto PRE, auto LV, auto AL) { launch(cgm_init_kernel<T, PRE, LV, AL>, st, c.b, c.ldb, c.minv, w.q, w.r, w.z, w.p, c.n, c.nvec, w.part); }, c.minv != nullptr, c.lv, c.al);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cgm_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, c.minv ? 1 : 0, opt->rtol, nvec, w.cells);
+    HIP_TRY(hipGetLastError());
+
+    CgCell    cells[kCols] = {};
+    const int rc = run_batches(
+        opt,
+        [&](int k) -> int {
+            if (const int rc = product(h, single, w, nvec, st)) return rc;
+            spmms++;
+            HIP_TRY(launch_step(w, c, k, st));
+            return CVR_OK;
+        },
+        [&](int, bool *stopped) -> int {          // stopped: every column has
+            if (const int rc = read_cell(cells, w.cells, sizeof(CgCell) * (size_t)nvec, st)) return rc;
+            *stopped = true;
+            for (int j = 0; j < nvec; j++) *stopped = *stopped && cells[j].stop;
+            return CVR_OK;
+        });
+    if (rc) return rc;
+    uint32_t zero = 0;
+    for (int j = 0; j < nvec; j++) if (cells[j].zero_x) zero |= 1u << j;
+    if (zero && n) {
+        launch(cgm_zero_kernel<T>, st, X, (long long)ldx, n, nvec, zero);
+        HIP_TRY(hipGetLastError());
+    }
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    for (int j = 0; j < nvec; j++) fill_result(&res[j], cells[j].iters, cells[j].status, spmms, cells[j].rnorm, cells[j].bnorm, seconds);
+    return CVR_OK;
+}
+
 // behind the argument checks
 int cg_multi_device(cvr_handle *h, const void *B, int64_t ldb, void *X, int64_t ldx, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
@@ -373,80 +397,9 @@ int cg_multi_device(cvr_handle *h, const void *B, int64_t ldb, void *X, int64_t 
     if (const int rc = check_handle(h, nvec, single)) return rc;
     Range range("cvr_cg_multi_device");
     HIP_TRY(hipSetDevice(h->device));
-    const long long n = h->info.nrows;
-    const bool      f32 = h->vsz == 4;
-    const int       pack = 16 / (int)h->vsz;
-    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
-    Call            c{B, ldb, X, ldx, opt->minv_dev, n, nvec, false, false, opt->rtol};
-    c.lv = nvec % pack == 0;
-    c.al = (((uintptr_t)B | (uintptr_t)X | (uintptr_t)c.minv) & 15u) == 0 && ldb % pack == 0 && ldx % pack == 0;
-
-    Workspace w;
-    {
-        auto         up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t row = h->vsz * (size_t)nvec;
-        const size_t np = up(row * (size_t)std::max<int64_t>(h->info.x_elems, n + 1)), ny = up(row * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
-        const size_t nz = c.minv ? up(row * (size_t)std::max<long long>(n, 1)) : 0, npq = up(sizeof(double) * kCols * kBlocks), npart = up(sizeof(double) * kCols * kSets * kBlocks);
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&w.arena), np + 2 * ny + nz + npq + npart + up(sizeof(CgCell) * kCols)));
-        uint8_t *a = w.arena;
-        w.p = a; a += np;
-        w.q = a; a += ny;
-        w.r = a; a += ny;
-        w.z = c.minv ? a : nullptr; a += nz;
-        w.part_pq = reinterpret_cast<double *>(a); a += npq;
-        w.part = reinterpret_cast<double *>(a); a += npart;
-        w.cells = reinterpret_cast<CgCell *>(a);
-    }
-    HIP_TRY(hipEventCreate(&w.e0));
-    HIP_TRY(hipEventCreate(&w.e1));
-    HIP_TRY(hipEventRecord(w.e0, st));
-
-    // P = X0 for the moment (with its zero row), Q = A X0; then R, Z, P and the start's sums
-    if (f32) hipLaunchKernelGGL((cgm_start_kernel<float>), kGrid, kBlock, 0, st, static_cast<const float *>(X), (long long)ldx, static_cast<float *>(w.p), n, nvec);
-    else     hipLaunchKernelGGL((cgm_start_kernel<double>), kGrid, kBlock, 0, st, static_cast<const double *>(X), (long long)ldx, static_cast<double *>(w.p), n, nvec);
-    HIP_TRY(hipGetLastError());
-    if (const int rc = product(h, single, w, nvec, st)) return rc;
-    int spmms = 1;
-    HIP_TRY(f32 ? launch_init<float>(w, c, st) : launch_init<double>(w, c, st));
-    hipLaunchKernelGGL(cgm_check_kernel, dim3(1), kBlock, 0, st, w.part, c.minv ? 1 : 0, opt->rtol, nvec, w.cells);
-    HIP_TRY(hipGetLastError());
-
-    CgCell cells[kCols] = {};
-    for (int done = 0;;) {
-        const int batch = std::min(every, opt->max_iters - done);
-        for (int i = 0; i < batch; i++) {
-            if (const int rc = product(h, single, w, nvec, st)) return rc;
-            spmms++;
-            HIP_TRY(f32 ? launch_step<float>(w, c, done + i, st) : launch_step<double>(w, c, done + i, st));
-        }
-        done += batch;
-        HIP_TRY(hipMemcpyAsync(cells, w.cells, sizeof(CgCell) * (size_t)nvec, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        bool all = true;
-        for (int j = 0; j < nvec; j++) all = all && cells[j].stop;
-        if (all || done >= opt->max_iters) break;
-    }
-    uint32_t zero = 0;
-    for (int j = 0; j < nvec; j++) if (cells[j].zero_x) zero |= 1u << j;
-    if (zero && n) {
-        if (f32) hipLaunchKernelGGL((cgm_zero_kernel<float>), kGrid, kBlock, 0, st, static_cast<float *>(X), (long long)ldx, n, nvec, zero);
-        else     hipLaunchKernelGGL((cgm_zero_kernel<double>), kGrid, kBlock, 0, st, static_cast<double *>(X), (long long)ldx, n, nvec, zero);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(w.e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
-    memset(res, 0, sizeof(*res) * (size_t)nvec);
-    for (int j = 0; j < nvec; j++) {
-        res[j].iterations = cells[j].iters;
-        res[j].status = cells[j].status;
-        res[j].spmv_count = spmms;
-        res[j].residual_norm = cells[j].rnorm;
-        res[j].b_norm = cells[j].bnorm;
-        res[j].seconds = (double)ms * 1e-3;
-    }
-    return CVR_OK;
+    return with_value_type(h, [&](auto t) {
+        return cg_multi_solve(h, single, static_cast<const decltype(t) *>(B), ldb, static_cast<decltype(t) *>(X), ldx, nvec, opt, res, st);
+    });
 }
 
 }  // namespace

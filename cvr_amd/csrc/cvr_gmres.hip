@@ -12,6 +12,7 @@
 // own 1024 partials, so its bits do not depend on the group it was formed in.  The scalars sit in a state cell (GmresCell) under BiCell's rule: thread 0
 // of workgroup 0 writes it, and a value a kernel reads is one that a kernel BEFORE it wrote.  The kernel that finds a stop records it and every later
 // kernel of the batch returns without writing, so the result does not depend on how many steps the host enqueues between two read-backs.
+// The host side is cvr_krylov.h's driver: this file adds the cell, the kernels, the step and the read-back (with the owed x in front of it).
 // (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 
@@ -20,7 +21,6 @@ using namespace cvrh::krylov;
 
 namespace {
 
-constexpr double kDblMax = 1.7976931348623157e308;
 constexpr int    kMaxM = CVR_GMRES_MAX_RESTART;
 constexpr int    kGroup = 8;          // columns per compile-time group: 16 accumulator VGPRs in fp64, and the group's packets in flight together
 
@@ -47,8 +47,6 @@ struct GmresCell {
     double    y[kMaxM];
     double    R[kMaxM * kMaxM];
 };
-
-__device__ __forceinline__ bool usable(double v) { return v != 0 && fabs(v) <= kDblMax; }          // neither zero nor Inf nor NaN
 
 // hs[s] = the sum of the s-th set of kBlocks partials for s < nsets, in LDS: sum_partials' tree set by set (the same bits as sum_partials<1> of that set), the
 // same in every workgroup.  Ends behind a barrier.
@@ -381,69 +379,37 @@ __global__ __launch_bounds__(kThreads) void gmres_x_kernel(T *__restrict__ x, co
 #undef CVR_GMRES_GROUPS
 #undef CVR_KRYLOV_PACKETS
 
-// the library's buffers of one call, one allocation: restart + 1 basis vectors and (with a preconditioner) z (x_ext each: SpMV inputs), w and r (y_ext
-// each: r takes the scaled product), the partial sums of the dots (one set per column) and of r . r, b . b and w . w, the cell
+// the library's buffers of one call: restart + 1 basis vectors and (with a preconditioner) z (x_ext each: SpMV inputs), w and r (y_ext each: r takes
+// the scaled product), the partial sums of the dots (one set per column) and of r . r, b . b and w . w, the cell
+template <typename T>
 struct Workspace {
-    uint8_t   *arena = nullptr;
-    void      *V = nullptr, *z = nullptr, *w = nullptr, *r = nullptr;
-    double    *part_h = nullptr, *part_s = nullptr;
-    GmresCell *cell = nullptr;
-    long long  stride = 0;          // of the basis, in values
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Workspace()
-    {
-        if (arena) (void)hipFree(arena);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
+    T         *V, *z, *w, *r;
+    double    *part_h, *part_s;
+    GmresCell *cell;
+    long long  stride;          // of the basis, in values
+    T         *basis(int i) const { return V + (long long)i * stride; }
 };
 
-#define CVR_GMRES_LAUNCH(kernel, ...) hipLaunchKernelGGL((kernel), dim3(kBlocks), dim3(kThreads), 0, st, __VA_ARGS__)
-// the instantiation by preconditioner and alignment of the caller's arrays
-#define CVR_GMRES_PRE_AL(name, ...)                                                                                                             \
-    do {                                                                                                                                        \
-        if (minv) { if (al) CVR_GMRES_LAUNCH((name<T, true, true>), __VA_ARGS__); else CVR_GMRES_LAUNCH((name<T, true, false>), __VA_ARGS__); } \
-        else      { if (al) CVR_GMRES_LAUNCH((name<T, false, true>), __VA_ARGS__); else CVR_GMRES_LAUNCH((name<T, false, false>), __VA_ARGS__); } \
-    } while (0)
-
-template <typename T> const T *basis(const Workspace &w, int i) { return static_cast<const T *>(w.V) + (long long)i * w.stride; }
-template <typename T> T       *basis_mut(const Workspace &w, int i) { return static_cast<T *>(w.V) + (long long)i * w.stride; }
-
-// behind the scaled product r = b - A x: the sums and the cycle's start
+// behind the scaled product r = b - A x: the sums and the cycle's start.  (gmres_rr_kernel reads b, the one caller's array, only at the call's start.)
 template <typename T>
-hipError_t launch_begin(const Workspace &w, const void *b, const void *minv, long long n, bool al, double rtol, bool first, hipStream_t st)
+hipError_t launch_begin(const Workspace<T> &w, const T *b, const T *minv, long long n, bool al, double rtol, bool first, hipStream_t st)
 {
-    if (first) {
-        if (al) CVR_GMRES_LAUNCH((gmres_rr_kernel<T, true, true>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
-        else CVR_GMRES_LAUNCH((gmres_rr_kernel<T, true, false>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
-    } else CVR_GMRES_LAUNCH((gmres_rr_kernel<T, false, true>), static_cast<const T *>(w.r), static_cast<const T *>(b), n, w.part_s, w.cell);
-    CVR_GMRES_PRE_AL(gmres_begin_kernel, static_cast<const T *>(w.r), static_cast<const T *>(minv), basis_mut<T>(w, 0), static_cast<T *>(w.z), n, w.part_s, rtol,
-                     first ? 1 : 0, w.cell);
+    with_flags([&](auto FIRST, auto AL) { launch(gmres_rr_kernel<T, FIRST, AL || !FIRST>, st, w.r, b, n, w.part_s, w.cell); }, first, al);
+    with_flags([&](auto PRE, auto AL) { launch(gmres_begin_kernel<T, PRE, AL>, st, w.r, minv, w.basis(0), w.z, n, w.part_s, rtol, first ? 1 : 0, w.cell); }, minv != nullptr, al);
     return hipGetLastError();
 }
 
 // step k with column j behind w = A z_j: the two Gram-Schmidt passes and the finish
 template <typename T>
-hipError_t launch_step(const Workspace &w, const void *minv, long long n, bool al, int j, int k, int m, int max_iters, double rtol, hipStream_t st)
+hipError_t launch_step(const Workspace<T> &w, const T *minv, long long n, bool al, int j, int k, int m, int max_iters, double rtol, hipStream_t st)
 {
-    const T *V = basis<T>(w, 0);
-    T       *wv = static_cast<T *>(w.w);
-    CVR_GMRES_LAUNCH((gmres_dots_kernel<T>), V, w.stride, wv, n, j + 1, w.part_h, w.cell);
-    CVR_GMRES_LAUNCH((gmres_update_kernel<T, false>), V, w.stride, wv, n, j, w.part_h, w.part_s, w.cell);
-    CVR_GMRES_LAUNCH((gmres_dots_kernel<T>), V, w.stride, wv, n, j + 1, w.part_h, w.cell);
-    CVR_GMRES_LAUNCH((gmres_update_kernel<T, true>), V, w.stride, wv, n, j, w.part_h, w.part_s, w.cell);
-    // (v_(j+1) and z_(j+1) are written only when j + 1 < m: basis vector m is never a column; it carries x into the scaled product)
-    if (minv) {
-        if (al) CVR_GMRES_LAUNCH((gmres_finish_kernel<T, true, true>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
-        else CVR_GMRES_LAUNCH((gmres_finish_kernel<T, true, false>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
-    } else CVR_GMRES_LAUNCH((gmres_finish_kernel<T, false, true>), wv, static_cast<const T *>(minv), basis_mut<T>(w, j + 1), static_cast<T *>(w.z), n, w.part_s, w.cell, j, k, m, max_iters, rtol);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_x(const Workspace &w, void *x, const void *minv, long long n, bool al, int lo, int hi, hipStream_t st)
-{
-    CVR_GMRES_PRE_AL(gmres_x_kernel, static_cast<T *>(x), static_cast<const T *>(minv), basis<T>(w, 0), w.stride, n, w.cell, lo, hi);
+    launch(gmres_dots_kernel<T>, st, w.V, w.stride, w.w, n, j + 1, w.part_h, w.cell);
+    launch(gmres_update_kernel<T, false>, st, w.V, w.stride, w.w, n, j, w.part_h, w.part_s, w.cell);
+    launch(gmres_dots_kernel<T>, st, w.V, w.stride, w.w, n, j + 1, w.part_h, w.cell);
+    launch(gmres_update_kernel<T, true>, st, w.V, w.stride, w.w, n, j, w.part_h, w.part_s, w.cell);
+    // (v_(j+1) and z_(j+1) are written only when j + 1 < m: basis vector m is never a column; it carries x into the scaled product.  minv is the
+    // kernel's one caller's array: without it there is no unaligned form)
+    with_flags([&](auto PRE, auto AL) { launch(gmres_finish_kernel<T, PRE, AL || !PRE>, st, w.w, minv, w.basis(j + 1), w.z, n, w.part_s, w.cell, j, k, m, max_iters, rtol); }, minv != nullptr, al);
     return hipGetLastError();
 }
 
@@ -453,10 +419,79 @@ int check_restart(int32_t restart)
     return CVR_OK;
 }
 
-int check_handle(const cvr_handle *h)
+int check_handle(const cvr_handle *h) { return check_square_preprocessed(h, "cvr_gmres", "GMRES needs"); }
+
+// cvr_krylov.h's driver with GMRES's cycle start, step and cell
+template <typename T>
+int gmres_solve(cvr_handle *h, const T *b, T *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
-    if (!h->converted) return fail(CVR_ERR_STATE, "cvr_gmres before cvr_preprocess");
-    if (h->info.nrows != h->info.ncols) return fail(CVR_ERR_INVALID, "GMRES needs a square matrix (%lld x %lld)", (long long)h->info.nrows, (long long)h->info.ncols);
+    const long long n = h->info.nrows;
+    const size_t    vb = sizeof(T) * (size_t)n;
+    const T        *minv = static_cast<const T *>(opt->minv_dev);
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+
+    Arena        a;
+    const size_t nx = Arena::slot(x_ext_bytes(h));          // a basis vector: whole slots, so the stride is a whole number of values
+    const size_t oV = a.add((size_t)(m + 1) * nx), oz = a.add(minv ? nx : 0), ow = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h));
+    const size_t oh = a.add(sizeof(double) * (size_t)m * kBlocks), os = a.add(sizeof(double) * 2 * kBlocks), ocell = a.add(sizeof(GmresCell));
+    const hipError_t e = a.alloc();
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return fail(CVR_ERR_NOMEM, "cvr_gmres: no device memory for %d basis vectors (%zu bytes)", m + 1, a.total());
+    }
+    HIP_TRY(e);
+    const Workspace<T> w{a.at<T>(oV), minv ? a.at<T>(oz) : nullptr, a.at<T>(ow), a.at<T>(orr), a.at<double>(oh), a.at<double>(os), a.at<GmresCell>(ocell), (long long)(nx / sizeof(T))};
+    if (const int rc = a.begin(st)) return rc;
+
+    // the pad slots of the SpMV inputs; basis vector 1 carries x into the scaled product (it is a column only from step 1 of a cycle on), r = b;
+    // r = b - A x; then the sums, the stop test and v_0
+    for (int i = 0; i <= m; i++)
+        if (const int rc = zero_pad_slot(w.basis(i), vb, sizeof(T), st)) return rc;
+    if (w.z)
+        if (const int rc = zero_pad_slot(w.z, vb, sizeof(T), st)) return rc;
+    auto residual = [&](bool first) -> int {
+        if (const int rc = start_residual(h, w.basis(1), w.r, x, b, n, st)) return rc;
+        HIP_TRY(launch_begin(w, b, minv, n, al, opt->rtol, first, st));
+        return CVR_OK;
+    };
+    if (const int rc = residual(true)) return rc;
+    int spmvs = 1;
+
+    GmresHead hd{};
+    int       x_lo = 0;          // the steps whose finish a gmres_x_kernel has looked at
+    auto form_x = [&](int hi) -> int {
+        if (hi > x_lo) {
+            with_flags([&](auto PRE, auto AL) { launch(gmres_x_kernel<T, PRE, AL>, st, x, minv, w.V, w.stride, n, w.cell, x_lo, hi); }, minv != nullptr, al);
+            HIP_TRY(hipGetLastError());
+        }
+        x_lo = hi;
+        return CVR_OK;
+    };
+    const int rc = run_batches(
+        opt,
+        [&](int k) -> int {
+            const int j = k % m;
+            if (j == 0 && k > 0) {          // the cycle before is full: its x, then the next one from the true residual
+                if (const int rc = form_x(k)) return rc;
+                if (const int rc = residual(false)) return rc;
+                spmvs++;
+            }
+            HIP_TRY(run_spmv(h, minv ? w.z : w.basis(j), w.w, st));
+            HIP_TRY(launch_step(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st));
+            spmvs++;
+            return CVR_OK;
+        },
+        [&](int done, bool *stopped) -> int {
+            if (const int rc = form_x(done)) return rc;
+            if (const int rc = read_cell(&hd, &w.cell->hd, sizeof(hd), st)) return rc;
+            *stopped = hd.stop != 0;
+            return CVR_OK;
+        });
+    if (rc) return rc;
+    if (hd.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    fill_result(res, hd.iters, hd.status, spmvs, hd.rnorm, hd.bnorm, seconds);
     return CVR_OK;
 }
 
@@ -466,103 +501,8 @@ int gmres_device(cvr_handle *h, const void *b, void *x, int m, const cvr_cg_opti
     if (const int rc = check_handle(h)) return rc;
     Range range("cvr_gmres_device");
     HIP_TRY(hipSetDevice(h->device));
-    const long long n = h->info.nrows;
-    const bool      f32 = h->vsz == 4;
-    const void     *minv = opt->minv_dev;
-    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
-    const int       every = opt->check_every > 0 ? opt->check_every : kDefaultCheckEvery;
-
-    Workspace w;
-    size_t    nx = 0;
-    {
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        nx = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.x_elems, n + 1), 1));
-        const size_t ny = up(h->vsz * (size_t)std::max<int64_t>(std::max<int64_t>(h->info.yext_elems, n), 1));
-        const size_t nh = minv ? nx : 0, nph = up(sizeof(double) * (size_t)m * kBlocks), nps = up(sizeof(double) * 2 * kBlocks);
-        const size_t total = (size_t)(m + 1) * nx + nh + 2 * ny + nph + nps + up(sizeof(GmresCell));
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&w.arena), total);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            w.arena = nullptr;
-            return fail(CVR_ERR_NOMEM, "cvr_gmres: no device memory for %d basis vectors (%zu bytes)", m + 1, total);
-        }
-        HIP_TRY(e);
-        uint8_t *a = w.arena;
-        w.V = a; a += (size_t)(m + 1) * nx;
-        w.z = minv ? a : nullptr; a += nh;
-        w.w = a; a += ny;
-        w.r = a; a += ny;
-        w.part_h = reinterpret_cast<double *>(a); a += nph;
-        w.part_s = reinterpret_cast<double *>(a); a += nps;
-        w.cell = reinterpret_cast<GmresCell *>(a);
-        w.stride = (long long)(nx / h->vsz);
-    }
-    HIP_TRY(hipEventCreate(&w.e0));
-    HIP_TRY(hipEventCreate(&w.e1));
-    HIP_TRY(hipEventRecord(w.e0, st));
-
-    // the pad slots of the SpMV inputs; basis vector 1 carries x into the scaled product (it is a column only from step 1 of a cycle on), r = b;
-    // r = b - A x; then the sums, the stop test and v_0
-    const size_t vb = h->vsz * (size_t)n;
-    uint8_t     *xin = static_cast<uint8_t *>(w.V) + nx;
-    for (int i = 0; i <= m; i++) HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.V) + (size_t)i * nx + vb, 0, h->vsz, st));
-    if (w.z) HIP_TRY(hipMemsetAsync(static_cast<uint8_t *>(w.z) + vb, 0, h->vsz, st));
-    auto residual = [&](bool first) -> int {
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(xin, x, vb, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w.r, b, vb, hipMemcpyDeviceToDevice, st));
-        }
-        if (const int rc = spmv_scaled_enqueue(h, -1.0, xin, 1.0, w.r, st)) return rc;
-        HIP_TRY(f32 ? launch_begin<float>(w, b, minv, n, al, opt->rtol, first, st) : launch_begin<double>(w, b, minv, n, al, opt->rtol, first, st));
-        return CVR_OK;
-    };
-    if (const int rc = residual(true)) return rc;
-    int spmvs = 1;
-
-    GmresHead hd{};
-    int       x_lo = 0;          // the steps whose finish a gmres_x_kernel has looked at
-    auto form_x = [&](int hi) -> int {
-        if (hi > x_lo) HIP_TRY(f32 ? launch_x<float>(w, x, minv, n, al, x_lo, hi, st) : launch_x<double>(w, x, minv, n, al, x_lo, hi, st));
-        x_lo = hi;
-        return CVR_OK;
-    };
-    for (int done = 0;;) {
-        const int batch = std::min(every, opt->max_iters - done);
-        for (int i = 0; i < batch; i++) {
-            const int k = done + i, j = k % m;
-            if (j == 0 && k > 0) {          // the cycle before is full: its x, then the next one from the true residual
-                if (const int rc = form_x(k)) return rc;
-                if (const int rc = residual(false)) return rc;
-                spmvs++;
-            }
-            const void *zin = minv ? w.z : static_cast<const void *>(static_cast<const uint8_t *>(w.V) + (size_t)j * nx);
-            HIP_TRY(run_spmv(h, zin, w.w, st));
-            HIP_TRY(f32 ? launch_step<float>(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st) : launch_step<double>(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st));
-            spmvs++;
-        }
-        done += batch;
-        if (const int rc = form_x(done)) return rc;
-        HIP_TRY(hipMemcpyAsync(&hd, &w.cell->hd, sizeof(hd), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (hd.stop || done >= opt->max_iters) break;
-    }
-    if (hd.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    HIP_TRY(hipEventRecord(w.e1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, w.e0, w.e1));
-    memset(res, 0, sizeof(*res));
-    res->iterations = hd.iters;
-    res->status = hd.status;
-    res->spmv_count = spmvs;
-    res->residual_norm = hd.rnorm;
-    res->b_norm = hd.bnorm;
-    res->seconds = (double)ms * 1e-3;
-    return CVR_OK;
+    return with_value_type(h, [&](auto t) { return gmres_solve(h, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), m, opt, res, st); });
 }
-
-#undef CVR_GMRES_PRE_AL
-#undef CVR_GMRES_LAUNCH
 
 }  // namespace
 
@@ -580,17 +520,7 @@ int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, 
     if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
     if (const int rc = check_restart(restart)) return rc;
     if (const int rc = check_handle(h)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t vb = h->vsz * (size_t)h->info.nrows;          // the handle's own vectors carry b and x: d_x has ncols + 1 values, d_y at least nrows
-    if (vb) {
-        HIP_TRY(hipMemcpyAsync(h->d_x, x_host, vb, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->d_y, b_host, vb, hipMemcpyHostToDevice, h->stream));
-    }
-    const int rc = gmres_device(h, h->d_y, h->d_x, restart, opt, res, h->stream);
-    if (rc) return rc;
-    if (vb) HIP_TRY(hipMemcpyAsync(x_host, h->d_x, vb, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return CVR_OK;
+    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return gmres_device(h, b, x, restart, opt, res, st); });
 }
 
 }  // extern "C"
