@@ -88,6 +88,15 @@ class CgResult(C.Structure):
 CG_CONVERGED, CG_MAX_ITERS, CG_BREAKDOWN = 0, 1, 2
 
 
+class PrecondInfo(C.Structure):
+    """cvr_precond_info"""
+    _fields_ = [("n", C.c_int64), ("block_size", C.c_int32), ("is_f32", C.c_int32), ("nblocks", C.c_int64), ("identity_blocks", C.c_int64),
+                ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+PRECOND_MAX_BLOCK = 32      # include/cvr_amd.h: CVR_PRECOND_MAX_BLOCK
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -98,6 +107,7 @@ class MmMatrix(C.Structure):
 SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_count", "cvr_create", "cvr_preprocess",
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
+           "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -154,6 +164,13 @@ def lib():
         L.cvr_bicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_gmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_gmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_precond_block_jacobi.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_int32, C.c_void_p]
+        L.cvr_precond_get_info.argtypes = [C.c_void_p, C.POINTER(PrecondInfo)]
+        L.cvr_precond_export.argtypes = [C.c_void_p, C.c_void_p]
+        L.cvr_precond_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_precond_destroy.argtypes = [C.c_void_p]
+        L.cvr_pcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -418,6 +435,69 @@ class Comm:
             pass
 
 
+class Precond:
+    """A preconditioner the library owns (cvr_precond): built once, applied on the device, handed to CvrMatrix.pcg()."""
+
+    def __init__(self):
+        self._p = C.c_void_p()
+        self.info = PrecondInfo()
+
+    @classmethod
+    def block_jacobi(cls, rp, ci, vals, block_size, device=0):
+        """cvr_precond_block_jacobi from host CSR arrays of a square matrix (n = len(rp) - 1; the type is vals' dtype, float32 or else float64)"""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), block_size, device)
+
+    @classmethod
+    def block_jacobi_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, block_size, is_f32=False, device=0):
+        """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
+        return cls._from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), block_size, device)
+
+    @classmethod
+    def _from_view(cls, view, block_size, device):
+        self = cls()
+        rc = lib().cvr_precond_block_jacobi(C.byref(self._p), C.byref(view), int(block_size), int(device), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_block_jacobi")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        return self
+
+    def export(self):
+        """the inverse blocks W as an array of shape (nblocks, block_size, block_size) of the object's dtype, each block row-major"""
+        bs = self.info.block_size
+        out = np.zeros((self.info.nblocks, bs, bs), dtype=self.dtype)
+        if out.size:
+            rc = lib().cvr_precond_export(self._p, out.ctypes.data)
+            if rc:
+                raise CvrError(rc, "cvr_precond_export")
+        return out
+
+    def apply(self, r_ptr, z_ptr, stream=None):
+        """asynchronous z = M^-1 r on device arrays of n values (cvr_precond_apply_device); r_ptr != z_ptr"""
+        rc = lib().cvr_precond_apply_device(self._p, r_ptr, z_ptr, stream)
+        if rc:
+            raise CvrError(rc, "cvr_precond_apply_device")
+
+    def close(self):
+        if getattr(self, "_p", None) and self._p.value:
+            lib().cvr_precond_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 class CvrMatrix:
     """One matrix (or row shard) resident on one GPU: cvr_create + cvr_preprocess, then spmv()."""
 
@@ -648,6 +728,17 @@ class CvrMatrix:
         pointer.  Returns (x, CgResult)."""
         b, x = self._host_vectors(b, x0)
         res = self._solve("cvr_cg", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b.ctypes.data, x.ctypes.data))
+        return x[: self.nrows], res
+
+    def pcg(self, precond, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, stream=None):
+        """conjugate gradients preconditioned by a Precond object (cvr_pcg_device): z = M^-1 r by its apply in place of a diagonal;
+        the arguments and the CgResult are cg's.  With block_size = 1 the result is bit for bit cg's with minv = the exported W."""
+        return self._solve("cvr_pcg_device", self._cg_options(rtol, max_iters, check_every, None), (precond._p, b_ptr, x_ptr), (stream,))
+
+    def pcg_host(self, precond, b, x0=None, rtol=None, max_iters=None, check_every=0):
+        """the same through host arrays (cvr_pcg): b and the start vector x0 (None: zero) of nrows values.  Returns (x, CgResult)."""
+        b, x = self._host_vectors(b, x0)
+        res = self._solve("cvr_pcg", self._cg_options(rtol, max_iters, check_every, None), (precond._p, b.ctypes.data, x.ctypes.data))
         return x[: self.nrows], res
 
     def cg_multi(self, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):

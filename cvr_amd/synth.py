@@ -161,6 +161,28 @@ def spd_from_pattern(n, rp, ci, c=0.5, dscale=None, dtype=np.float64):
     return n, n, out_rp, cc.astype(np.int32), val.astype(dtype)
 
 
+def block_diag_spd(n, bs, cond=1e3, seed=11, dtype=np.float64):
+    """An exactly block-diagonal symmetric positive definite matrix (the block-Jacobi preconditioner's test family): dense blocks of bs rows (the last
+    one shorter when bs does not divide n), each Q diag(lambda) Q^T with a random orthogonal Q and eigenvalues spread log-uniformly over [1, cond] --
+    both ends in every block, the others drawn per block, so the matrix has about n distinct eigenvalues and plain CG needs many steps while
+    block-Jacobi with the same bs solves it in one.  Symmetric bit for bit.  Returns (n, n, row_ptr, col_idx, vals) like the generators above."""
+    rng = np.random.default_rng(seed)
+    nb = -(-n // bs)
+    q, _ = np.linalg.qr(rng.standard_normal((nb, bs, bs)))
+    lam = cond ** rng.random((nb, bs))
+    lam[:, 0], lam[:, -1] = 1.0, cond
+    blocks = np.einsum("kij,kj,klj->kil", q, lam, q)
+    blocks = 0.5 * (blocks + blocks.transpose(0, 2, 1))
+    rows = np.repeat(np.arange(nb * bs, dtype=np.int64), bs)
+    cols = (rows // bs) * bs + np.tile(np.arange(bs, dtype=np.int64), nb * bs)
+    vals = blocks.reshape(-1)
+    ok = (rows < n) & (cols < n)
+    rows, cols, vals = rows[ok], cols[ok], vals[ok]
+    rp = np.zeros(n + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return n, n, rp, cols.astype(np.int32), vals.astype(dtype)
+
+
 def nonsym_from_pattern(n, rp, ci, c=0.5, rscale=None, seed=3, dtype=np.float64):
     """A nonsymmetric, strictly diagonally dominant matrix from any square pattern (the BiCGSTAB solver's test matrices): W = the pattern as
     it is (not symmetrised) without the diagonal and without duplicates, with seeded weights in [0.5, 1.5) and each row scaled to the absolute

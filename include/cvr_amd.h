@@ -577,6 +577,63 @@ int cvr_gmres_device(cvr_handle *h, const void *b_dev, void *x_dev, int32_t rest
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg.  opt->minv_dev stays a device pointer. */
 int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* ---- a preconditioner the library owns: block-Jacobi, and the conjugate gradients that use it -----------
+ * M = the block diagonal of A in blocks of block_size (1 .. CVR_PRECOND_MAX_BLOCK) rows and columns; the object holds W = M^-1, built once on the
+ * device and applied by a kernel, z = W r.  It is independent of any handle (built from the CSR view, usable by every handle of the same n, type and
+ * device, by several at once) and is not refreshed by cvr_update_values.  T = float or double by csr->is_f32.
+ * CSR input: the view is read literally, as cvr_create reads it, and checked as there (CVR_ERR_INVALID: row_ptr decreasing, a column outside
+ *   [0, ncols), ...).  arrays_on_device 0 or 1: host arrays are copied up once and released before the call returns, device arrays (memory of `device`)
+ *   are read where they lie; row_ptr comes to the host once for the checks, copied on `stream`, which is synchronised before anything else reads the
+ *   arrays: a caller that produced them on `stream` needs no synchronisation of its own.  The matrix must be square.
+ * Blocks: block k covers rows and columns k*bs .. min(n, (k+1)*bs) - 1; nblocks = ceil(n / bs); n = 0 gives 0 blocks and is valid.  Entry (i, j) of a
+ *   block is the fp64 sum of all CSR entries of row i with that column, in CSR order (duplicates are legal); entries outside the blocks are ignored.  A
+ *   short last block is completed with the identity, so cvr_precond_export and the apply always see bs x bs.
+ * Inverse: each block is inverted in fp64 by Gauss-Jordan elimination with partial pivoting (the largest magnitude of the column from the diagonal
+ *   down), rounded once to T and stored; only W is kept.  A block whose elimination meets a pivot that is zero or not finite (an empty row, a NaN, a
+ *   singular block), or whose inverse holds a value that is not finite, becomes the identity block and is counted in identity_blocks; the call still
+ *   succeeds.
+ * Storage: cvr_precond_export returns nblocks * bs * bs values of T, block after block, each row-major, whatever the device layout is (there every
+ *   block lies transposed: the loads of neighbouring rows are contiguous).
+ * Apply, for row i of block k, m = min(bs, n - k*bs) the columns of the block that exist:
+ *     z_i = T(t_0 + t_1 + ... + t_(m-1))   with   t_j = double(W[i][j]) * double(r[k*bs + j]),
+ *   summed left to right starting from t_0 (not from +0), every product and every addition rounded on its own (no fused multiply-add).  The columns
+ *   and rows a short last block was completed with are never touched: no r and no z beyond n.  The kernel runs on the solvers' grid (1024 workgroups
+ *   of 256 threads, a thread over its 16-byte packets of z in order); the result has the same bits every call and for every alignment of r_dev and z_dev.
+ * cvr_precond_block_jacobi enqueues on `stream` (NULL = HIP's null stream), synchronises it and makes `device` current; cvr_precond_apply_device
+ * only enqueues (r_dev and z_dev: n values of T each in the memory of the object's device, r_dev != z_dev, not overlapping) and makes the object's
+ * device current.
+ * Errors.  CVR_ERR_INVALID, before any device work: a null argument; block_size outside 1 .. CVR_PRECOND_MAX_BLOCK; nrows != ncols; r_dev == z_dev.
+ * CVR_ERR_NO_DEVICE: `device` out of range.  CVR_ERR_NOMEM: an allocation failed (nothing is left allocated).  cvr_precond_destroy(NULL) is CVR_OK. */
+typedef struct cvr_precond cvr_precond;
+#define CVR_PRECOND_MAX_BLOCK 32
+typedef struct {
+    int64_t n;
+    int32_t block_size, is_f32;
+    int64_t nblocks, identity_blocks;
+    int32_t device, reserved;
+} cvr_precond_info;
+int cvr_precond_block_jacobi(cvr_precond **out, const cvr_csr_view *csr, int32_t block_size, int32_t device, void *stream);
+int cvr_precond_get_info(const cvr_precond *p, cvr_precond_info *info);
+int cvr_precond_export(const cvr_precond *p, void *blocks_host);
+int cvr_precond_apply_device(const cvr_precond *p, const void *r_dev, void *z_dev, void *stream);
+int cvr_precond_destroy(cvr_precond *p);
+
+/* Conjugate gradients preconditioned by such an object.  Everything cvr_cg_device's text above fixes holds word for word -- the handles, b_dev and
+ * x_dev, the options and the result, r = b - A x by the scaled product, the updates of x, r and p, alpha and beta, the fixed-tree sums, the stop rule,
+ * b == 0, a start within the tolerance, the non-finite cases, check_every, spmv_count, seconds, the ordering on `stream` -- with z = W r by the apply
+ * arithmetic above in place of z = T(minv * r); z is a buffer of the library, allocated per call.  In the sum r.z the thread that owns element i adds
+ * the term double(r_i) * double(z_i), in element order, as cvr_cg_device does.  Four vector launches beside the SpMV per step (z is formed by a launch
+ * of its own between the update and the direction).
+ * The contract that follows: with block_size = 1, x, iterations, status, residual_norm and b_norm are bit for bit what cvr_cg_device returns with
+ * minv_dev = the exported W.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; p null; opt->minv_dev != NULL
+ * (one preconditioner per call): CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols: CVR_ERR_INVALID; then, each
+ * CVR_ERR_INVALID with cvr_last_error naming the mismatch: p's n differs from the handle's nrows, p's type from the handle's, p's device from the
+ * handle's. */
+int cvr_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg */
+int cvr_pcg(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
