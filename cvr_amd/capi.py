@@ -95,6 +95,7 @@ class PrecondInfo(C.Structure):
 
 
 PRECOND_MAX_BLOCK = 32      # include/cvr_amd.h: CVR_PRECOND_MAX_BLOCK
+GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
 class MmMatrix(C.Structure):
@@ -108,6 +109,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
+           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -171,6 +173,10 @@ def lib():
         L.cvr_precond_destroy.argtypes = [C.c_void_p]
         L.cvr_pcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_pbicgstab_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_pbicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_pgmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_pgmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -785,6 +791,17 @@ class CvrMatrix:
         res = self._solve("cvr_bicgstab", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b.ctypes.data, x.ctypes.data))
         return x[: self.nrows], res
 
+    def pbicgstab(self, precond, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, stream=None):
+        """BiCGSTAB preconditioned by a Precond object (cvr_pbicgstab_device): p^ = M^-1 p and s^ = M^-1 s by its apply in place of a diagonal;
+        the arguments and the CgResult are bicgstab's.  With block_size = 1 the result is bit for bit bicgstab's with minv = the exported W."""
+        return self._solve("cvr_pbicgstab_device", self._cg_options(rtol, max_iters, check_every, None), (precond._p, b_ptr, x_ptr), (stream,))
+
+    def pbicgstab_host(self, precond, b, x0=None, rtol=None, max_iters=None, check_every=0):
+        """the same through host arrays (cvr_pbicgstab): b and the start vector x0 (None: zero) of nrows values.  Returns (x, CgResult)."""
+        b, x = self._host_vectors(b, x0)
+        res = self._solve("cvr_pbicgstab", self._cg_options(rtol, max_iters, check_every, None), (precond._p, b.ctypes.data, x.ctypes.data))
+        return x[: self.nrows], res
+
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
         """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device
         arrays (anything with data_ptr() and new_zeros()) of nrows values of the handle's type: x0 is the start vector and is overwritten with the
@@ -801,6 +818,20 @@ class CvrMatrix:
         opt = self._gmres_options("gmres_host", options, minv)
         b, x = self._host_vectors(b, x0)
         return x[: self.nrows], self._solve("cvr_gmres", opt, (b.ctypes.data, x.ctypes.data, int(restart)))
+
+    def pgmres(self, precond, b, x0=None, restart=30, stream=None, **options):
+        """restarted GMRES(restart) preconditioned by a Precond object (cvr_pgmres_device): z = M^-1 v by its apply in place of a diagonal; b, x0,
+        the options and the return value are gmres's.  With block_size = 1 the result is bit for bit gmres's with minv = the exported W."""
+        opt = self._gmres_options("pgmres", options, None)
+        x = b.new_zeros(max(self.nrows, 1)) if x0 is None else x0
+        res = self._solve("cvr_pgmres_device", opt, (precond._p, b.data_ptr(), x.data_ptr(), int(restart)), (stream,))
+        return (x[: self.nrows] if x0 is None else x), res
+
+    def pgmres_host(self, precond, b, x0=None, restart=30, **options):
+        """the same through host arrays (cvr_pgmres): b and the start vector x0 (None: zero) of nrows values.  Returns (x, CgResult)."""
+        opt = self._gmres_options("pgmres_host", options, None)
+        b, x = self._host_vectors(b, x0)
+        return x[: self.nrows], self._solve("cvr_pgmres", opt, (precond._p, b.ctypes.data, x.ctypes.data, int(restart)))
 
     def spmm(self, X, iters=1):
         """Y = A X for the k columns of X (host array of shape (ncols, k)) in one pass per block of 8 (cvr_spmm); returns (Y of shape

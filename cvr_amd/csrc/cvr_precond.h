@@ -1,0 +1,71 @@
+// cvr_precond.h -- the block-Jacobi object as the solvers see it, shared by cvr_precond.hip (the object, cvr_pcg_device), cvr_pbicgstab.hip and
+// cvr_pgmres.hip: the struct, the apply of one packet (every solver forms z = W r by this code, so the same r gives the same bits in all of them) and
+// the checks every preconditioned entry point makes.  How W is built and laid out: cvr_precond.hip's head.
+#pragma once
+#include "cvr_krylov.h"
+
+struct cvr_precond {
+    int      device = 0;
+    int64_t  n = 0, nblocks = 0, identity_blocks = 0;
+    int32_t  bs = 1, is_f32 = 0;
+    void    *d_w = nullptr;          // nblocks * bs * bs values of T, every block transposed
+};
+
+namespace cvrh {
+namespace krylov {
+namespace {
+
+// The fp64 sums of the packet at e (cnt of its values exist; the others 0): s_i = t_0 + t_1 + .., t_j = double(W[i][j]) * double(r[k bs + j]), left to
+// right over the columns of block k that exist.  R: the type of r -- T in the apply, double where GMRES forms x from its fp64 combination.
+template <typename T, typename R>
+__device__ __forceinline__ void apply_sums(const T *__restrict__ wt, int bs, const R *__restrict__ r, long long n, long long e, int cnt, double (&sv)[kPack<T>])
+{
+    long long k = e / bs;
+    int       il = (int)(e - k * bs);
+#pragma unroll
+    for (int jj = 0; jj < kPack<T>; jj++) {
+        sv[jj] = 0;
+        if (jj < cnt) {
+            const long long r0 = k * bs;
+            const int       m = n - r0 < bs ? (int)(n - r0) : bs;
+            const T        *w = wt + r0 * bs + il;
+            double          s = (double)w[0] * (double)r[r0];
+            for (int j = 1; j < m; j++) s += (double)w[(long long)j * bs] * (double)r[r0 + j];
+            sv[jj] = s;
+            if (++il == bs) { il = 0; k++; }
+        }
+    }
+}
+
+// z of the packet at e: z_i = T(s_i)
+template <typename T>
+__device__ __forceinline__ void apply_pack(const T *__restrict__ wt, int bs, const T *__restrict__ r, long long n, long long e, int cnt, T (&zv)[kPack<T>])
+{
+    double sv[kPack<T>];
+    apply_sums<T, T>(wt, bs, r, n, e, cnt, sv);
+#pragma unroll
+    for (int jj = 0; jj < kPack<T>; jj++) zv[jj] = (T)sv[jj];
+}
+
+// what the preconditioned entry points check before any device work and before the handle is looked at, behind their solver's own checks
+// (`entry`: "cvr_pcg", "cvr_pbicgstab", ...)
+inline int check_precond_args(const cvr_precond *p, const cvr_cg_options *opt, const char *entry)
+{
+    if (!p) return fail(CVR_ERR_INVALID, "null argument");
+    if (opt->minv_dev) return fail(CVR_ERR_INVALID, "%s: minv_dev is set beside a preconditioner object: one preconditioner per call", entry);
+    return CVR_OK;
+}
+
+// ... and what they ask of the pair, behind check_square_preprocessed
+inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const char *entry)
+{
+    if (p->n != h->info.nrows) return fail(CVR_ERR_INVALID, "%s: the preconditioner has n = %lld, the handle nrows = %lld", entry, (long long)p->n, (long long)h->info.nrows);
+    if ((p->is_f32 != 0) != (h->vsz == 4))
+        return fail(CVR_ERR_INVALID, "%s: the preconditioner's type is %s, the handle's %s", entry, p->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
+    if (p->device != h->device) return fail(CVR_ERR_INVALID, "%s: the preconditioner lies on device %d, the handle on device %d", entry, p->device, h->device);
+    return CVR_OK;
+}
+
+}  // namespace
+}  // namespace krylov
+}  // namespace cvrh

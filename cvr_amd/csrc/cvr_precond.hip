@@ -1,6 +1,7 @@
 // cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*) and the conjugate gradients that use it (cvr_pcg_device,
 // cvr_pcg).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into LDS, inverts them there in fp64 and stores the
-// inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for the elements CVR_KRYLOV_PACKETS gives it.
+// inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for the elements CVR_KRYLOV_PACKETS gives it
+// (cvr_precond.h: the struct and the apply of one packet, shared with cvr_pbicgstab.hip and cvr_pgmres.hip).
 //   precond_build_kernel   one wavefront per workgroup; L = 8, 16 or 32 lanes per block (the power of two from bs up), 64 / L blocks per wavefront
 //   precond_apply_kernel   z = W r
 //   pcg_apply_kernel       the same inside the solver, with the partial sums of r . z (set 1 of cg_direction_kernel<T, true>) and, at the start, p = z
@@ -10,16 +11,10 @@
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
+#include "cvr_precond.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
-
-struct cvr_precond {
-    int      device = 0;
-    int64_t  n = 0, nblocks = 0, identity_blocks = 0;
-    int32_t  bs = 1, is_f32 = 0;
-    void    *d_w = nullptr;          // nblocks * bs * bs values of T, every block transposed
-};
 
 namespace {
 
@@ -155,28 +150,6 @@ __global__ __launch_bounds__(kBuildLanes) void precond_build_kernel(const int64_
         T *w = wt + kb * bs * bs;
         for (int j = 0; j < bs; j++) w[j * bs + sub] = bad ? (T)(j == sub ? 1 : 0) : (T)a[sub * ld + j];
         if (bad && sub == 0) atomicAdd(nidentity, 1ull);
-    }
-}
-
-// z of the packet at e (cnt of its values exist; the others 0): z_i = T(t_0 + t_1 + ..), t_j = double(W[i][j]) * double(r[k bs + j]), left to right
-// over the columns of block k that exist
-template <typename T>
-__device__ __forceinline__ void apply_pack(const T *__restrict__ wt, int bs, const T *__restrict__ r, long long n, long long e, int cnt, T (&zv)[kPack<T>])
-{
-    long long k = e / bs;
-    int       il = (int)(e - k * bs);
-#pragma unroll
-    for (int jj = 0; jj < kPack<T>; jj++) {
-        zv[jj] = (T)0;
-        if (jj < cnt) {
-            const long long r0 = k * bs;
-            const int       m = n - r0 < bs ? (int)(n - r0) : bs;
-            const T        *w = wt + r0 * bs + il;
-            double          s = (double)w[0] * (double)r[r0];
-            for (int j = 1; j < m; j++) s += (double)w[(long long)j * bs] * (double)r[r0 + j];
-            zv[jj] = (T)s;
-            if (++il == bs) { il = 0; k++; }
-        }
     }
 }
 
@@ -381,8 +354,7 @@ int pcg_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, const cvr_
 int check_pcg_args(const void *h, const cvr_precond *p, const void *b, const void *x, const cvr_cg_options *opt, const cvr_cg_result *res)
 {
     if (const int rc = check_solver_args(h, b, x, opt, res)) return rc;
-    if (!p) return fail(CVR_ERR_INVALID, "null argument");
-    if (opt->minv_dev) return fail(CVR_ERR_INVALID, "cvr_pcg: minv_dev is set beside a preconditioner object: one preconditioner per call");
+    if (const int rc = check_precond_args(p, opt, "cvr_pcg")) return rc;
     return CVR_OK;
 }
 
@@ -390,9 +362,7 @@ int check_pcg_args(const void *h, const cvr_precond *p, const void *b, const voi
 int check_pcg_handle(const cvr_handle *h, const cvr_precond *p)
 {
     if (const int rc = check_square_preprocessed(h, "cvr_pcg", "conjugate gradients need")) return rc;
-    if (p->n != h->info.nrows) return fail(CVR_ERR_INVALID, "cvr_pcg: the preconditioner has n = %lld, the handle nrows = %lld", (long long)p->n, (long long)h->info.nrows);
-    if ((p->is_f32 != 0) != (h->vsz == 4)) return fail(CVR_ERR_INVALID, "cvr_pcg: the preconditioner's type is %s, the handle's %s", p->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
-    if (p->device != h->device) return fail(CVR_ERR_INVALID, "cvr_pcg: the preconditioner lies on device %d, the handle on device %d", p->device, h->device);
+    if (const int rc = check_precond_pair(h, p, "cvr_pcg")) return rc;
     return CVR_OK;
 }
 

@@ -183,6 +183,40 @@ def block_diag_spd(n, bs, cond=1e3, seed=11, dtype=np.float64):
     return n, n, rp, cols.astype(np.int32), vals.astype(dtype)
 
 
+def block_diag_nonsym(n, bs, cond=1e3, seed=13, dtype=np.float64):
+    """The nonsymmetric sibling of block_diag_spd (the test family of the preconditioned BiCGSTAB and GMRES): exactly block-diagonal, dense blocks of bs
+    rows (the last one shorter when bs does not divide n), each U diag(sigma) V^T with independent random orthogonal U and V and singular values spread
+    log-uniformly over [1, cond] -- both ends in every block, so every block is nonsingular with condition cond, and not symmetric.  A short last block
+    is a block of its own size, built the same way.  Returns (n, n, row_ptr, col_idx, vals) like the generators above."""
+    rng = np.random.default_rng(seed)
+    nb, last = -(-n // bs), n % bs
+    rows, cols, vals = [], [], []
+
+    def blocks_of(count, m, first_row):
+        if count == 0:
+            return
+        u, _ = np.linalg.qr(rng.standard_normal((count, m, m)))
+        v, _ = np.linalg.qr(rng.standard_normal((count, m, m)))
+        sig = cond ** rng.random((count, m))
+        sig[:, 0] = 1.0
+        sig[:, -1] = cond if m > 1 else 1.0
+        blk = np.einsum("kij,kj,klj->kil", u, sig, v)
+        r = first_row + np.repeat(np.arange(count * m, dtype=np.int64), m)
+        rows.append(r)
+        cols.append(first_row + ((r - first_row) // m) * m + np.tile(np.arange(m, dtype=np.int64), count * m))
+        vals.append(blk.reshape(-1))
+
+    full = nb - (1 if last else 0)
+    blocks_of(full, bs, 0)
+    blocks_of(1 if last else 0, last, full * bs)
+    rows = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    cols = np.concatenate(cols) if cols else np.zeros(0, dtype=np.int64)
+    vals = np.concatenate(vals) if vals else np.zeros(0)
+    rp = np.zeros(n + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return n, n, rp, cols.astype(np.int32), vals.astype(dtype)
+
+
 def nonsym_from_pattern(n, rp, ci, c=0.5, rscale=None, seed=3, dtype=np.float64):
     """A nonsymmetric, strictly diagonally dominant matrix from any square pattern (the BiCGSTAB solver's test matrices): W = the pattern as
     it is (not symmetrised) without the diagonal and without duplicates, with seeded weights in [0.5, 1.5) and each row scaled to the absolute

@@ -634,6 +634,44 @@ int cvr_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void 
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pcg(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* BiCGSTAB preconditioned by such an object.  Everything cvr_bicgstab_device's text above fixes holds word for word -- the handles, b_dev and x_dev,
+ * the options and the result, r = b - A x by the scaled product, every update, the fixed-tree sums, alpha, omega and beta, the stop rules and status
+ * codes, b == 0, a start within the tolerance, the non-finite cases, the half-step stop, check_every, spmv_count, seconds, the ordering on `stream` --
+ * with M^-1 = W of the object in place of diag(minv): p^ = W p wherever that text says p^ = T(minv * p), s^ = W s wherever it says
+ * s^ = T(double(minv) * double(s)), both by the apply arithmetic above.  p^ and s^ are buffers of the library, allocated per call with the others.
+ * Each apply is a launch of its own (an element of p^ needs its whole block of p): seven vector launches beside the two SpMVs per step.  A kernel
+ * behind a stop or a half-step stop writes nothing, the applies included: x and the result do not depend on check_every.
+ * The contract that follows: with block_size = 1, x, iterations, status, residual_norm and b_norm are bit for bit what cvr_bicgstab_device returns
+ * with minv_dev = the exported W, on every layout and for every check_every.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; p null; opt->minv_dev != NULL
+ * (one preconditioner per call): CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols: CVR_ERR_INVALID; then, each
+ * CVR_ERR_INVALID with cvr_last_error naming the mismatch: p's n differs from the handle's nrows, p's type from the handle's, p's device from the
+ * handle's. */
+int cvr_pbicgstab_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg */
+int cvr_pbicgstab(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
+
+/* Restarted GMRES(m) preconditioned by such an object.  Everything cvr_gmres_device's text above fixes holds word for word -- `restart`, the handles,
+ * b_dev and x_dev, the options and the result, the start of the call and of every cycle, the two Gram-Schmidt passes, the rotations, the scalars, the
+ * fixed-tree sums, the stop rules and status codes, b == 0, a start within the tolerance, the non-finite cases, the lucky breakdown, check_every,
+ * spmv_count, seconds, the ordering on `stream` -- with M^-1 = W of the object in place of diag(minv): z_j = W v_j by the apply arithmetic above
+ * wherever that text says z = T(double(minv) * double(v_j)).  The apply is a launch of its own: six vector launches beside the SpMV per step.
+ *   Forming x from q columns (q = 0: nothing): y as there.  Per element u = +0; for i = 0..q-1: u = u + y_i * double(v_i), kept in fp64 (never
+ *     rounded to T) in a buffer of the library of n doubles, allocated with the call's other buffers.  Then, for row i of block k with m columns:
+ *     x_i = T(double(x_i) + (t_0 + t_1 + ... + t_(m-1)))   with   t_j = double(W[i][j]) * u[k*bs + j],
+ *     the apply's order and rounding with the fp64 u where the apply has double(r).  Two launches where cvr_gmres_device has one.
+ * A kernel behind a stop writes nothing that reaches x or the result, the applies and the two x-forming kernels included.
+ * The contract that follows: with block_size = 1, x, iterations, status, residual_norm and b_norm are bit for bit what cvr_gmres_device returns with
+ * minv_dev = the exported W, on every layout and for every check_every.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; p null; opt->minv_dev != NULL;
+ * restart < 1 or restart > CVR_GMRES_MAX_RESTART ("restart" in cvr_last_error): CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE;
+ * nrows != ncols: CVR_ERR_INVALID; the three mismatches of cvr_pcg_device, each CVR_ERR_INVALID; no device memory for the call's buffers:
+ * CVR_ERR_NOMEM, nothing allocated. */
+int cvr_pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void *x_dev, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res,
+                      void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg */
+int cvr_pgmres(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
