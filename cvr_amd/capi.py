@@ -109,6 +109,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
+           "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
@@ -173,6 +174,9 @@ def lib():
         L.cvr_precond_destroy.argtypes = [C.c_void_p]
         L.cvr_pcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_pbicgstab_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pbicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_pgmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
@@ -492,6 +496,13 @@ class Precond:
         if rc:
             raise CvrError(rc, "cvr_precond_apply_device")
 
+    def apply_multi(self, R_ptr, ldr, Z_ptr, ldz, nvec, stream=None):
+        """asynchronous Z = M^-1 R on row-major device blocks of n rows of ldr / ldz values, 1 <= nvec <= 8 columns
+        (cvr_precond_apply_multi_device); column c of Z is bit for bit apply()'s z for column c of R; the blocks must not overlap"""
+        rc = lib().cvr_precond_apply_multi_device(self._p, R_ptr, ldr, Z_ptr, ldz, nvec, stream)
+        if rc:
+            raise CvrError(rc, "cvr_precond_apply_multi_device")
+
     def close(self):
         if getattr(self, "_p", None) and self._p.value:
             lib().cvr_precond_destroy(self._p)
@@ -758,9 +769,8 @@ class CvrMatrix:
             raise CvrError(rc, "cvr_cg_multi_device")
         return list(res)
 
-    def cg_multi_host(self, B, X0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
-        """the same through host arrays (cvr_cg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec); minv_ptr stays a
-        device pointer.  Returns (X of shape (nrows, nvec), list of CgResult)."""
+    def _host_blocks(self, B, X0):
+        """a host block solver's B, contiguous in the handle's type with exactly nrows rows, and its X: X0 (None: zero) in a new array"""
         B = np.ascontiguousarray(B, dtype=self.dtype)
         if B.ndim != 2 or B.shape[0] < self.nrows:
             raise ValueError("B must be 2-D with at least nrows rows")
@@ -772,10 +782,35 @@ class CvrMatrix:
             if X0.ndim != 2 or X0.shape[0] < self.nrows or X0.shape[1] != k:
                 raise ValueError("X0 must have B's shape")
             X[: self.nrows] = X0[: self.nrows]
+        return B, X, k
+
+    def cg_multi_host(self, B, X0=None, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_cg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec); minv_ptr stays a
+        device pointer.  Returns (X of shape (nrows, nvec), list of CgResult)."""
+        B, X, k = self._host_blocks(B, X0)
         opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), (CgResult * max(k, 1))()
         rc = lib().cvr_cg_multi(self._h, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)
         if rc:
             raise CvrError(rc, "cvr_cg_multi")
+        return X[: self.nrows], list(res)
+
+    def pcg_multi(self, precond, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, stream=None):
+        """cg_multi preconditioned by a Precond object (cvr_pcg_multi_device): Z = M^-1 R by its k-wide apply in place of a diagonal; the
+        blocks and the list of nvec CgResult are cg_multi's.  Column j is bit for bit pcg()'s result for B[:, j] and X[:, j]."""
+        opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(int(nvec), 1))()
+        rc = lib().cvr_pcg_multi_device(self._h, precond._p, B_ptr, ldb, X_ptr, ldx, nvec, C.byref(opt), res, stream)
+        if rc:
+            raise CvrError(rc, "cvr_pcg_multi_device")
+        return list(res)
+
+    def pcg_multi_host(self, precond, B, X0=None, rtol=None, max_iters=None, check_every=0):
+        """the same through host arrays (cvr_pcg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec).  Returns (X of shape
+        (nrows, nvec), list of CgResult)."""
+        B, X, k = self._host_blocks(B, X0)
+        opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(k, 1))()
+        rc = lib().cvr_pcg_multi(self._h, precond._p, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)
+        if rc:
+            raise CvrError(rc, "cvr_pcg_multi")
         return X[: self.nrows], list(res)
 
     def bicgstab(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):

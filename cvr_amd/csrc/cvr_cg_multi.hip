@@ -9,288 +9,14 @@
 // unrolled over the kSpmmBlock columns there can be, so a column's accumulators and scalars are registers; nvec itself is a runtime argument.
 // Every column has its own state cell.  A column that has stopped is not written any more (its bit in the kernels' `live` mask is clear; its
 // values are still loaded and computed with where they share a sub-block with a live column, and dropped); the others go on.
-// The host side is cvr_krylov.h's driver: this file adds the cells, the kernels, the step and the read-back of all columns.
-#include "cvr_krylov.h"
+// The host side is cvr_krylov.h's driver: the cells and the kernels are in cvr_cg_multi_kernels.h (shared with cvr_pcg_multi.hip), this file adds the
+// step and the read-back of all columns.
+#include "cvr_cg_multi_kernels.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
 
 namespace {
-
-constexpr int kCols = cvr::kSpmmBlock;          // columns per call
-constexpr int kSets = 3;                        // partial-sum sets per column in `part`: column c's begin at part + c * kSets * kBlocks
-
-// a column's state cell: cvr_cg.hip's CgCell, member for member
-struct CgCell {
-    double  bb, bnorm;
-    double  rr, rnorm;
-    double  rz[2];
-    int32_t stop, status, iters, zero_x;
-};
-
-// the sub-block's values at p + off for the columns of `mask` (bits 0 .. kPack - 1): one 16-byte store when all of them are live, else one by one
-template <typename T, bool VEC>
-__device__ __forceinline__ void store_cols(T *__restrict__ p, long long off, uint32_t mask, const T (&v)[kPack<T>])
-{
-    constexpr uint32_t kFull = (1u << kPack<T>) - 1;
-    if (VEC && mask == kFull) {
-        store_pack<T, true>(p, off, kPack<T>, v);
-    } else {
-#pragma unroll
-        for (int i = 0; i < kPack<T>; i++) if (mask >> i & 1u) p[off + i] = v[i];
-    }
-}
-
-// the sub-blocks of one row: cb = the first column, cc = how many of its kPack<T> columns exist (the loop is unrolled: cb is a constant in the body)
-#define CVR_CG_MULTI_SUBBLOCKS(T, cb, cc)                 \
-    _Pragma("unroll") for (int cb = 0; cb < kCols; cb += kPack<T>) \
-        if (int cc = nvec - cb < kPack<T> ? nvec - cb : kPack<T>; cc > 0)
-
-// P = [X0 | a zero row] with ld = nvec, from the caller's X of leading dimension ldx
-template <typename T>
-__global__ __launch_bounds__(kThreads) void cgm_start_kernel(const T *__restrict__ x, long long ldx, T *__restrict__ p, long long n, int nvec)
-{
-    const long long total = (n + 1) * nvec;
-    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < total; i += (long long)gridDim.x * kThreads) {
-        const long long row = i / nvec;
-        p[i] = row < n ? x[row * ldx + (i - row * nvec)] : (T)0;
-    }
-}
-
-// x = 0 in the columns of `mask` (b == 0 there)
-template <typename T>
-__global__ __launch_bounds__(kThreads) void cgm_zero_kernel(T *__restrict__ x, long long ldx, long long n, int nvec, uint32_t mask)
-{
-    for (long long row = (long long)blockIdx.x * kThreads + threadIdx.x; row < n; row += (long long)gridDim.x * kThreads)
-        for (int c = 0; c < nvec; c++)
-            if (mask >> c & 1u) x[row * ldx + c] = (T)0;
-}
-
-// The start: q holds A x0.  r = T(b - q) (the scaled product's alpha = -1, beta = 1 write-out), z = minv .* r (PRE), p = z (or r), and per column
-// the partial sums of r . r, r . z (PRE) and b . b.  LV: the library's blocks take 16-byte packets (nvec is a multiple of kPack); AL: so do b
-// (ldb a multiple of kPack, 16-byte aligned) and minv.
-template <typename T, bool PRE, bool LV, bool AL>
-__global__ __launch_bounds__(kThreads) void cgm_init_kernel(const T *__restrict__ b, long long ldb, const T *__restrict__ minv, const T *__restrict__ q,
-                                                            T *__restrict__ r, T *__restrict__ z, T *__restrict__ p, long long n, int nvec,
-                                                            double *__restrict__ out)
-{
-    __shared__ double sh[kCols][kSets][kWaves];
-    double acc[kCols][kSets] = {};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T mv[kPack<T>];
-        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
-        CVR_CG_MULTI_SUBBLOCKS(T, cb, cc) {
-            const uint32_t all = (1u << cc) - 1;
-#pragma unroll
-            for (int j = 0; j < kPack<T>; j++) {
-                if (j < cnt) {
-                    const long long row = e + j;
-                    T bv[kPack<T>], qv[kPack<T>], rv[kPack<T>], zv[kPack<T>];
-                    load_pack<T, AL>(b, row * ldb + cb, cc, bv);
-                    load_pack<T, LV>(q, row * nvec + cb, cc, qv);
-#pragma unroll
-                    for (int i = 0; i < kPack<T>; i++) {
-                        rv[i] = bv[i] - qv[i];
-                        zv[i] = PRE ? (T)((double)mv[j] * (double)rv[i]) : rv[i];
-                        acc[cb + i][0] += (double)rv[i] * (double)rv[i];
-                        if constexpr (PRE) acc[cb + i][1] += (double)rv[i] * (double)zv[i];
-                        acc[cb + i][2] += (double)bv[i] * (double)bv[i];
-                    }
-                    store_cols<T, LV>(r, row * nvec + cb, all, rv);
-                    if constexpr (PRE) store_cols<T, LV>(z, row * nvec + cb, all, zv);
-                    store_cols<T, LV>(p, row * nvec + cb, all, zv);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < kCols; c++)
-        if (c < nvec) store_partials<kSets>(acc[c], out + (size_t)c * kSets * kBlocks, sh[c]);
-}
-
-// one workgroup: every column's start sums into its cell, and the stop test of its start vector (cvr_cg.hip's cg_check_kernel per column)
-__global__ __launch_bounds__(kThreads) void cgm_check_kernel(const double *__restrict__ part, int pre, double rtol, int nvec, CgCell *__restrict__ cells)
-{
-    __shared__ double sh[kCols][kSets][kWaves];
-    for (int col = 0; col < nvec; col++) {
-        double s[kSets];
-        sum_partials<kSets>(part + (size_t)col * kSets * kBlocks, s, sh[col]);
-        if (threadIdx.x != 0) continue;
-        CgCell c;
-        c.bb = s[2]; c.bnorm = sqrt(s[2]);
-        c.rr = s[0]; c.rnorm = sqrt(s[0]);
-        c.rz[0] = pre ? s[1] : s[0]; c.rz[1] = 0;
-        c.stop = 0; c.status = CVR_CG_MAX_ITERS; c.iters = 0; c.zero_x = 0;
-        if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
-        else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= kDblMax) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
-        cells[col] = c;
-    }
-}
-
-// per column the partial sums of p . q
-template <typename T, bool LV>
-__global__ __launch_bounds__(kThreads) void cgm_pq_kernel(const T *__restrict__ p, const T *__restrict__ q, long long n, int nvec, double *__restrict__ out,
-                                                          const CgCell *__restrict__ cells)
-{
-    __shared__ double sh[kCols][1][kWaves];
-    int going = 0;          // (no workgroup of this kernel sets a stop)
-    for (int c = 0; c < nvec; c++) going |= !cells[c].stop;
-    if (!going) return;
-    double acc[kCols][1] = {};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        CVR_CG_MULTI_SUBBLOCKS(T, cb, cc) {
-#pragma unroll
-            for (int j = 0; j < kPack<T>; j++) {
-                if (j < cnt) {
-                    T pv[kPack<T>], qv[kPack<T>];
-                    load_pack<T, LV>(p, (e + j) * nvec + cb, cc, pv);
-                    load_pack<T, LV>(q, (e + j) * nvec + cb, cc, qv);
-#pragma unroll
-                    for (int i = 0; i < kPack<T>; i++) acc[cb + i][0] += (double)pv[i] * (double)qv[i];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < kCols; c++)
-        if (c < nvec) store_partials<1>(acc[c], out + (size_t)c * kBlocks, sh[c]);
-}
-
-// Step k, per column that has not stopped: alpha = r.z / p.q; x += alpha p, r -= alpha q, z = minv .* r; the partial sums of r . r (set 0) and
-// r . z (set 1, PRE).  p.q <= 0 or not finite: that column's breakdown, recorded, nothing of it written.  AL: x (ldx a multiple of kPack, 16-byte
-// aligned) and minv take 16-byte packets.
-template <typename T, bool PRE, bool LV, bool AL>
-__global__ __launch_bounds__(kThreads) void cgm_update_kernel(T *__restrict__ x, long long ldx, T *__restrict__ r, T *__restrict__ z, const T *__restrict__ p,
-                                                              const T *__restrict__ q, const T *__restrict__ minv, long long n, int nvec,
-                                                              const double *__restrict__ part_pq, double *__restrict__ out, CgCell *__restrict__ cells, int k)
-{
-    constexpr int K = PRE ? 2 : 1;
-    __shared__ double shp[kCols][1][kWaves];
-    __shared__ double sh[kCols][K][kWaves];
-    __shared__ int stopped[kCols];
-    if ((int)threadIdx.x < nvec) stopped[threadIdx.x] = cells[threadIdx.x].stop;
-    double   alpha[kCols] = {};
-    uint32_t live = 0;
-#pragma unroll
-    for (int c = 0; c < kCols; c++) {
-        if (c < nvec) {
-            double pq[1];
-            sum_partials<1>(part_pq + (size_t)c * kBlocks, pq, shp[c]);
-            if (stopped[c]) continue;
-            if (!(pq[0] > 0) || !(pq[0] <= kDblMax)) {
-                if (blockIdx.x == 0 && threadIdx.x == 0) { cells[c].status = CVR_CG_BREAKDOWN; cells[c].stop = 1; }
-                continue;
-            }
-            alpha[c] = cells[c].rz[k & 1] / pq[0];
-            if (blockIdx.x == 0 && threadIdx.x == 0) cells[c].iters = k + 1;
-            live |= 1u << c;
-        }
-    }
-    if (!live) return;
-    double acc[kCols][K] = {};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T mv[kPack<T>];
-        if constexpr (PRE) load_pack<T, AL>(minv, e, (int)cnt, mv);
-        CVR_CG_MULTI_SUBBLOCKS(T, cb, cc) {
-            const uint32_t m = live >> cb & ((1u << cc) - 1);
-            if (!m) continue;
-#pragma unroll
-            for (int j = 0; j < kPack<T>; j++) {
-                if (j < cnt) {
-                    const long long row = e + j;
-                    T xv[kPack<T>], rv[kPack<T>], pv[kPack<T>], qv[kPack<T>], zv[kPack<T>];
-                    load_pack<T, AL>(x, row * ldx + cb, cc, xv);
-                    load_pack<T, LV>(r, row * nvec + cb, cc, rv);
-                    load_pack<T, LV>(p, row * nvec + cb, cc, pv);
-                    load_pack<T, LV>(q, row * nvec + cb, cc, qv);
-#pragma unroll
-                    for (int i = 0; i < kPack<T>; i++) {
-                        xv[i] = (T)((double)xv[i] + alpha[cb + i] * (double)pv[i]);
-                        rv[i] = (T)((double)rv[i] - alpha[cb + i] * (double)qv[i]);
-                        if constexpr (PRE) zv[i] = (T)((double)mv[j] * (double)rv[i]);
-                        acc[cb + i][0] += (double)rv[i] * (double)rv[i];
-                        if constexpr (PRE) acc[cb + i][1] += (double)rv[i] * (double)zv[i];
-                    }
-                    store_cols<T, AL>(x, row * ldx + cb, m, xv);
-                    store_cols<T, LV>(r, row * nvec + cb, m, rv);
-                    if constexpr (PRE) store_cols<T, LV>(z, row * nvec + cb, m, zv);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < kCols; c++)
-        if (c < nvec) store_partials<K>(acc[c], out + (size_t)c * kSets * kBlocks, sh[c]);
-}
-
-// Step k, behind the update, per column that has not stopped: r.r and r.z from its partials into its cell; ||r|| <= rtol ||b||: converged, recorded,
-// nothing of it written; else p = z + beta p with beta = r.z / r.z of the step before.  z is r without a preconditioner.
-template <typename T, bool PRE, bool LV>
-__global__ __launch_bounds__(kThreads) void cgm_direction_kernel(T *__restrict__ p, const T *__restrict__ z, long long n, int nvec, const double *__restrict__ part,
-                                                                 CgCell *__restrict__ cells, int k, double rtol)
-{
-    constexpr int K = PRE ? 2 : 1;
-    __shared__ double sh[kCols][K][kWaves];
-    __shared__ int stopped[kCols];
-    if ((int)threadIdx.x < nvec) stopped[threadIdx.x] = cells[threadIdx.x].stop;
-    double   beta[kCols] = {};
-    uint32_t live = 0;
-#pragma unroll
-    for (int c = 0; c < kCols; c++) {
-        if (c < nvec) {
-            double s[K];
-            sum_partials<K>(part + (size_t)c * kSets * kBlocks, s, sh[c]);
-            if (stopped[c]) continue;
-            const double rr = s[0], rz = s[K - 1], rnorm = sqrt(rr);
-            const bool   done = rnorm <= rtol * cells[c].bnorm;
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                cells[c].rr = rr; cells[c].rnorm = rnorm; cells[c].rz[(k + 1) & 1] = rz;
-                if (done) { cells[c].status = CVR_CG_CONVERGED; cells[c].stop = 1; }
-            }
-            if (done) continue;
-            beta[c] = rz / cells[c].rz[k & 1];
-            live |= 1u << c;
-        }
-    }
-    if (!live) return;
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        CVR_CG_MULTI_SUBBLOCKS(T, cb, cc) {
-            const uint32_t m = live >> cb & ((1u << cc) - 1);
-            if (!m) continue;
-#pragma unroll
-            for (int j = 0; j < kPack<T>; j++) {
-                if (j < cnt) {
-                    T pv[kPack<T>], zv[kPack<T>];
-                    load_pack<T, LV>(p, (e + j) * nvec + cb, cc, pv);
-                    load_pack<T, LV>(z, (e + j) * nvec + cb, cc, zv);
-#pragma unroll
-                    for (int i = 0; i < kPack<T>; i++) pv[i] = (T)((double)zv[i] + beta[cb + i] * (double)pv[i]);
-                    store_cols<T, LV>(p, (e + j) * nvec + cb, m, pv);
-                }
-            }
-        }
-    }
-}
-
-// the library's blocks of one call: P (x_ext rows, ld = nvec), Q and R (y_ext rows each), Z, the partial sums, the cells
-template <typename T>
-struct Workspace {
-    T      *p, *q, *r, *z;
-    double *part_pq, *part;
-    CgCell *cells;
-};
-
-// what the vector launches of a call share.  lv: the library's blocks take 16-byte packets; al: so do the caller's
-template <typename T>
-struct Call {
-    const T  *b; long long ldb;
-    T        *x; long long ldx;
-    const T  *minv;
-    long long n;
-    int       nvec;
-    bool      lv, al;
-    double    rtol;
-};
 
 // the three vector launches of step k (the product Q = A P is enqueued in front of them); without a preconditioner z is r
 template <typename T>
@@ -301,39 +27,6 @@ hipError_t launch_step(const Workspace<T> &w, const Call<T> &c, int k, hipStream
                c.minv != nullptr, c.lv, c.al);
     with_flags([&](auto PRE, auto LV) { launch(cgm_direction_kernel<T, PRE, LV>, st, w.p, PRE ? w.z : w.r, c.n, c.nvec, w.part, w.cells, k, c.rtol); }, c.minv != nullptr, c.lv);
     return hipGetLastError();
-}
-
-// what both entry points check beside check_solver_args, before any device work and before the handle is looked at
-int check_block_args(int32_t nvec, int64_t ldb, int64_t ldx)
-{
-    if (nvec < 1 || nvec > kCols) return fail(CVR_ERR_INVALID, "nvec = %d: 1 to %d right-hand sides per call", nvec, kCols);
-    if (ldb < nvec || ldx < nvec) return fail(CVR_ERR_INVALID, "ldb = %lld, ldx = %lld: each must be >= nvec = %d", (long long)ldb, (long long)ldx, nvec);
-    return CVR_OK;
-}
-
-// what is asked of the handle; single: one vector of stride 1, which goes through run_spmv on any layout
-int check_handle(const cvr_handle *h, int32_t nvec, bool single)
-{
-    if (const int rc = check_square_preprocessed(h, "cvr_cg_multi", "conjugate gradients need")) return rc;
-    if (single) return CVR_OK;
-    if (!cvr_spmm_supported(h)) return fail(CVR_ERR_STATE, "cvr_cg_multi: this handle's image is not the plain layout; create it with cvr_options.nvec >= 2 for several right-hand sides");
-    if ((uint64_t)(h->info.ncols + 1) * (uint64_t)nvec * h->vsz > 0xffffffffull)
-        return fail(CVR_ERR_INVALID, "P of %lld rows of %d values exceeds the 4 GiB a buffer descriptor addresses", (long long)(h->info.ncols + 1), nvec);
-    return CVR_OK;
-}
-
-// Q = A P for all columns
-template <typename T>
-int product(cvr_handle *h, bool single, const Workspace<T> &w, int nvec, hipStream_t st)
-{
-    if (single) {
-        HIP_TRY(run_spmv(h, w.p, w.q, st));
-        return CVR_OK;
-    }
-    if (h->d_map) HIP_TRY(handle_enter(h, st));          // (a mutable handle's image: ordered with its updates, as cvr_spmm_device)
-    HIP_TRY(cvr::launch_spmm(h->parts[0].img, w.p, nvec, w.q, nvec, nvec, st));
-    if (h->d_map) HIP_TRY(handle_leave(h, st));
-    return CVR_OK;
 }
 
 // cvr_krylov.h's driver with the block's start, step and cells
@@ -394,7 +87,7 @@ int cg_multi_solve(cvr_handle *h, bool single, const T *B, int64_t ldb, T *X, in
 int cg_multi_device(cvr_handle *h, const void *B, int64_t ldb, void *X, int64_t ldx, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
     const bool single = nvec == 1 && ldb == 1 && ldx == 1;
-    if (const int rc = check_handle(h, nvec, single)) return rc;
+    if (const int rc = check_handle(h, nvec, single, "cvr_cg_multi")) return rc;
     Range range("cvr_cg_multi_device");
     HIP_TRY(hipSetDevice(h->device));
     return with_value_type(h, [&](auto t) {
@@ -418,21 +111,8 @@ int cvr_cg_multi(cvr_handle *h, const void *B_host, void *X_host, int32_t nvec, 
 {
     if (const int rc = check_solver_args(h, B_host, X_host, opt, res)) return rc;
     if (const int rc = check_block_args(nvec, nvec, nvec)) return rc;
-    if (const int rc = check_handle(h, nvec, nvec == 1)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t bytes = h->vsz * (size_t)nvec * (size_t)h->info.nrows, slot = (bytes + 255) & ~(size_t)255;
-    struct Mem { void *p = nullptr; ~Mem() { if (p) (void)hipFree(p); } } mem;          // B and X on the device, for this call
-    HIP_TRY(hipMalloc(&mem.p, 2 * slot + 256));
-    uint8_t *B = static_cast<uint8_t *>(mem.p), *X = B + slot;
-    if (bytes) {
-        HIP_TRY(hipMemcpyAsync(B, B_host, bytes, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(X, X_host, bytes, hipMemcpyHostToDevice, h->stream));
-    }
-    const int rc = cg_multi_device(h, B, nvec, X, nvec, nvec, opt, res, h->stream);
-    if (rc) return rc;
-    if (bytes) HIP_TRY(hipMemcpyAsync(X_host, X, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return CVR_OK;
+    if (const int rc = check_handle(h, nvec, nvec == 1, "cvr_cg_multi")) return rc;
+    return solve_block_from_host(h, B_host, X_host, nvec, [&](const void *B, void *X, hipStream_t st) { return cg_multi_device(h, B, nvec, X, nvec, nvec, opt, res, st); });
 }
 
 }  // extern "C"

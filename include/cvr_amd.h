@@ -634,6 +634,36 @@ int cvr_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void 
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pcg(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
+ * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
+ * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
+ * Column c of Z is bit for bit what cvr_precond_apply_device gives for column c of R: the same left-to-right sum from t_0, every product and every
+ * addition rounded on its own (no fused multiply-add); no R and no Z beyond row n - 1 for a short last block.  Each W[i][j] is loaded once for all
+ * columns of its row, and a row of R in 16-byte pieces where nvec, the leading dimension and the base allow it.  The kernel runs on the solvers'
+ * grid (1024 workgroups of 256 threads); the thread that owns a 16-byte packet of rows of a single vector owns those rows of every column.
+ * The call only enqueues on `stream` and makes the object's device current; n == 0 is CVR_OK.
+ * Errors, CVR_ERR_INVALID before any device work: a null argument; R_dev == Z_dev; nvec outside 1..8; ldr < nvec or ldz < nvec. */
+int cvr_precond_apply_multi_device(const cvr_precond *p, const void *R_dev, int64_t ldr, void *Z_dev, int64_t ldz, int32_t nvec, void *stream);
+
+/* Batched conjugate gradients preconditioned by such an object.  Everything cvr_cg_multi_device's text above fixes holds word for word -- the
+ * blocks B_dev and X_dev, the leading dimensions, the padding columns that are never touched, res[nvec]; independent columns, each with its own
+ * state cell and its own stop, and no write to a stopped column's slices; spmv_count and seconds the same in every res[j]; nvec = 1 with
+ * ldb = ldx = 1 on every single-GPU handle through cvr_spmv_device's launch path; the ordering, a mutable handle's image, "not capturable in a HIP
+ * graph" -- with Z = W R by the apply arithmetic above in place of z = T(minv * r); Z is a block of the library, allocated per call.  In the sum
+ * r.z of a column the thread that owns element i adds the term double(r_i) * double(z_i), in element order.  Four vector launches beside the
+ * k-wide product per step (Z is formed by a launch of its own between the update and the direction: an element of z needs its whole block of r).
+ * The contract, for every column j: column j of X and res[j].iterations, .status, .residual_norm and .b_norm are bit for bit what cvr_pcg_device
+ * returns on the same handle and object for b = B[:, j], x0 = X[:, j] and the same options -- for every check_every, ldb, ldx and alignment.  It
+ * follows that with block_size = 1 column j is bit for bit cvr_cg_multi_device's with minv_dev = the exported W.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; p null; opt->minv_dev != NULL
+ * (one preconditioner per call); nvec outside 1..8, ldb < nvec or ldx < nvec: CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE;
+ * nrows != ncols: CVR_ERR_INVALID; a handle that does not take the block (cvr_cg_multi_device): CVR_ERR_STATE; (ncols + 1) * nvec values beyond
+ * 4 GiB: CVR_ERR_INVALID; then the three mismatches of cvr_pcg_device (n, type, device), each CVR_ERR_INVALID naming the mismatch. */
+int cvr_pcg_multi_device(cvr_handle *h, const cvr_precond *p, const void *B_dev, int64_t ldb, void *X_dev, int64_t ldx, int32_t nvec,
+                         const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host B and X (nrows x nvec each, row-major, ld = nvec; X in and out), as cvr_cg_multi */
+int cvr_pcg_multi(cvr_handle *h, const cvr_precond *p, const void *B_host, void *X_host, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* BiCGSTAB preconditioned by such an object.  Everything cvr_bicgstab_device's text above fixes holds word for word -- the handles, b_dev and x_dev,
  * the options and the result, r = b - A x by the scaled product, every update, the fixed-tree sums, alpha, omega and beta, the stop rules and status
  * codes, b == 0, a start within the tolerance, the non-finite cases, the half-step stop, check_every, spmv_count, seconds, the ordering on `stream` --

@@ -69,7 +69,7 @@ def metadata(lines):
             if item.get("name"):
                 out[item["name"]] = item
             item = {}
-        m = re.match(r"^\s*-?\s*\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s*(\S+)", l)
+        m = re.match(r"^\s*-?\s*\.(name|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s*(\S+)", l)
         if m:
             item[m.group(1)] = m.group(2) if m.group(1) == "name" else int(m.group(2))
     if item.get("name"):
