@@ -95,6 +95,15 @@ class PrecondInfo(C.Structure):
 
 
 PRECOND_MAX_BLOCK = 32      # include/cvr_amd.h: CVR_PRECOND_MAX_BLOCK
+CHEBYSHEV_MAX_DEGREE = 16   # include/cvr_amd.h: CVR_CHEBYSHEV_MAX_DEGREE
+CHEBYSHEV_LMAX_FACTOR = 1.1  # include/cvr_amd.h: CVR_CHEBYSHEV_LMAX_FACTOR
+
+
+class ChebyshevInfo(C.Structure):
+    """cvr_chebyshev_info"""
+    _fields_ = [("degree", C.c_int32), ("is_f32", C.c_int32), ("lmin", C.c_double), ("lmax", C.c_double),
+                ("a", C.c_double * CHEBYSHEV_MAX_DEGREE), ("b", C.c_double * CHEBYSHEV_MAX_DEGREE)]
+
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
@@ -109,6 +118,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_get_info", "cvr_destroy", "cvr_spmv", "cvr_spmv_device", "cvr_spmv_device_repeat", "cvr_spmm_device", "cvr_spmm", "cvr_spmm_supported",
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
+           "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
@@ -174,6 +184,9 @@ def lib():
         L.cvr_precond_destroy.argtypes = [C.c_void_p]
         L.cvr_pcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_precond_chebyshev.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_double, C.c_double]
+        L.cvr_precond_chebyshev_info.argtypes = [C.c_void_p, C.POINTER(ChebyshevInfo)]
+        L.cvr_chebyshev_bounds.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -479,6 +492,29 @@ class Precond:
         lib().cvr_precond_get_info(self._p, C.byref(self.info))
         self.dtype = np.float32 if self.info.is_f32 else np.float64
         return self
+
+    @classmethod
+    def chebyshev(cls, matrix, degree, lmin, lmax):
+        """cvr_precond_chebyshev: z = p_degree(A) r, the Chebyshev polynomial for a spectrum in [lmin, lmax], applied through `matrix`'s own SpMV.  The
+        object borrows the CvrMatrix (kept alive here; close the object before the matrix) and serves one stream at a time."""
+        self = cls()
+        rc = lib().cvr_precond_chebyshev(C.byref(self._p), matrix._h, int(degree), float(lmin), float(lmax))
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_chebyshev")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        self._matrix = matrix
+        return self
+
+    def chebyshev_info(self):
+        """cvr_precond_chebyshev_info: dict(degree, is_f32, lmin, lmax, a, b) with the degree coefficients a[k], b[k] (a[0] = 0, b[0] = c0) as fp64 arrays"""
+        ci = ChebyshevInfo()
+        rc = lib().cvr_precond_chebyshev_info(self._p, C.byref(ci))
+        if rc:
+            raise CvrError(rc, "cvr_precond_chebyshev_info")
+        return dict(degree=ci.degree, is_f32=ci.is_f32, lmin=ci.lmin, lmax=ci.lmax, a=np.array(ci.a[: ci.degree], dtype=np.float64),
+                    b=np.array(ci.b[: ci.degree], dtype=np.float64))
 
     def export(self):
         """the inverse blocks W as an array of shape (nblocks, block_size, block_size) of the object's dtype, each block row-major"""
@@ -934,6 +970,15 @@ class CvrMatrix:
         if rc:
             raise CvrError(rc, "cvr_power_iteration")
         return lam.value, sec.value
+
+    def chebyshev_bounds(self, power_iters=20, eig_ratio=30.0, stream=None):
+        """(lmin, lmax) for Precond.chebyshev from `power_iters` power steps (cvr_chebyshev_bounds): lmax = 1.1 * the Rayleigh quotient,
+        lmin = lmax / eig_ratio; synchronises the stream"""
+        lo, hi = C.c_double(), C.c_double()
+        rc = lib().cvr_chebyshev_bounds(self._h, int(power_iters), float(eig_ratio), C.byref(lo), C.byref(hi), stream)
+        if rc:
+            raise CvrError(rc, "cvr_chebyshev_bounds")
+        return lo.value, hi.value
 
     def bench(self, warmup, iters):
         s = C.c_double()

@@ -1,0 +1,310 @@
+// cvr_chebyshev.hip -- the Chebyshev polynomial preconditioner, the second kind of cvr_precond (include/cvr_amd.h: cvr_precond_chebyshev,
+// cvr_precond_chebyshev_info, cvr_chebyshev_bounds), and the conjugate gradients that use it.  z = p_d(A) r is the Chebyshev iteration for A z = r
+// from z = 0 with fixed coefficients: degree - 1 products q = A z through run_spmv (cvr_spmv_device's path) on the borrowed handle, each followed by
+// one element-wise kernel on the solvers' grid; no dot product, no read-back -- the scalars a[k], b[k] are computed once on the host.
+//   cheb_first_kernel   step 0:      d = T(c0 r), z = d
+//   cheb_step_kernel    step k >= 1: d = T(a[k] d + b[k] (r - q)), z = T(z + d)
+// Both come in four modes: kInner (z goes to the object's zi: an earlier step), kLast (z goes to the caller's array: the last step of
+// cvr_precond_apply_device), kSolve and kSolveStart (the last step inside cvr_pcg_device: z goes to the solver's buffer with the partial sums of
+// r . z in set 1, what pcg_apply_kernel forms; at the start p = z too; behind a stop nothing is written).  With degree = 1 step 0 is the last.
+// The solver is cvr_precond.hip's pcg_solve with this apply between cg_update_kernel<T, false, AL> and cg_direction_kernel<T, true>
+// (cvr_cg_kernels.h: the kernels cvr_cg_device runs, unchanged): 3 + degree vector launches and degree SpMVs per step.
+// (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+#include "cvr_krylov.h"
+#include "cvr_cg_kernels.h"
+#include "cvr_precond.h"
+
+using namespace cvrh;
+using namespace cvrh::krylov;
+
+namespace {
+
+enum Mode { kInner, kLast, kSolve, kSolveStart };
+
+// What a step's kernel does with z of a packet, by mode.  zi: the object's buffer, out: the caller's z (kLast) or the solver's (kSolve, kSolveStart).
+// AL: the caller's arrays (r, and z of kLast) are 16-byte aligned; the library's always are.
+template <typename T, Mode M, bool AL>
+__device__ __forceinline__ void put_z(T *zi, T *out, T *p, long long e, int cnt, const T (&rv)[kPack<T>], const T (&zv)[kPack<T>], double &acc)
+{
+    if constexpr (M == kInner) store_pack<T, true>(zi, e, cnt, zv);
+    else if constexpr (M == kLast) store_pack<T, AL>(out, e, cnt, zv);
+    else {
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc += (double)rv[j] * (double)zv[j];
+        store_pack<T, true>(out, e, cnt, zv);
+        if constexpr (M == kSolveStart) store_pack<T, true>(p, e, cnt, zv);
+    }
+}
+
+// Step 0: d = T(c0 * double(r)), z = d.  (d is kept only where a later step reads it: kInner.)
+template <typename T, Mode M, bool AL>
+__global__ __launch_bounds__(kThreads) void cheb_first_kernel(const T *__restrict__ r, T *__restrict__ d, T *zi, T *out, T *p, long long n, double c0,
+                                                              double *__restrict__ part, const CgCell *__restrict__ cell)
+{
+    __shared__ double sh[1][kWaves];
+    if constexpr (M == kSolve)
+        if (cell->stop) return;          // (no workgroup of this kernel sets it)
+    double acc[1] = {0};
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T rv[kPack<T>], dv[kPack<T>];
+        load_pack<T, AL>(r, e, (int)cnt, rv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) dv[j] = (T)(c0 * (double)rv[j]);
+        if constexpr (M == kInner) store_pack<T, true>(d, e, (int)cnt, dv);
+        put_z<T, M, AL>(zi, out, p, e, (int)cnt, rv, dv, acc[0]);
+    }
+    if constexpr (M == kSolve || M == kSolveStart) store_partials<1>(acc, part, sh);
+}
+
+// Step k >= 1, behind q = A z: d = T(a * double(d) + b * (double(r) - double(q))), z = T(double(z) + double(d)); z is read from zi
+template <typename T, Mode M, bool AL>
+__global__ __launch_bounds__(kThreads) void cheb_step_kernel(const T *__restrict__ r, const T *__restrict__ q, T *__restrict__ d, T *zi, T *out, T *p, long long n,
+                                                             double a, double b, double *__restrict__ part, const CgCell *__restrict__ cell)
+{
+    __shared__ double sh[1][kWaves];
+    if constexpr (M == kSolve)
+        if (cell->stop) return;          // (no workgroup of this kernel sets it)
+    double acc[1] = {0};
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T rv[kPack<T>], qv[kPack<T>], dv[kPack<T>], zv[kPack<T>];
+        load_pack<T, AL>(r, e, (int)cnt, rv);
+        load_pack<T, true>(q, e, (int)cnt, qv);
+        load_pack<T, true>(d, e, (int)cnt, dv);
+        load_pack<T, true>(zi, e, (int)cnt, zv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) {
+            dv[j] = (T)(a * (double)dv[j] + b * ((double)rv[j] - (double)qv[j]));
+            zv[j] = (T)((double)zv[j] + (double)dv[j]);
+        }
+        if constexpr (M == kInner) store_pack<T, true>(d, e, (int)cnt, dv);
+        put_z<T, M, AL>(zi, out, p, e, (int)cnt, rv, zv, acc[0]);
+    }
+    if constexpr (M == kSolve || M == kSolveStart) store_partials<1>(acc, part, sh);
+}
+
+// the start vector of cvr_chebyshev_bounds: x_i = T(1 + double(uint32(i * 2654435761)) * 2^-32)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void cheb_start_kernel(T *__restrict__ x, long long n)
+{
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T xv[kPack<T>];
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) xv[j] = (T)(1.0 + (double)((uint32_t)(e + j) * 2654435761u) * 0x1p-32);
+        store_pack<T, true>(x, e, (int)cnt, xv);
+    }
+}
+
+// One apply enqueued on `st`: step 0 .. degree - 1, the last of them in mode `last` (kLast, kSolve or kSolveStart) with z going to `out`.
+// AL: r (and `out` of kLast) are 16-byte aligned.  *spmvs grows by the products enqueued.
+template <typename T, Mode LASTMODE, bool AL>
+int enqueue_apply(const cvr_precond *pc, const T *r, T *out, T *p, double *part, const CgCell *cell, hipStream_t st, int *spmvs)
+{
+    const long long n = pc->n;
+    T *zi = static_cast<T *>(pc->d_zi), *q = static_cast<T *>(pc->d_q), *d = static_cast<T *>(pc->d_d);
+    if (pc->degree == 1) {
+        launch(cheb_first_kernel<T, LASTMODE, AL>, st, r, d, zi, out, p, n, pc->b[0], part, cell);
+        HIP_TRY(hipGetLastError());
+        return CVR_OK;
+    }
+    launch(cheb_first_kernel<T, kInner, AL>, st, r, d, zi, out, p, n, pc->b[0], part, cell);
+    HIP_TRY(hipGetLastError());
+    for (int k = 1; k < pc->degree; k++) {
+        HIP_TRY(run_spmv(pc->h, zi, q, st));
+        if (spmvs) ++*spmvs;
+        if (k + 1 < pc->degree) launch(cheb_step_kernel<T, kInner, AL>, st, r, (const T *)q, d, zi, out, p, n, pc->a[k], pc->b[k], part, cell);
+        else launch(cheb_step_kernel<T, LASTMODE, AL>, st, r, (const T *)q, d, zi, out, p, n, pc->a[k], pc->b[k], part, cell);
+        HIP_TRY(hipGetLastError());
+    }
+    return CVR_OK;
+}
+
+// ---- preconditioned conjugate gradients: cvr_precond.hip's pcg_solve with the polynomial in place of W
+
+template <typename T>
+int cheb_pcg_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    const long long n = h->info.nrows;
+    const size_t    vb = sizeof(T) * (size_t)n;
+    const bool      al = (((uintptr_t)b | (uintptr_t)x) & 15u) == 0;
+
+    Arena        a;
+    const size_t op = a.add(x_ext_bytes(h)), oq = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h)), oz = a.add(vec_bytes(h));
+    const size_t opq = a.add(sizeof(double) * kBlocks), opart = a.add(sizeof(double) * 3 * kBlocks), ocell = a.add(sizeof(CgCell));
+    HIP_TRY(a.alloc());
+    const Workspace<T> w{a.at<T>(op), a.at<T>(oq), a.at<T>(orr), a.at<T>(oz), a.at<double>(opq), a.at<double>(opart), a.at<CgCell>(ocell)};
+    if (const int rc = a.begin(st)) return rc;
+
+    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then p = r and the sums r . r and b . b, z = p_d(A) r, p = z and r . z, the cell
+    if (const int rc = zero_pad_slot(w.p, vb, sizeof(T), st)) return rc;
+    if (const int rc = start_residual(h, w.p, w.r, x, b, n, st)) return rc;
+    int spmvs = 1;
+    with_flags([&](auto AL) { launch(cg_init_kernel<T, false, AL>, st, b, (const T *)nullptr, (const T *)w.r, w.z, w.p, n, w.part); }, al);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = enqueue_apply<T, kSolveStart, true>(pc, w.r, w.z, w.p, w.part + kBlocks, w.cell, st, &spmvs)) return rc;
+    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, 1, opt->rtol, w.cell);
+    HIP_TRY(hipGetLastError());
+
+    CgCell cell{};
+    const int rc = run_batches(
+        opt,
+        [&](int k) -> int {
+            HIP_TRY(run_spmv(h, w.p, w.q, st));
+            spmvs++;
+            launch(cg_pq_kernel<T>, st, w.p, w.q, n, w.part_pq, w.cell);
+            with_flags([&](auto AL) { launch(cg_update_kernel<T, false, AL>, st, x, w.r, w.z, w.p, w.q, (const T *)nullptr, n, w.part_pq, w.part, w.cell, k); }, al);
+            HIP_TRY(hipGetLastError());
+            if (const int rc = enqueue_apply<T, kSolve, true>(pc, w.r, w.z, w.p, w.part + kBlocks, w.cell, st, &spmvs)) return rc;
+            launch(cg_direction_kernel<T, true>, st, w.p, w.z, n, w.part, w.cell, k, opt->rtol);
+            HIP_TRY(hipGetLastError());
+            return CVR_OK;
+        },
+        [&](int, bool *stopped) -> int {
+            if (const int rc = read_cell(&cell, w.cell, sizeof(cell), st)) return rc;
+            *stopped = cell.stop != 0;
+            return CVR_OK;
+        });
+    if (rc) return rc;
+    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
+    return CVR_OK;
+}
+
+// ---- the object
+
+int cheb_alloc(void **out, size_t bytes, const char *what)
+{
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+    if (e == hipSuccess) return CVR_OK;
+    *out = nullptr;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_chebyshev: no device memory for %s (%zu bytes)", what, bytes);
+    return fail(CVR_ERR_HIP, "cvr_precond_chebyshev: hipMalloc of %s: %s", what, hipGetErrorString(e));
+}
+
+// the three buffers, zeroed (zi[ncols] == 0 from here on: the kernels write values 0 .. n - 1 only)
+int cheb_buffers(cvr_precond *p)
+{
+    const size_t bytes[3] = {x_ext_bytes(p->h), y_ext_bytes(p->h), vec_bytes(p->h)};
+    void       **bufs[3] = {&p->d_zi, &p->d_q, &p->d_d};
+    const char  *names[3] = {"zi", "q", "d"};
+    for (int i = 0; i < 3; i++) {
+        if (const int rc = cheb_alloc(bufs[i], bytes[i], names[i])) return rc;
+        HIP_TRY(hipMemset(*bufs[i], 0, bytes[i]));
+    }
+    HIP_TRY(hipDeviceSynchronize());          // (whatever stream the first apply comes on finds them zeroed)
+    return CVR_OK;
+}
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+int chebyshev_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st)
+{
+    const bool al = (((uintptr_t)r | (uintptr_t)z) & 15u) == 0;
+    if (p->is_f32)
+        return with_flags([&](auto AL) { return enqueue_apply<float, kLast, AL>(p, static_cast<const float *>(r), static_cast<float *>(z), (float *)nullptr, (double *)nullptr, (const CgCell *)nullptr, st, nullptr); }, al);
+    return with_flags([&](auto AL) { return enqueue_apply<double, kLast, AL>(p, static_cast<const double *>(r), static_cast<double *>(z), (double *)nullptr, (double *)nullptr, (const CgCell *)nullptr, st, nullptr); }, al);
+}
+
+int chebyshev_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    return with_value_type(h, [&](auto t) { return cheb_pcg_solve(h, p, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
+}
+
+void chebyshev_release(cvr_precond *p)
+{
+    for (void *buf : {p->d_zi, p->d_q, p->d_d})
+        if (buf) (void)hipFree(buf);
+    p->d_zi = p->d_q = p->d_d = nullptr;
+}
+
+}  // namespace krylov
+}  // namespace cvrh
+
+extern "C" {
+
+int cvr_precond_chebyshev(cvr_precond **out, cvr_handle *h, int32_t degree, double lmin, double lmax)
+{
+    if (!out || !h) return fail(CVR_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (degree < 1 || degree > CVR_CHEBYSHEV_MAX_DEGREE) return fail(CVR_ERR_INVALID, "degree = %d: must be 1 .. %d", degree, CVR_CHEBYSHEV_MAX_DEGREE);
+    if (!std::isfinite(lmin) || !std::isfinite(lmax) || !(lmin > 0) || !(lmin < lmax))
+        return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev: bounds lmin = %g, lmax = %g: must be finite with 0 < lmin < lmax", lmin, lmax);
+    if (const int rc = check_square_preprocessed(h, "cvr_precond_chebyshev", "a Chebyshev preconditioner needs")) return rc;
+    Range range("cvr_precond_chebyshev");
+    HIP_TRY(hipSetDevice(h->device));
+    cvr_precond *p = new (std::nothrow) cvr_precond;
+    if (!p) return fail(CVR_ERR_NOMEM, "out of host memory");
+    p->kind = kPrecondChebyshev;
+    p->device = h->device;
+    p->n = h->info.nrows;
+    p->bs = 0;
+    p->is_f32 = h->vsz == 4 ? 1 : 0;
+    p->h = h;
+    p->degree = degree;
+    p->lmin = lmin;
+    p->lmax = lmax;
+    // the coefficients: every operation an fp64 one of its own (the file is compiled without contraction)
+    const double theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta;
+    double       rho = 1 / sigma;
+    p->a[0] = 0;
+    p->b[0] = 1 / theta;
+    for (int k = 1; k < degree; k++) {
+        const double next = 1 / (2 * sigma - rho);
+        p->a[k] = next * rho;
+        p->b[k] = 2 * next / delta;
+        rho = next;
+    }
+    if (const int rc = cheb_buffers(p)) {
+        cvr_precond_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return CVR_OK;
+}
+
+int cvr_precond_chebyshev_info(const cvr_precond *p, cvr_chebyshev_info *info)
+{
+    if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondChebyshev) return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev_info: the preconditioner is of kind %d (block-Jacobi), not a Chebyshev object", p->kind);
+    memset(info, 0, sizeof(*info));
+    info->degree = p->degree;
+    info->is_f32 = p->is_f32;
+    info->lmin = p->lmin;
+    info->lmax = p->lmax;
+    for (int k = 0; k < p->degree; k++) {
+        info->a[k] = p->a[k];
+        info->b[k] = p->b[k];
+    }
+    return CVR_OK;
+}
+
+int cvr_chebyshev_bounds(cvr_handle *h, int32_t power_iters, double eig_ratio, double *lmin, double *lmax, void *stream)
+{
+    if (!h || !lmin || !lmax) return fail(CVR_ERR_INVALID, "null argument");
+    if (power_iters < 0) return fail(CVR_ERR_INVALID, "cvr_chebyshev_bounds: power_iters = %d: must not be negative", power_iters);
+    if (!std::isfinite(eig_ratio) || !(eig_ratio > 1)) return fail(CVR_ERR_INVALID, "cvr_chebyshev_bounds: eig_ratio = %g: must be finite and > 1", eig_ratio);
+    if (const int rc = check_square_preprocessed(h, "cvr_chebyshev_bounds", "the bounds need")) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    const hipStream_t st = (hipStream_t)stream;
+    const long long   n = h->info.nrows;
+    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } x;
+    HIP_TRY(hipMalloc(&x.p, x_ext_bytes(h)));
+    HIP_TRY(hipMemsetAsync(x.p, 0, x_ext_bytes(h), st));
+    if (h->vsz == 4) launch(cheb_start_kernel<float>, st, static_cast<float *>(x.p), n);
+    else launch(cheb_start_kernel<double>, st, static_cast<double *>(x.p), n);
+    HIP_TRY(hipGetLastError());
+    double lambda = 0, seconds = 0;
+    if (const int rc = cvr_power_iteration(h, nullptr, nullptr, power_iters, x.p, &lambda, &seconds, stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));          // (the buffer is released behind everything that reads it)
+    if (!std::isfinite(lambda) || !(lambda > 0)) return fail(CVR_ERR_STATE, "cvr_chebyshev_bounds: the Rayleigh quotient after %d power steps is %g: not finite or not > 0", power_iters, lambda);
+    *lmax = CVR_CHEBYSHEV_LMAX_FACTOR * lambda;
+    *lmin = *lmax / eig_ratio;
+    return CVR_OK;
+}
+
+}  // extern "C"

@@ -136,7 +136,8 @@ int check_args(const void *h, const cvr_precond *p, const void *b, const void *x
 int check_handle(const cvr_handle *h, const cvr_precond *p)
 {
     if (const int rc = check_square_preprocessed(h, "cvr_pbicgstab", "BiCGSTAB needs")) return rc;
-    return check_precond_pair(h, p, "cvr_pbicgstab");
+    if (const int rc = check_precond_pair(h, p, "cvr_pbicgstab")) return rc;
+    return check_block_jacobi(p, "cvr_pbicgstab");
 }
 
 int pbicgstab_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)

@@ -213,7 +213,8 @@ int check_pcg_multi_args(const void *h, const cvr_precond *p, const void *B, con
 int check_pcg_multi_handle(const cvr_handle *h, const cvr_precond *p, int32_t nvec, bool single)
 {
     if (const int rc = check_handle(h, nvec, single, "cvr_pcg_multi")) return rc;
-    return check_precond_pair(h, p, "cvr_pcg_multi");
+    if (const int rc = check_precond_pair(h, p, "cvr_pcg_multi")) return rc;
+    return check_block_jacobi(p, "cvr_pcg_multi");
 }
 
 // behind the checks
@@ -246,6 +247,7 @@ int cvr_precond_apply_multi_device(const cvr_precond *p, const void *R_dev, int6
     if (R_dev == Z_dev) return fail(CVR_ERR_INVALID, "cvr_precond_apply_multi_device: R and Z are the same block");
     if (nvec < 1 || nvec > kCols) return fail(CVR_ERR_INVALID, "nvec = %d: 1 to %d columns per call", nvec, kCols);
     if (ldr < nvec || ldz < nvec) return fail(CVR_ERR_INVALID, "ldr = %lld, ldz = %lld: each must be >= nvec = %d", (long long)ldr, (long long)ldz, nvec);
+    if (const int rc = check_block_jacobi(p, "cvr_precond_apply_multi_device")) return rc;
     if (p->n == 0) return CVR_OK;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(p->is_f32 ? launch_apply_multi<float>(p, R_dev, ldr, Z_dev, ldz, nvec, (hipStream_t)stream)

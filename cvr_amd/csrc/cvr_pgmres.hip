@@ -207,7 +207,8 @@ int check_args(const void *h, const cvr_precond *p, const void *b, const void *x
 int check_handle(const cvr_handle *h, const cvr_precond *p)
 {
     if (const int rc = check_square_preprocessed(h, "cvr_pgmres", "GMRES needs")) return rc;
-    return check_precond_pair(h, p, "cvr_pgmres");
+    if (const int rc = check_precond_pair(h, p, "cvr_pgmres")) return rc;
+    return check_block_jacobi(p, "cvr_pgmres");
 }
 
 int pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)

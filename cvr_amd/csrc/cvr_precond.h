@@ -1,14 +1,23 @@
-// cvr_precond.h -- the block-Jacobi object as the solvers see it, shared by cvr_precond.hip (the object, cvr_pcg_device), cvr_pbicgstab.hip and
-// cvr_pgmres.hip: the struct, the apply of one packet (every solver forms z = W r by this code, so the same r gives the same bits in all of them) and
-// the checks every preconditioned entry point makes.  How W is built and laid out: cvr_precond.hip's head.
+// cvr_precond.h -- the preconditioner object as the solvers see it, shared by cvr_precond.hip (the block-Jacobi object, cvr_pcg_device),
+// cvr_chebyshev.hip (the Chebyshev kind), cvr_pcg_multi.hip, cvr_pbicgstab.hip and cvr_pgmres.hip: the struct with its kind, the block-Jacobi apply of one
+// packet (every solver forms z = W r by this code, so the same r gives the same bits in all of them) and the checks every preconditioned entry point
+// makes.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.
 #pragma once
 #include "cvr_krylov.h"
+
+constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1;          // cvr_precond::kind
 
 struct cvr_precond {
     int      device = 0;
     int64_t  n = 0, nblocks = 0, identity_blocks = 0;
     int32_t  bs = 1, is_f32 = 0;
     void    *d_w = nullptr;          // nblocks * bs * bs values of T, every block transposed
+    int32_t  kind = kPrecondBlockJacobi;
+    // kind == kPrecondChebyshev (bs, nblocks and identity_blocks are 0, d_w is null): the borrowed handle, the polynomial, the object's three buffers
+    cvr_handle *h = nullptr;
+    int32_t     degree = 0;
+    double      lmin = 0, lmax = 0, a[CVR_CHEBYSHEV_MAX_DEGREE] = {}, b[CVR_CHEBYSHEV_MAX_DEGREE] = {};
+    void       *d_zi = nullptr, *d_q = nullptr, *d_d = nullptr;          // z between the steps (x_ext values, element ncols stays 0), q = A z (y_ext), d (n)
 };
 
 namespace cvrh {
@@ -66,6 +75,19 @@ inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const c
     return CVR_OK;
 }
 
+// ... and, behind both, the entry points that take block-Jacobi objects only
+inline int check_block_jacobi(const cvr_precond *p, const char *entry)
+{
+    if (p->kind != kPrecondBlockJacobi)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (Chebyshev): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
+    return CVR_OK;
+}
+
 }  // namespace
+
+// cvr_chebyshev.hip: the Chebyshev kind behind cvr_precond_apply_device, cvr_pcg_device / cvr_pcg (the checks are the callers') and cvr_precond_destroy
+int  chebyshev_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st);
+int  chebyshev_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st);
+void chebyshev_release(cvr_precond *p);
 }  // namespace krylov
 }  // namespace cvrh

@@ -1,5 +1,5 @@
 // cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*) and the conjugate gradients that use it (cvr_pcg_device,
-// cvr_pcg).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into LDS, inverts them there in fp64 and stores the
+// cvr_pcg); the entry points both kinds of object share hand the Chebyshev kind on to cvr_chebyshev.hip (apply, pcg_device, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into LDS, inverts them there in fp64 and stores the
 // inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for the elements CVR_KRYLOV_PACKETS gives it
 // (cvr_precond.h: the struct and the apply of one packet, shared with cvr_pbicgstab.hip and cvr_pgmres.hip).
 //   precond_build_kernel   one wavefront per workgroup; L = 8, 16 or 32 lanes per block (the power of two from bs up), 64 / L blocks per wavefront
@@ -370,6 +370,7 @@ int pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, cons
 {
     Range range("cvr_pcg_device");
     HIP_TRY(hipSetDevice(h->device));
+    if (p->kind == kPrecondChebyshev) return chebyshev_pcg_device(h, p, b, x, opt, res, st);
     return with_value_type(h, [&](auto t) { return pcg_solve(h, p, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
 }
 
@@ -418,6 +419,7 @@ int cvr_precond_get_info(const cvr_precond *p, cvr_precond_info *info)
 int cvr_precond_export(const cvr_precond *p, void *blocks_host)
 {
     if (!p || !blocks_host) return fail(CVR_ERR_INVALID, "null argument");
+    if (const int rc = check_block_jacobi(p, "cvr_precond_export")) return rc;
     if (p->nblocks == 0) return CVR_OK;
     HIP_TRY(hipSetDevice(p->device));
     const size_t vsz = p->is_f32 ? 4 : 8, bs = (size_t)p->bs, count = (size_t)p->nblocks * bs * bs;
@@ -442,6 +444,7 @@ int cvr_precond_apply_device(const cvr_precond *p, const void *r_dev, void *z_de
     if (p->n == 0) return CVR_OK;
     HIP_TRY(hipSetDevice(p->device));
     const hipStream_t st = (hipStream_t)stream;
+    if (p->kind == kPrecondChebyshev) return chebyshev_apply(p, r_dev, z_dev, st);
     const bool        al = ((uintptr_t)z_dev & 15u) == 0;
     const long long   n = p->n;
     if (p->is_f32)
@@ -458,6 +461,10 @@ int cvr_precond_destroy(cvr_precond *p)
     if (p->d_w) {
         (void)hipSetDevice(p->device);
         (void)hipFree(p->d_w);
+    }
+    if (p->kind == kPrecondChebyshev && (p->d_zi || p->d_q || p->d_d)) {
+        (void)hipSetDevice(p->device);
+        chebyshev_release(p);
     }
     delete p;
     return CVR_OK;

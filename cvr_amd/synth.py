@@ -161,6 +161,25 @@ def spd_from_pattern(n, rp, ci, c=0.5, dscale=None, dtype=np.float64):
     return n, n, out_rp, cc.astype(np.int32), val.astype(dtype)
 
 
+def laplacian_2d(m, dtype=np.float64):
+    """The 5-point Laplacian of an m x m grid with Dirichlet boundaries (n = m * m rows, 4 on the diagonal, -1 to the grid neighbours): the model
+    problem whose CG iteration count grows with the mesh.  Its spectrum is 4 - 2 cos(i pi / (m + 1)) - 2 cos(j pi / (m + 1)), i, j = 1 .. m.
+    Returns (n, n, row_ptr, col_idx, vals) like the generators above, the columns of a row ascending."""
+    n = m * m
+    i, j = np.divmod(np.arange(n, dtype=np.int64), m)
+    rows, cols, vals = [], [], []
+    for ok, off, v in ((i > 0, -m, -1.0), (j > 0, -1, -1.0), (np.ones(n, dtype=bool), 0, 4.0), (j < m - 1, 1, -1.0), (i < m - 1, m, -1.0)):
+        r = np.flatnonzero(ok)
+        rows.append(r)
+        cols.append(r + off)
+        vals.append(np.full(len(r), v))
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    order = np.lexsort((cols, rows))
+    rp = np.zeros(n + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return n, n, rp, cols[order].astype(np.int32), vals[order].astype(dtype)
+
+
 def block_diag_spd(n, bs, cond=1e3, seed=11, dtype=np.float64):
     """An exactly block-diagonal symmetric positive definite matrix (the block-Jacobi preconditioner's test family): dense blocks of bs rows (the last
     one shorter when bs does not divide n), each Q diag(lambda) Q^T with a random orthogonal Q and eigenvalues spread log-uniformly over [1, cond] --

@@ -634,6 +634,60 @@ int cvr_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void 
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pcg(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* ---- a second kind of cvr_precond: the Chebyshev polynomial preconditioner, z = p_d(A) r ---------------
+ * For a symmetric positive definite A whose spectrum lies in [lmin, lmax], p_d is the polynomial of `degree` terms (degree - 1 in A) of the Chebyshev
+ * iteration for A z = r started from 0: the apply is degree - 1 products through cvr_spmv_device's launch path, each followed by one fused
+ * element-wise kernel; it forms no dot product, and its scalars are constants the host computes once.  Block-Jacobi objects are kind 0 and unchanged;
+ * this is kind 1.
+ * The object borrows `h`, which must outlive it: a preprocessed, square, single-GPU handle of any layout, fp64 or fp32.  Its n, type and device are
+ * the handle's.  It owns three device buffers: zi of info.x_elems values, whose element ncols stays 0, q of info.yext_elems values and d of n values.
+ * Because it owns these buffers, one object serves one stream at a time: two applies or solves with the same object must not be in flight on
+ * different streams.  A mutable handle's new values (cvr_update_values) are followed automatically, every product being the handle's own; the bounds
+ * stay as given.
+ * Arithmetic, T = the handle's type, scalars fp64, every operation rounded on its own (no fused multiply-add).  On the host, once
+ * (cvr_precond_chebyshev_info returns all of it):
+ *     theta = (lmax + lmin) / 2;  delta = (lmax - lmin) / 2;  sigma = theta / delta;  rho_0 = 1 / sigma;  c0 = 1 / theta;
+ *     for k = 1 .. degree-1:  rho_k = 1 / (2 * sigma - rho_(k-1));  a[k] = rho_k * rho_(k-1);  b[k] = 2 * rho_k / delta;      a[0] = 0, b[0] = c0.
+ *   Step 0:       d = T(c0 * double(r));  z = d.
+ *   Step k >= 1:  q = A z through cvr_spmv_device's launch path (bit for bit its y for the same z);
+ *                 d = T(a[k] * double(d) + b[k] * (double(r) - double(q)));  z = T(double(z) + double(d)).
+ *   The last step writes z to the caller's array, earlier steps to the object's zi.  The kernels run on the solvers' grid (1024 workgroups of 256
+ *   threads, a thread over its 16-byte packets in order); the result has the same bits every call and for every alignment of r_dev and z_dev.
+ * cvr_precond_apply_device takes this kind: it enqueues degree - 1 SpMVs and degree vector launches on `stream`, and only enqueues.
+ * cvr_pcg_device and cvr_pcg take this kind: everything cvr_pcg_device's text above fixes holds with this apply in place of z = W r.  The last kernel
+ *   of an apply adds the terms of r.z into set 1 as the block-Jacobi apply does (the thread that owns element i, in element order), writes p = z at
+ *   the start, and writes nothing once the state cell holds a stop; the earlier kernels and the SpMVs of an apply touch only the object's buffers.
+ *   So x, iterations, status, residual_norm and b_norm do not depend on check_every.  spmv_count = 1 + (degree - 1) + degree * (steps enqueued);
+ *   3 + degree vector launches per step.  The contract that follows: on an fp64 handle with degree = 1 the result is bit for bit cvr_cg_device's
+ *   with minv_dev = n copies of c0.  The handle of the solve may be another one than the object's (same n, type and device: cvr_pcg_device's three
+ *   checks): the polynomial is then in the object's matrix.
+ *   Bounds that do not enclose the spectrum (lmax too small) make p_d(A) indefinite: r.z or p.q turns negative and the solve ends as
+ *   CVR_CG_BREAKDOWN or runs to CVR_CG_MAX_ITERS; it never reports a wrong x as converged, the stop test being on ||r||.
+ * cvr_precond_get_info works for both kinds: for this one block_size, nblocks and identity_blocks are 0.  cvr_precond_destroy frees the buffers.
+ * cvr_precond_export, cvr_precond_apply_multi_device, cvr_pcg_multi_device / cvr_pcg_multi, cvr_pbicgstab_device / cvr_pbicgstab and
+ * cvr_pgmres_device / cvr_pgmres take block-Jacobi objects only: for this kind they return CVR_ERR_STATE behind their other checks, with
+ * cvr_last_error naming the kind.
+ * Errors of cvr_precond_chebyshev, before any device work: a null argument; degree outside 1 .. CVR_CHEBYSHEV_MAX_DEGREE; bounds that are not finite
+ * or not 0 < lmin < lmax: CVR_ERR_INVALID.  Before cvr_preprocess: CVR_ERR_STATE.  nrows != ncols: CVR_ERR_INVALID.  No device memory:
+ * CVR_ERR_NOMEM, nothing left allocated.  cvr_precond_chebyshev_info: a null argument, or a block-Jacobi object: CVR_ERR_INVALID. */
+#define CVR_CHEBYSHEV_MAX_DEGREE 16
+typedef struct {
+    int32_t degree, is_f32;
+    double  lmin, lmax;
+    double  a[CVR_CHEBYSHEV_MAX_DEGREE], b[CVR_CHEBYSHEV_MAX_DEGREE];   /* entries from `degree` on are 0 */
+} cvr_chebyshev_info;
+int cvr_precond_chebyshev(cvr_precond **out, cvr_handle *h, int32_t degree, double lmin, double lmax);
+int cvr_precond_chebyshev_info(const cvr_precond *p, cvr_chebyshev_info *info);
+/* Bounds for it from a few power steps.  The start vector is x_i = T(1 + double(uint32(i * 2654435761)) * 2^-32) (the product taken modulo 2^32) in
+ * a buffer of the library; cvr_power_iteration(h, NULL, NULL, power_iters, ...) runs from it on `stream` and gives lambda; then
+ * *lmax = CVR_CHEBYSHEV_LMAX_FACTOR * lambda and *lmin = *lmax / eig_ratio.  The Rayleigh quotient is a lower bound of lambda_max for a symmetric
+ * A, hence the margin; the factor 1.1 and the usual eig_ratio = 30 are the convention of hypre and Ifpack2.  Synchronises `stream`.
+ * Errors: a null h, lmin or lmax; power_iters < 0; eig_ratio not finite or not > 1: CVR_ERR_INVALID, before any device work.  Then
+ * cvr_power_iteration's (before cvr_preprocess: CVR_ERR_STATE; not square: CVR_ERR_INVALID).  lambda not finite or not > 0 (power_iters = 0, an
+ * indefinite or zero matrix): CVR_ERR_STATE, *lmin and *lmax untouched. */
+#define CVR_CHEBYSHEV_LMAX_FACTOR 1.1
+int cvr_chebyshev_bounds(cvr_handle *h, int32_t power_iters, double eig_ratio, double *lmin, double *lmax, void *stream);
+
 /* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
