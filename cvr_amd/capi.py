@@ -107,6 +107,11 @@ class ChebyshevInfo(C.Structure):
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
+class LsqrInfo(C.Structure):
+    """cvr_lsqr_info"""
+    _fields_ = [("arnorm", C.c_double), ("anorm", C.c_double), ("stop_test", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -120,7 +125,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
-           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres",
+           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -194,6 +199,8 @@ def lib():
         L.cvr_pbicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_pgmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pgmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_lsqr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo), C.c_void_p]
+        L.cvr_lsqr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -872,6 +879,36 @@ class CvrMatrix:
         b, x = self._host_vectors(b, x0)
         res = self._solve("cvr_pbicgstab", self._cg_options(rtol, max_iters, check_every, None), (precond._p, b.ctypes.data, x.ctypes.data))
         return x[: self.nrows], res
+
+    def lsqr(self, at, b_ptr, x_ptr, damp=0.0, rtol=None, max_iters=None, check_every=0, stream=None):
+        """min ||b - A x||_2 (damp > 0: with the Tikhonov term damp^2 ||x - x0||^2) by LSQR on the device (cvr_lsqr_device) for A of any shape:
+        `at` is a CvrMatrix of A^T (transpose=1 on the same CSR; self for a square symmetric A), b_ptr a device array of nrows values, x_ptr one
+        of ncols values (the start vector in, the solution out).  Returns (CgResult, LsqrInfo); synchronises the stream."""
+        res, info = CgResult(), LsqrInfo()
+        opt = self._cg_options(rtol, max_iters, check_every, None)
+        rc = lib().cvr_lsqr_device(self._h, at._h, b_ptr, x_ptr, float(damp), C.byref(opt), C.byref(res), C.byref(info), stream)
+        if rc:
+            raise CvrError(rc, "cvr_lsqr_device")
+        return res, info
+
+    def lsqr_host(self, at, b, x0=None, damp=0.0, rtol=None, max_iters=None, check_every=0):
+        """the same through host arrays (cvr_lsqr): b of nrows values and the start vector x0 (None: zero) of ncols values.  Returns
+        (x, CgResult, LsqrInfo)."""
+        b = np.ascontiguousarray(b, dtype=self.dtype)
+        if len(b) < self.nrows:
+            raise ValueError("b is shorter than nrows")
+        x = np.zeros(max(self.ncols, 1), dtype=self.dtype)
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=self.dtype)
+            if len(x0) < self.ncols:
+                raise ValueError("x0 is shorter than ncols")
+            x[: self.ncols] = x0[: self.ncols]
+        res, info = CgResult(), LsqrInfo()
+        opt = self._cg_options(rtol, max_iters, check_every, None)
+        rc = lib().cvr_lsqr(self._h, at._h, b.ctypes.data, x.ctypes.data, float(damp), C.byref(opt), C.byref(res), C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_lsqr")
+        return x[: self.ncols], res, info
 
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
         """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device

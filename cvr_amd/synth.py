@@ -131,6 +131,28 @@ def banded_sym(n, half_band=13, seed=7, dtype=np.float64):
     return n, n, rp, cols.astype(np.int32), vals
 
 
+def rect_banded(m, n, half_band=2, extra=0, seed=17, dtype=np.float64):
+    """An m x n least-squares test matrix of full rank min(m, n) (the LSQR probe's shapes): row i has a dominant entry in [1, 2) at its
+    diagonal-like column d_i = i * n // m (m >= n; i itself when m < n), entries in [-0.5, 0.5) / (2 half_band + extra) at the columns
+    d_i - half_band .. d_i + half_band that exist, and `extra` more of them at random columns (duplicates dropped).  Columns of a row
+    ascending.  Returns (m, n, row_ptr, col_idx, vals) like the generators above."""
+    rng = np.random.default_rng(seed)
+    i = np.arange(m, dtype=np.int64)
+    d = i * n // m if m >= n else i
+    offs = np.arange(-half_band, half_band + 1, dtype=np.int64)
+    rows = np.concatenate([np.repeat(i, len(offs)), np.repeat(i, extra)])
+    cols = np.concatenate([(d[:, None] + offs[None, :]).reshape(-1), rng.integers(0, n, size=m * extra)])
+    ok = (cols >= 0) & (cols < n)
+    key, first = np.unique(rows[ok] * np.int64(n) + cols[ok], return_index=True)
+    r, c = key // n, key % n
+    vals = (rng.random(len(key)) - 0.5) / max(2 * half_band + extra, 1)
+    on = c == d[r]
+    vals[on] = 1.0 + rng.random(int(on.sum()))
+    rp = np.zeros(m + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(r, minlength=m))
+    return m, n, rp, c.astype(np.int32), vals.astype(dtype)
+
+
 def spd_from_pattern(n, rp, ci, c=0.5, dscale=None, dtype=np.float64):
     """A symmetric positive definite matrix with a known condition bound from any square pattern (the solver's test matrices):
     W = P u P^T without the diagonal and without duplicates, d_i = the degree of vertex i in W, A = I + c D^-1/2 W D^-1/2.  The normalised

@@ -425,7 +425,8 @@ typedef struct {
 #define CVR_CG_MAX_ITERS 1
 #define CVR_CG_BREAKDOWN 2    /* CG: p.Ap <= 0 or not finite: A is not positive definite on the Krylov space;
                                  BiCGSTAB: r^.v, t.t, omega or r^.r zero or not finite;
-                                 GMRES: a cycle's start residual not finite, or rho zero or not finite          */
+                                 GMRES: a cycle's start residual not finite, or rho zero or not finite;
+                                 LSQR: beta, alpha, rho or phi / rho not finite, or rho zero                     */
 
 typedef struct {
     int32_t iterations;       /* steps applied to x (BiCGSTAB: a stop at the half step counts as one)     */
@@ -755,6 +756,66 @@ int cvr_pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, vo
                       void *stream);
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pgmres(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
+
+/* ---- least squares on the device: LSQR ------------------------------------------------------------------
+ * min ||b - A x||_2 over x for A of any shape and rank -- over- and under-determined and rank-deficient systems included --, and with damp > 0
+ * min ||b - A x||^2 + damp^2 ||x - x0||^2 (Tikhonov): LSQR of Paige and Saunders (ACM TOMS 8, 1982), the Golub-Kahan bidiagonalisation with one
+ * product by A and one by A^T per step.  From x0 = 0 it converges to the solution of least 2-norm. */
+typedef struct {
+    double  arnorm;     /* estimate of ||A^T r - damp^2 (x - x0)||_2 at the stop                 */
+    double  anorm;      /* running Frobenius estimate of [A; damp I]                             */
+    int32_t stop_test;  /* 0: none (max_iters / breakdown); 1: residual test; 2: normal-equations test */
+    int32_t reserved;
+} cvr_lsqr_info;
+/* a: the single-GPU handle of A, m x n (any layout).  at: a handle of A^T, n x m, of the same value type on the same device -- usually cvr_create
+ * with cvr_options.transpose = 1 on the CSR that made `a`; a == at for a square symmetric A.  The library checks shapes, type and device; that `at`
+ * holds A^T is the caller's promise.  b_dev: m values of the handles' type, x_dev: n values, the start vector x0 on entry and the solution on exit;
+ * neither needs a pad element or a scratch tail.  The options, the result and the status codes are cvr_cg_device's; opt->minv_dev must be NULL.
+ * info may be NULL.  The buffers of the call are the library's, allocated per call: v (a's info.x_elems values, v[n] == 0), u^ (the larger of a's
+ * info.yext_elems and m + 1 values: the output of a's scaled product and the input of at's product, u^[m] == 0), q (a's info.yext_elems), p (at's
+ * info.yext_elems) and w (n values).
+ * Arithmetic, T = the handles' type, every operation below rounded on its own (no fused multiply-add); every scalar is fp64; u is kept unnormalised,
+ * u^ = beta u (A^T u^ = beta A^T u, so no pass divides u^ by its norm); v is kept normalised:
+ *   start: u^ = b - A x0 by one cvr_spmv_scaled_device on `a` with alpha = -1, beta = 1 (in T);  bnorm = sqrt(b.b);  beta = sqrt(u^.u^);
+ *     p = A^T u^ through cvr_spmv_device's launch path on `at`;  v^ = T(double(p) / beta);  alpha = sqrt(v^.v^);  v = T(double(v^) / alpha);  w = v;
+ *     rhobar = alpha;  phibar = beta;  anorm2 = 0;  psi2 = 0;  rnorm = beta;  arnorm = alpha * beta;  anorm = 0.
+ *   per step: q = A v through cvr_spmv_device's launch path on `a` (bit for bit its y for the same v);
+ *     u^ = T(double(q) - (alpha / beta) * double(u^));  beta' = sqrt(u^.u^);
+ *     p = A^T u^ (the same path on `at`);  if beta' != 0: v^ = T(double(p) / beta' - beta' * double(v));  alpha' = sqrt(v^.v^), or 0 when beta' == 0;
+ *     anorm2 = anorm2 + ((alpha * alpha + beta' * beta') + damp * damp);
+ *     if damp > 0: rhobar1 = sqrt(rhobar * rhobar + damp * damp);  psi = (damp / rhobar1) * phibar;  phibar = (rhobar / rhobar1) * phibar;
+ *       else rhobar1 = rhobar;  psi = 0;
+ *     rho = sqrt(rhobar1 * rhobar1 + beta' * beta');  c = rhobar1 / rho;  s = beta' / rho;  theta = s * alpha';  rhobar = -c * alpha';
+ *     phi = c * phibar;  phibar = s * phibar;
+ *     x = T(double(x) + (phi / rho) * double(w));
+ *     psi2 = psi2 + psi * psi;  rnorm = sqrt(phibar * phibar + psi2);  arnorm = alpha' * |s * phi|;  anorm = sqrt(anorm2);
+ *     the stop tests;  then v = T(double(v^) / alpha');  w = T(double(v) - (theta / rho) * double(w));  alpha = alpha';  beta = beta'.
+ *   The sums b.b, u^.u^ and v^.v^ are accumulated in fp64 from the rounded T values in cvr_cg_device's fixed tree (1024 workgroups of 256 threads,
+ *   each thread over its 16-byte packets in order, then lanes, wavefronts and workgroups in a fixed order; no atomics): a call gives the same bits
+ *   every time, whatever the alignment of b_dev and x_dev.
+ * Stop rule, evaluated on the device after every step, with rnorm, arnorm and anorm all finite (a norm that is not finite never counts as converged):
+ *   test 1: rnorm <= rtol * bnorm;  else test 2: arnorm <= (rtol * anorm) * rnorm.  Either is CVR_CG_CONVERGED with info->stop_test = 1 or 2.  The
+ *   step that finds the stop has applied its update of x; it writes neither v nor w.
+ *   beta', alpha', rho or phi / rho not finite, or rho == 0: CVR_CG_BREAKDOWN, found before x is touched, so x, iterations, residual_norm and info
+ *   stay at the last iterate's.  beta' == 0 or alpha' == 0 is no breakdown: the formulas then end in test 1 or test 2.
+ *   At the start, in this order: b == 0: x = 0, 0 iterations, converged, residual_norm = 0 (stop_test 0);  beta not finite: CVR_CG_BREAKDOWN;
+ *   beta <= rtol * bnorm: converged by test 1;  (each of these three with arnorm = 0, since alpha is not looked at;)  alpha not finite:
+ *   CVR_CG_BREAKDOWN;  alpha == 0: converged by test 2.  All with 0 iterations, x untouched (but for b == 0), residual_norm = beta, anorm = 0.  A NaN
+ *   or an Inf in b makes beta not finite.
+ *   max_iters steps without a stop: CVR_CG_MAX_ITERS with x the last iterate.  max_iters = 0 forms and tests the start only (spmv_count == 2).
+ * residual_norm is rnorm, the recurrence's estimate of sqrt(||b - A x||^2 + damp^2 ||x - x0||^2); b_norm is bnorm.
+ * check_every: as for cvr_cg_device -- x, iterations, status, residual_norm, b_norm and info are bit for bit the same for every check_every; only
+ * spmv_count (2 + 2 per step enqueued) and seconds differ.  Three vector launches beside the two SpMVs per step.
+ * Ordering: as cvr_cg_device on both handles; makes their device current.
+ * Errors, in this order.  Before any device work and before a handle is looked at: cvr_cg_device's argument checks (on a, b, x, opt, res); at
+ * null; opt->minv_dev != NULL ("minv_dev" in cvr_last_error); damp negative or not finite ("damp"): CVR_ERR_INVALID.  Then: either handle before
+ * cvr_preprocess: CVR_ERR_STATE; at's nrows != a's ncols or at's ncols != a's nrows: CVR_ERR_INVALID; different value types or devices:
+ * CVR_ERR_INVALID. */
+int cvr_lsqr_device(cvr_handle *a, cvr_handle *at, const void *b_dev, void *x_dev, double damp, const cvr_cg_options *opt, cvr_cg_result *res,
+                    cvr_lsqr_info *info, void *stream);
+/* the same with host b (m values) and x (n values; in and out): copied up, cvr_lsqr_device on a's stream, x copied back */
+int cvr_lsqr(cvr_handle *a, cvr_handle *at, const void *b_host, void *x_host, double damp, const cvr_cg_options *opt, cvr_cg_result *res,
+             cvr_lsqr_info *info);
 
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
