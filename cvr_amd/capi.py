@@ -112,6 +112,11 @@ class LsqrInfo(C.Structure):
     _fields_ = [("arnorm", C.c_double), ("anorm", C.c_double), ("stop_test", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MinresInfo(C.Structure):
+    """cvr_minres_info"""
+    _fields_ = [("anorm", C.c_double), ("acond", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -125,7 +130,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
-           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr",
+           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -201,6 +206,8 @@ def lib():
         L.cvr_pgmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_lsqr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo), C.c_void_p]
         L.cvr_lsqr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo)]
+        L.cvr_minres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo), C.c_void_p]
+        L.cvr_minres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -909,6 +916,27 @@ class CvrMatrix:
         if rc:
             raise CvrError(rc, "cvr_lsqr")
         return x[: self.ncols], res, info
+
+    def minres(self, b_ptr, x_ptr, shift=0.0, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
+        """solves (A - shift I) x = b for a symmetric A, indefinite ones included, by MINRES on the device (cvr_minres_device): the arguments are
+        cg's (minv_ptr: an optional positive diagonal preconditioner).  Returns (CgResult, MinresInfo); synchronises the stream."""
+        res, info = CgResult(), MinresInfo()
+        opt = self._cg_options(rtol, max_iters, check_every, minv_ptr)
+        rc = lib().cvr_minres_device(self._h, b_ptr, x_ptr, float(shift), C.byref(opt), C.byref(res), C.byref(info), stream)
+        if rc:
+            raise CvrError(rc, "cvr_minres_device")
+        return res, info
+
+    def minres_host(self, b, x0=None, shift=0.0, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
+        """the same through host arrays (cvr_minres): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device pointer.
+        Returns (x, CgResult, MinresInfo)."""
+        b, x = self._host_vectors(b, x0)
+        res, info = CgResult(), MinresInfo()
+        opt = self._cg_options(rtol, max_iters, check_every, minv_ptr)
+        rc = lib().cvr_minres(self._h, b.ctypes.data, x.ctypes.data, float(shift), C.byref(opt), C.byref(res), C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_minres")
+        return x[: self.nrows], res, info
 
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
         """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device

@@ -426,7 +426,8 @@ typedef struct {
 #define CVR_CG_BREAKDOWN 2    /* CG: p.Ap <= 0 or not finite: A is not positive definite on the Krylov space;
                                  BiCGSTAB: r^.v, t.t, omega or r^.r zero or not finite;
                                  GMRES: a cycle's start residual not finite, or rho zero or not finite;
-                                 LSQR: beta, alpha, rho or phi / rho not finite, or rho zero                     */
+                                 LSQR: beta, alpha, rho or phi / rho not finite, or rho zero;
+                                 MINRES: alfa or phi / gamma not finite, r2.z negative or not finite, or gamma zero or not finite */
 
 typedef struct {
     int32_t iterations;       /* steps applied to x (BiCGSTAB: a stop at the half step counts as one)     */
@@ -816,6 +817,60 @@ int cvr_lsqr_device(cvr_handle *a, cvr_handle *at, const void *b_dev, void *x_de
 /* the same with host b (m values) and x (n values; in and out): copied up, cvr_lsqr_device on a's stream, x copied back */
 int cvr_lsqr(cvr_handle *a, cvr_handle *at, const void *b_host, void *x_host, double damp, const cvr_cg_options *opt, cvr_cg_result *res,
              cvr_lsqr_info *info);
+
+/* ---- symmetric indefinite systems on the device: MINRES -------------------------------------------------------
+ * (A - shift I) x = b for a symmetric A, definite or not, singular consistent systems included: MINRES of Paige and Saunders (SIAM J. Numer. Anal. 12,
+ * 1975), the symmetric Lanczos process with one Givens rotation per step -- one SpMV per step, a fixed number of vectors, and a residual norm that
+ * does not increase from step to step.  (cvr_cg_device ends in CVR_CG_BREAKDOWN on an indefinite A; GMRES(m) and LSQR solve it without using the
+ * symmetry.) */
+typedef struct {
+    double  anorm;        /* sqrt of the running sum of alfa^2 + oldb^2 + beta'^2: Frobenius estimate of the tridiagonal */
+    double  acond;        /* gmax / gmin over the steps' gamma                                                          */
+    int32_t reserved[2];
+} cvr_minres_info;        /* 24 bytes */
+/* h: any single-GPU handle of a square A (any layout; fused-preprocess, image-cache, mutable and transposed handles included, as for cvr_cg_device).
+ * That A is symmetric is the caller's promise: the library does not check it.  b_dev and x_dev: nrows values each of the handle's type; x_dev is the
+ * start vector on entry and the solution on exit; neither needs a pad element or a scratch tail.  shift: any finite value.  The options, the result
+ * and the status codes are cvr_cg_device's.  opt->minv_dev is an optional diagonal preconditioner M^-1 (nrows values) and must be positive: the
+ * caller's promise; a violation that makes r2.z negative is reported as a breakdown (below).  A cvr_precond object is deliberately not taken, and
+ * there is no cvr_pminres: MINRES needs a symmetric positive definite M, and the block-Jacobi of an indefinite A is not one.  info may be NULL.
+ * The buffers of the call are the library's, one allocation per call: v (info.x_elems values, v[n] == 0), q = A v (info.yext_elems), two r, two w
+ * (zeroed at the start), z only with minv_dev, the partial sums and the state cell.
+ * Arithmetic, T = the handle's type, every operation below rounded on its own (no fused multiply-add); every scalar is fp64:
+ *   start: r2 = b - A x0 by one cvr_spmv_scaled_device with alpha = -1, beta = 1 (in T), and with shift != 0 then r2 = T(double(r2) + shift * double(x0)):
+ *     the residual of A - shift I;  z = T(double(minv) * double(r2)), or z is r2 itself without minv_dev;  b_norm = sqrt(b . T(double(minv) * double(b))), the norm the residual is measured in (sqrt(b.b) without minv_dev);  beta = sqrt(r2.z);
+ *     v = T(double(z) / beta);  w1 = w2 = 0;  oldb = 0, dbar = 0, epsln = 0, phibar = beta, cs = -1, sn = 0, tnorm2 = 0, gmax = 0, gmin = DBL_MAX.
+ *   step k: q = A v through cvr_spmv_device's launch path (bit for bit its y for the same v);
+ *     y' = T((double(q) - shift * double(v)) - (beta / oldb) * double(r1))  (no shift term when shift == 0, no r1 term at k = 0);  alfa = v.y';
+ *     y = T(double(y') - (alfa / beta) * double(r2));  r1 <- r2, r2 <- y;  z = T(double(minv) * double(r2));  beta' = sqrt(r2.z);
+ *     tnorm2 = tnorm2 + ((alfa * alfa + oldb * oldb) + beta' * beta');
+ *     oldeps = epsln;  delta = cs * dbar + sn * alfa;  gbar = sn * dbar - cs * alfa;  epsln = sn * beta';  dbar = -cs * beta';
+ *     gamma = sqrt(gbar * gbar + beta' * beta');  cs = gbar / gamma;  sn = beta' / gamma;  phi = cs * phibar;  phibar = sn * phibar;
+ *     w = T(((double(v) - oldeps * double(w1)) - delta * double(w2)) / gamma);  x = T(double(x) + phi * double(w));  w1 <- w2, w2 <- w;
+ *     gmax = max(gmax, gamma);  gmin = min(gmin, gamma);  rnorm = phibar;  the stop test;  then v = T(double(z) / beta'), oldb = beta, beta = beta'.
+ *   The sums b.b, b.T(minv b), r2.z and v.y' are accumulated in fp64 from the rounded T values in cvr_cg_device's fixed tree (1024 workgroups of 256
+ *   threads, each thread over its 16-byte packets in order, then lanes, wavefronts and workgroups in a fixed order; no atomics): a call gives the same
+ *   bits every time, whatever the alignment of b_dev, x_dev and minv_dev.
+ * Stop rule, evaluated on the device after every step and once at the start:
+ *   rnorm finite and rnorm <= rtol * b_norm is CVR_CG_CONVERGED.  The step that finds it has applied its update of x and writes no v.  beta' == 0 is no
+ *   breakdown: it makes phibar 0, which ends in this test even at rtol = 0.
+ *   alfa not finite, r2.z negative or not finite (M not positive definite, or a NaN), gamma zero or not finite, or phi / gamma not finite:
+ *   CVR_CG_BREAKDOWN, found before x is touched, so x, iterations, residual_norm and info stay at the last iterate's.
+ *   At the start, in this order: b.b == 0: x = 0, 0 iterations, converged, residual_norm = 0;  r2.z negative or not finite: CVR_CG_BREAKDOWN with 0
+ *   iterations and x untouched (residual_norm = sqrt(r2.z), not finite or NaN);  beta <= rtol * b_norm: converged with 0 iterations and x untouched.  A NaN
+ *   or an Inf in b makes r2.z not finite.  After the start info->anorm = 0 and info->acond = 0; after a step anorm = sqrt(tnorm2), acond = gmax / gmin
+ *   (oldb of step 1 is the start's beta, so tnorm2 carries r2.z of the start, as in Paige and Saunders' own code).
+ *   max_iters steps without a stop: CVR_CG_MAX_ITERS with x the last iterate.  max_iters = 0 forms and tests the start only (spmv_count == 1).
+ * residual_norm is rnorm = phibar, the recurrence's ||b - (A - shift I) x|| in the M^-1 norm (the 2-norm without minv_dev); b_norm is the same norm of b.
+ * check_every: as for cvr_cg_device -- x, iterations, status, residual_norm, b_norm and info are bit for bit the same for every check_every; only
+ * spmv_count (1 + one per step enqueued) and seconds differ.  Three vector launches beside the SpMV per step.
+ * Ordering: as cvr_cg_device; makes the handle's device current.
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks; shift not finite ("shift" in
+ * cvr_last_error): CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols: CVR_ERR_INVALID. */
+int cvr_minres_device(cvr_handle *h, const void *b_dev, void *x_dev, double shift, const cvr_cg_options *opt, cvr_cg_result *res, cvr_minres_info *info,
+                      void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg; opt->minv_dev stays a device pointer */
+int cvr_minres(cvr_handle *h, const void *b_host, void *x_host, double shift, const cvr_cg_options *opt, cvr_cg_result *res, cvr_minres_info *info);
 
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
