@@ -1,5 +1,5 @@
-// cvr_bicg_kernels.h -- the state cell and the vector kernels of BiCGSTAB, shared by cvr_bicgstab.hip (cvr_bicgstab_device) and cvr_pbicgstab.hip
-// (cvr_pbicgstab_device): both solvers run the same code, so what they have in common has the same bits.  What each kernel does: cvr_bicgstab.hip's head.
+// cvr_bicg_kernels.h -- the state cell and the vector kernels of BiCGSTAB (cvr_bicgstab.hip: cvr_bicgstab_device, cvr_pbicgstab_device).  What each
+// kernel does: cvr_bicgstab.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 

@@ -1,5 +1,5 @@
-// cvr_cg_kernels.h -- the state cell and the vector kernels of conjugate gradients, shared by cvr_cg.hip (cvr_cg_device) and cvr_precond.hip
-// (cvr_pcg_device): both solvers run the same code, so what they have in common has the same bits.  What each kernel does: cvr_cg.hip's head.
+// cvr_cg_kernels.h -- the state cell and the vector kernels of conjugate gradients (cvr_cg.hip: cvr_cg_device, cvr_pcg_device).  cvr_precond.hip and
+// cvr_chebyshev.hip include it for the cell, which their applies inside the solver read.  What each kernel does: cvr_cg.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
@@ -46,25 +46,6 @@ __global__ __launch_bounds__(kThreads) void cg_init_kernel(const T *__restrict__
         store_pack<T, true>(p, e, (int)cnt, zv);
     }
     store_partials<3>(acc, out, sh);
-}
-
-// one workgroup: the start's sums into the state cell, and the stop test of the start vector
-__global__ __launch_bounds__(kThreads) void cg_check_kernel(const double *__restrict__ part, int pre, double rtol, CgCell *__restrict__ cell)
-{
-    __shared__ double sh[3][kWaves];
-    double s[3];
-    sum_partials<3>(part, s, sh);
-    if (threadIdx.x != 0) return;
-    CgCell c;
-    c.bb = s[2]; c.bnorm = sqrt(s[2]);
-    c.rr = s[0]; c.rnorm = sqrt(s[0]);
-    c.rz[0] = pre ? s[1] : s[0]; c.rz[1] = 0;
-    c.stop = 0; c.status = CVR_CG_MAX_ITERS; c.iters = 0; c.zero_x = 0;
-    if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
-    // (an Inf in b makes both norms infinite, and Inf <= rtol * Inf holds: a residual that is not finite never counts as converged -- step 0 then
-    // finds p . q not finite and records the breakdown)
-    else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= kDblMax) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
-    *cell = c;
 }
 
 // the partial sums of p . q

@@ -1,5 +1,5 @@
-// cvr_cg_multi_kernels.h -- the state cells, the vector kernels and the host pieces of batched conjugate gradients, shared by cvr_cg_multi.hip
-// (cvr_cg_multi_device) and cvr_pcg_multi.hip (cvr_pcg_multi_device): both solvers run the same code, so what they have in common has the same bits.
+// cvr_cg_multi_kernels.h -- the state cells, the vector kernels and the host pieces of batched conjugate gradients (cvr_cg_multi.hip:
+// cvr_cg_multi_device, cvr_pcg_multi_device).  cvr_pcg_multi.hip includes it for the cells and the column walk of its k-wide apply.
 // What the kernels do and how a row's columns are walked: cvr_cg_multi.hip's head.
 #pragma once
 #include "cvr_krylov.h"
@@ -97,25 +97,6 @@ __global__ __launch_bounds__(kThreads) void cgm_init_kernel(const T *__restrict_
 #pragma unroll
     for (int c = 0; c < kCols; c++)
         if (c < nvec) store_partials<kSets>(acc[c], out + (size_t)c * kSets * kBlocks, sh[c]);
-}
-
-// one workgroup: every column's start sums into its cell, and the stop test of its start vector (cvr_cg.hip's cg_check_kernel per column)
-__global__ __launch_bounds__(kThreads) void cgm_check_kernel(const double *__restrict__ part, int pre, double rtol, int nvec, CgCell *__restrict__ cells)
-{
-    __shared__ double sh[kCols][kSets][kWaves];
-    for (int col = 0; col < nvec; col++) {
-        double s[kSets];
-        sum_partials<kSets>(part + (size_t)col * kSets * kBlocks, s, sh[col]);
-        if (threadIdx.x != 0) continue;
-        CgCell c;
-        c.bb = s[2]; c.bnorm = sqrt(s[2]);
-        c.rr = s[0]; c.rnorm = sqrt(s[0]);
-        c.rz[0] = pre ? s[1] : s[0]; c.rz[1] = 0;
-        c.stop = 0; c.status = CVR_CG_MAX_ITERS; c.iters = 0; c.zero_x = 0;
-        if (c.bb == 0) { c.zero_x = 1; c.rr = 0; c.rnorm = 0; c.status = CVR_CG_CONVERGED; c.stop = 1; }
-        else if (c.rnorm <= rtol * c.bnorm && c.rnorm <= kDblMax) { c.status = CVR_CG_CONVERGED; c.stop = 1; }
-        cells[col] = c;
-    }
 }
 
 // per column the partial sums of p . q

@@ -1,5 +1,5 @@
 // cvr_chebyshev.hip -- the Chebyshev polynomial preconditioner, the second kind of cvr_precond (include/cvr_amd.h: cvr_precond_chebyshev,
-// cvr_precond_chebyshev_info, cvr_chebyshev_bounds), and the conjugate gradients that use it.  z = p_d(A) r is the Chebyshev iteration for A z = r
+// cvr_precond_chebyshev_info, cvr_chebyshev_bounds).  z = p_d(A) r is the Chebyshev iteration for A z = r
 // from z = 0 with fixed coefficients: degree - 1 products q = A z through run_spmv (cvr_spmv_device's path) on the borrowed handle, each followed by
 // one element-wise kernel on the solvers' grid; no dot product, no read-back -- the scalars a[k], b[k] are computed once on the host.
 //   cheb_first_kernel   step 0:      d = T(c0 r), z = d
@@ -7,8 +7,9 @@
 // Both come in four modes: kInner (z goes to the object's zi: an earlier step), kLast (z goes to the caller's array: the last step of
 // cvr_precond_apply_device), kSolve and kSolveStart (the last step inside cvr_pcg_device: z goes to the solver's buffer with the partial sums of
 // r . z in set 1, what pcg_apply_kernel forms; at the start p = z too; behind a stop nothing is written).  With degree = 1 step 0 is the last.
-// The solver is cvr_precond.hip's pcg_solve with this apply between cg_update_kernel<T, false, AL> and cg_direction_kernel<T, true>
-// (cvr_cg_kernels.h: the kernels cvr_cg_device runs, unchanged): 3 + degree vector launches and degree SpMVs per step.
+// The solver is cvr_cg.hip's cg_solve, which enqueues this apply through chebyshev_cg_apply (cvr_precond.h) between cg_update_kernel<T, false, AL>
+// and cg_direction_kernel<T, true>: 3 + degree vector launches and degree SpMVs per step.  This file launches no cg_* kernel and holds no solve loop
+// (cvr_cg_kernels.h is included for the state cell the kSolve kernels read).
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
@@ -118,59 +119,6 @@ int enqueue_apply(const cvr_precond *pc, const T *r, T *out, T *p, double *part,
     return CVR_OK;
 }
 
-// ---- preconditioned conjugate gradients: cvr_precond.hip's pcg_solve with the polynomial in place of W
-
-template <typename T>
-int cheb_pcg_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
-{
-    const long long n = h->info.nrows;
-    const size_t    vb = sizeof(T) * (size_t)n;
-    const bool      al = (((uintptr_t)b | (uintptr_t)x) & 15u) == 0;
-
-    Arena        a;
-    const size_t op = a.add(x_ext_bytes(h)), oq = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h)), oz = a.add(vec_bytes(h));
-    const size_t opq = a.add(sizeof(double) * kBlocks), opart = a.add(sizeof(double) * 3 * kBlocks), ocell = a.add(sizeof(CgCell));
-    HIP_TRY(a.alloc());
-    const Workspace<T> w{a.at<T>(op), a.at<T>(oq), a.at<T>(orr), a.at<T>(oz), a.at<double>(opq), a.at<double>(opart), a.at<CgCell>(ocell)};
-    if (const int rc = a.begin(st)) return rc;
-
-    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then p = r and the sums r . r and b . b, z = p_d(A) r, p = z and r . z, the cell
-    if (const int rc = zero_pad_slot(w.p, vb, sizeof(T), st)) return rc;
-    if (const int rc = start_residual(h, w.p, w.r, x, b, n, st)) return rc;
-    int spmvs = 1;
-    with_flags([&](auto AL) { launch(cg_init_kernel<T, false, AL>, st, b, (const T *)nullptr, (const T *)w.r, w.z, w.p, n, w.part); }, al);
-    HIP_TRY(hipGetLastError());
-    if (const int rc = enqueue_apply<T, kSolveStart, true>(pc, w.r, w.z, w.p, w.part + kBlocks, w.cell, st, &spmvs)) return rc;
-    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, 1, opt->rtol, w.cell);
-    HIP_TRY(hipGetLastError());
-
-    CgCell cell{};
-    const int rc = run_batches(
-        opt,
-        [&](int k) -> int {
-            HIP_TRY(run_spmv(h, w.p, w.q, st));
-            spmvs++;
-            launch(cg_pq_kernel<T>, st, w.p, w.q, n, w.part_pq, w.cell);
-            with_flags([&](auto AL) { launch(cg_update_kernel<T, false, AL>, st, x, w.r, w.z, w.p, w.q, (const T *)nullptr, n, w.part_pq, w.part, w.cell, k); }, al);
-            HIP_TRY(hipGetLastError());
-            if (const int rc = enqueue_apply<T, kSolve, true>(pc, w.r, w.z, w.p, w.part + kBlocks, w.cell, st, &spmvs)) return rc;
-            launch(cg_direction_kernel<T, true>, st, w.p, w.z, n, w.part, w.cell, k, opt->rtol);
-            HIP_TRY(hipGetLastError());
-            return CVR_OK;
-        },
-        [&](int, bool *stopped) -> int {
-            if (const int rc = read_cell(&cell, w.cell, sizeof(cell), st)) return rc;
-            *stopped = cell.stop != 0;
-            return CVR_OK;
-        });
-    if (rc) return rc;
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    double seconds = 0;
-    if (const int rc = a.seconds(st, &seconds)) return rc;
-    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
-    return CVR_OK;
-}
-
 // ---- the object
 
 int cheb_alloc(void **out, size_t bytes, const char *what)
@@ -210,10 +158,14 @@ int chebyshev_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st
     return with_flags([&](auto AL) { return enqueue_apply<double, kLast, AL>(p, static_cast<const double *>(r), static_cast<double *>(z), (double *)nullptr, (double *)nullptr, (const CgCell *)nullptr, st, nullptr); }, al);
 }
 
-int chebyshev_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+template <typename T>
+int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
 {
-    return with_value_type(h, [&](auto t) { return cheb_pcg_solve(h, p, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
+    if (start) return enqueue_apply<T, kSolveStart, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
+    return enqueue_apply<T, kSolve, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
 }
+template int chebyshev_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
+template int chebyshev_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
 
 void chebyshev_release(cvr_precond *p)
 {

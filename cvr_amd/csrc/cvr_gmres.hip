@@ -1,5 +1,6 @@
-// cvr_gmres.hip -- restarted GMRES(m) on the device for any nonsingular A (include/cvr_amd.h: cvr_gmres_device, cvr_gmres): cvr_bicgstab.hip's plan with
-// an Arnoldi basis.  Right-preconditioned; per step one SpMV through run_spmv (cvr_spmv_device's path) and five vector launches, whatever the column j:
+// cvr_gmres.hip -- restarted GMRES(m) on the device for any nonsingular A (include/cvr_amd.h: cvr_gmres_device, cvr_gmres, cvr_pgmres_device,
+// cvr_pgmres): cvr_bicgstab.hip's plan with an Arnoldi basis.  Right-preconditioned; per step one SpMV through run_spmv (cvr_spmv_device's path) and
+// five vector launches, whatever the column j:
 //   w = A z_j                  (z_j = minv .* v_j, written with v_j; v_j itself without a preconditioner)
 //   gmres_dots_kernel          the partial sums of v_i . w for i = 0..j, the columns in compile-time groups of up to 8 with w's packet loaded once per group
 //   gmres_update_kernel        h_i from those partials (summed in every workgroup, the same order everywhere); w -= sum h_i v_i in one pass over the basis
@@ -12,47 +13,120 @@
 // own 1024 partials, so its bits do not depend on the group it was formed in.  The scalars sit in a state cell (GmresCell) under BiCell's rule: thread 0
 // of workgroup 0 writes it, and a value a kernel reads is one that a kernel BEFORE it wrote.  The kernel that finds a stop records it and every later
 // kernel of the batch returns without writing, so the result does not depend on how many steps the host enqueues between two read-backs.
-// The host side is cvr_krylov.h's driver: this file adds the cell, the kernels, the step and the read-back (with the owed x in front of it).
-// (The reference has no solver: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+// The preconditioner is an argument of the one solve function: none, the diagonal opt->minv_dev (fused into the kernels above), or a block-Jacobi
+// object (cvr_pgmres*).  An element of W v needs its whole block of v, so with an object z_j = W v_j is a launch of its own (pgmres_apply_kernel, by
+// cvr_precond.h's apply_pack) behind gmres_begin_kernel and gmres_finish_kernel, which then run in their forms without a diagonal, <T, false, true>
+// (not enqueued where the host knows that no v_(j+1) is formed: the cycle's or the call's last step).  x is then formed by two launches, because W
+// needs the combination u of a whole block: pgmres_u_kernel (gmres_x_kernel's loop over the owed columns, u kept in fp64 in a buffer of n doubles)
+// and pgmres_x_kernel (x = T(double(x) + W u), the apply's sum with u where it has double(r)), both under gmres_x_kernel's guard.
+// The host side is cvr_krylov.h's driver: this file adds the step and the read-back (with the owed x in front of it); the cell and the gmres_*
+// kernels are in cvr_gmres_kernels.h.
+// (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_gmres_kernels.h"
+#include "cvr_precond.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
 
 namespace {
 
+// z = W v on the solvers' grid, v and z the library's buffers (16-byte aligned); nothing is written once the cell holds a stop (no workgroup of this
+// kernel sets it)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pgmres_apply_kernel(const T *__restrict__ wt, int bs, const T *__restrict__ v, T *__restrict__ z, long long n,
+                                                                const GmresCell *__restrict__ cell)
+{
+    if (cell->hd.stop) return;
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T zv[kPack<T>];
+        apply_pack<T>(wt, bs, v, n, e, (int)cnt, zv);
+        store_pack<T, true>(z, e, (int)cnt, zv);
+    }
+}
+
+// u of the columns the cell says are owed, when the step that said so lies in (lo, hi] (gmres_x_kernel's guard): per value u = +0, u = u + y_i double(v_i)
+// for i ascending, stored as it is, in fp64.  Reads the cell only.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pgmres_u_kernel(double *__restrict__ ubuf, const T *__restrict__ V, long long stride, long long n,
+                                                            const GmresCell *__restrict__ cell, int lo, int hi)
+{
+    __shared__ double ys[kMaxM];
+    const int q = cell->hd.owed, at = cell->hd.owed_at;
+    if (q <= 0 || at <= lo || at > hi) return;
+    for (int i = threadIdx.x; i < q; i += kThreads) ys[i] = cell->y[i];
+    __syncthreads();
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        double u[kPack<T>];
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) u[l] = 0;
+        CVR_GMRES_GROUPS(add_group, q, ys, u);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) if (l < cnt) ubuf[e + l] = u[l];
+    }
+}
+
+// ... and x from it, under the same guard: x_i = T(double(x_i) + (t_0 + t_1 + ..)), t_j = double(W[i][j]) * u[k bs + j], the apply's sum.  Reads the cell
+// only.  AL: x, the caller's array, is 16-byte aligned.
+template <typename T, bool AL>
+__global__ __launch_bounds__(kThreads) void pgmres_x_kernel(T *__restrict__ x, const T *__restrict__ wt, int bs, const double *__restrict__ ubuf, long long n,
+                                                            const GmresCell *__restrict__ cell, int lo, int hi)
+{
+    const int q = cell->hd.owed, at = cell->hd.owed_at;
+    if (q <= 0 || at <= lo || at > hi) return;
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T      xv[kPack<T>];
+        double sv[kPack<T>];
+        load_pack<T, AL>(x, e, (int)cnt, xv);
+        apply_sums<T, double>(wt, bs, ubuf, n, e, (int)cnt, sv);
+#pragma unroll
+        for (int l = 0; l < kPack<T>; l++) xv[l] = (T)((double)xv[l] + sv[l]);
+        store_pack<T, AL>(x, e, (int)cnt, xv);
+    }
+}
+
 // the library's buffers of one call: restart + 1 basis vectors and (with a preconditioner) z (x_ext each: SpMV inputs), w and r (y_ext each: r takes
-// the scaled product), the partial sums of the dots (one set per column) and of r . r, b . b and w . w, the cell
+// the scaled product), with an object u (n doubles), the partial sums of the dots (one set per column) and of r . r, b . b and w . w, the cell
 template <typename T>
 struct Workspace {
     T         *V, *z, *w, *r;
-    double    *part_h, *part_s;
+    double    *u, *part_h, *part_s;
     GmresCell *cell;
     long long  stride;          // of the basis, in values
     T         *basis(int i) const { return V + (long long)i * stride; }
 };
 
-// behind the scaled product r = b - A x: the sums and the cycle's start.  (gmres_rr_kernel reads b, the one caller's array, only at the call's start.)
+// z = W v, with an object
 template <typename T>
-hipError_t launch_begin(const Workspace<T> &w, const T *b, const T *minv, long long n, bool al, double rtol, bool first, hipStream_t st)
+void launch_apply(const Workspace<T> &w, const cvr_precond *pc, const T *v, long long n, hipStream_t st)
+{
+    launch(pgmres_apply_kernel<T>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, v, w.z, n, (const GmresCell *)w.cell);
+}
+
+// behind the scaled product r = b - A x: the sums, the cycle's start and, with an object, z_0.  (gmres_rr_kernel reads b, the one caller's array, only
+// at the call's start; beside an object gmres_begin_kernel, which reads none, runs in its aligned form.)
+template <typename T>
+hipError_t launch_begin(const Workspace<T> &w, const cvr_precond *pc, const T *b, const T *minv, long long n, bool al, double rtol, bool first, hipStream_t st)
 {
     with_flags([&](auto FIRST, auto AL) { launch(gmres_rr_kernel<T, FIRST, AL || !FIRST>, st, w.r, b, n, w.part_s, w.cell); }, first, al);
-    with_flags([&](auto PRE, auto AL) { launch(gmres_begin_kernel<T, PRE, AL>, st, w.r, minv, w.basis(0), w.z, n, w.part_s, rtol, first ? 1 : 0, w.cell); }, minv != nullptr, al);
+    with_flags([&](auto PRE, auto AL) { launch(gmres_begin_kernel<T, PRE, AL>, st, w.r, minv, w.basis(0), w.z, n, w.part_s, rtol, first ? 1 : 0, w.cell); }, minv != nullptr, al || pc);
+    if (pc) launch_apply(w, pc, w.basis(0), n, st);
     return hipGetLastError();
 }
 
-// step k with column j behind w = A z_j: the two Gram-Schmidt passes and the finish
+// step k with column j behind w = A z_j: the two Gram-Schmidt passes, the finish and, with an object, z_(j+1)
 template <typename T>
-hipError_t launch_step(const Workspace<T> &w, const T *minv, long long n, bool al, int j, int k, int m, int max_iters, double rtol, hipStream_t st)
+hipError_t launch_step(const Workspace<T> &w, const cvr_precond *pc, const T *minv, long long n, bool al, int j, int k, int m, int max_iters, double rtol, hipStream_t st)
 {
     launch(gmres_dots_kernel<T>, st, w.V, w.stride, w.w, n, j + 1, w.part_h, w.cell);
     launch(gmres_update_kernel<T, false>, st, w.V, w.stride, w.w, n, j, w.part_h, w.part_s, w.cell);
     launch(gmres_dots_kernel<T>, st, w.V, w.stride, w.w, n, j + 1, w.part_h, w.cell);
     launch(gmres_update_kernel<T, true>, st, w.V, w.stride, w.w, n, j, w.part_h, w.part_s, w.cell);
-    // (v_(j+1) and z_(j+1) are written only when j + 1 < m: basis vector m is never a column; it carries x into the scaled product.  minv is the
-    // kernel's one caller's array: without it there is no unaligned form)
+    // (v_(j+1) and z_(j+1) are written only when j + 1 < m and k + 1 < max_iters, which the host knows as well: basis vector m is never a column; it
+    // carries x into the scaled product.  A stop the finish finds is in the cell.  minv is the kernel's one caller's array: without it there is no
+    // unaligned form)
     with_flags([&](auto PRE, auto AL) { launch(gmres_finish_kernel<T, PRE, AL || !PRE>, st, w.w, minv, w.basis(j + 1), w.z, n, w.part_s, w.cell, j, k, m, max_iters, rtol); }, minv != nullptr, al);
+    if (pc && j + 1 < m && k + 1 < max_iters) launch_apply(w, pc, w.basis(j + 1), n, st);
     return hipGetLastError();
 }
 
@@ -64,47 +138,54 @@ int check_restart(int32_t restart)
 
 int check_handle(const cvr_handle *h) { return check_square_preprocessed(h, "cvr_gmres", "GMRES needs"); }
 
-// cvr_krylov.h's driver with GMRES's cycle start, step and cell
+// cvr_krylov.h's driver with GMRES's cycle start, step and cell.  pc: a block-Jacobi object or null; with one, minv is null (the entry points see to it)
 template <typename T>
-int gmres_solve(cvr_handle *h, const T *b, T *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+int gmres_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
 {
     const long long n = h->info.nrows;
     const size_t    vb = sizeof(T) * (size_t)n;
     const T        *minv = static_cast<const T *>(opt->minv_dev);
-    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0;
+    const bool      al = (((uintptr_t)b | (uintptr_t)x | (uintptr_t)minv) & 15u) == 0, has_z = minv || pc;
 
     Arena        a;
     const size_t nx = Arena::slot(x_ext_bytes(h));          // a basis vector: whole slots, so the stride is a whole number of values
-    const size_t oV = a.add((size_t)(m + 1) * nx), oz = a.add(minv ? nx : 0), ow = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h));
+    const size_t oV = a.add((size_t)(m + 1) * nx), oz = a.add(has_z ? nx : 0), ow = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h));
+    const size_t ou = a.add(pc ? sizeof(double) * (size_t)std::max<long long>(n, 1) : 0);
     const size_t oh = a.add(sizeof(double) * (size_t)m * kBlocks), os = a.add(sizeof(double) * 2 * kBlocks), ocell = a.add(sizeof(GmresCell));
     const hipError_t e = a.alloc();
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
-        return fail(CVR_ERR_NOMEM, "cvr_gmres: no device memory for %d basis vectors (%zu bytes)", m + 1, a.total());
+        return fail(CVR_ERR_NOMEM, "%s: no device memory for %d basis vectors (%zu bytes)", pc ? "cvr_pgmres" : "cvr_gmres", m + 1, a.total());
     }
     HIP_TRY(e);
-    const Workspace<T> w{a.at<T>(oV), minv ? a.at<T>(oz) : nullptr, a.at<T>(ow), a.at<T>(orr), a.at<double>(oh), a.at<double>(os), a.at<GmresCell>(ocell), (long long)(nx / sizeof(T))};
+    const Workspace<T> w{a.at<T>(oV), has_z ? a.at<T>(oz) : nullptr, a.at<T>(ow), a.at<T>(orr), pc ? a.at<double>(ou) : nullptr, a.at<double>(oh), a.at<double>(os),
+                         a.at<GmresCell>(ocell), (long long)(nx / sizeof(T))};
     if (const int rc = a.begin(st)) return rc;
 
     // the pad slots of the SpMV inputs; basis vector 1 carries x into the scaled product (it is a column only from step 1 of a cycle on), r = b;
-    // r = b - A x; then the sums, the stop test and v_0
+    // r = b - A x; then the sums, the stop test, v_0 and z_0
     for (int i = 0; i <= m; i++)
         if (const int rc = zero_pad_slot(w.basis(i), vb, sizeof(T), st)) return rc;
     if (w.z)
         if (const int rc = zero_pad_slot(w.z, vb, sizeof(T), st)) return rc;
     auto residual = [&](bool first) -> int {
         if (const int rc = start_residual(h, w.basis(1), w.r, x, b, n, st)) return rc;
-        HIP_TRY(launch_begin(w, b, minv, n, al, opt->rtol, first, st));
+        HIP_TRY(launch_begin(w, pc, b, minv, n, al, opt->rtol, first, st));
         return CVR_OK;
     };
     if (const int rc = residual(true)) return rc;
     int spmvs = 1;
 
     GmresHead hd{};
-    int       x_lo = 0;          // the steps whose finish a gmres_x_kernel has looked at
+    int       x_lo = 0;          // the steps whose finish the x-forming kernels have looked at
     auto form_x = [&](int hi) -> int {
         if (hi > x_lo) {
-            with_flags([&](auto PRE, auto AL) { launch(gmres_x_kernel<T, PRE, AL>, st, x, minv, w.V, w.stride, n, w.cell, x_lo, hi); }, minv != nullptr, al);
+            if (pc) {
+                launch(pgmres_u_kernel<T>, st, w.u, (const T *)w.V, w.stride, n, (const GmresCell *)w.cell, x_lo, hi);
+                with_flags([&](auto AL) { launch(pgmres_x_kernel<T, AL>, st, x, static_cast<const T *>(pc->d_w), (int)pc->bs, (const double *)w.u, n, (const GmresCell *)w.cell, x_lo, hi); }, al);
+            } else {
+                with_flags([&](auto PRE, auto AL) { launch(gmres_x_kernel<T, PRE, AL>, st, x, minv, w.V, w.stride, n, w.cell, x_lo, hi); }, minv != nullptr, al);
+            }
             HIP_TRY(hipGetLastError());
         }
         x_lo = hi;
@@ -119,8 +200,8 @@ int gmres_solve(cvr_handle *h, const T *b, T *x, int m, const cvr_cg_options *op
                 if (const int rc = residual(false)) return rc;
                 spmvs++;
             }
-            HIP_TRY(run_spmv(h, minv ? w.z : w.basis(j), w.w, st));
-            HIP_TRY(launch_step(w, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st));
+            HIP_TRY(run_spmv(h, w.z ? w.z : w.basis(j), w.w, st));
+            HIP_TRY(launch_step(w, pc, minv, n, al, j, k, m, opt->max_iters, opt->rtol, st));
             spmvs++;
             return CVR_OK;
         },
@@ -131,20 +212,29 @@ int gmres_solve(cvr_handle *h, const T *b, T *x, int m, const cvr_cg_options *op
             return CVR_OK;
         });
     if (rc) return rc;
-    if (hd.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    double seconds = 0;
-    if (const int rc = a.seconds(st, &seconds)) return rc;
-    fill_result(res, hd.iters, hd.status, spmvs, hd.rnorm, hd.bnorm, seconds);
-    return CVR_OK;
+    return finish_solve(a, st, x, vb, hd, spmvs, res);
 }
 
-// behind the argument checks
-int gmres_device(cvr_handle *h, const void *b, void *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+// what cvr_pgmres_device and cvr_pgmres check: the solver's arguments, the object's and the restart before the handle is looked at, then the handle
+// and the pair
+int check_pgmres(const cvr_handle *h, const cvr_precond *p, const void *b, const void *x, int32_t restart, const cvr_cg_options *opt, const cvr_cg_result *res)
 {
-    if (const int rc = check_handle(h)) return rc;
-    Range range("cvr_gmres_device");
+    if (const int rc = check_solver_args(h, b, x, opt, res)) return rc;
+    if (const int rc = check_precond_args(p, opt, "cvr_pgmres")) return rc;
+    if (const int rc = check_restart(restart)) return rc;
+    if (const int rc = check_square_preprocessed(h, "cvr_pgmres", "GMRES needs")) return rc;
+    if (const int rc = check_precond_pair(h, p, "cvr_pgmres")) return rc;
+    return check_block_jacobi(p, "cvr_pgmres");
+}
+
+// behind the argument checks (and, with an object, behind those of the handle and the pair: check_pgmres)
+int gmres_device(cvr_handle *h, const cvr_precond *pc, const void *b, void *x, int m, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
+{
+    if (!pc)
+        if (const int rc = check_handle(h)) return rc;
+    Range range(pc ? "cvr_pgmres_device" : "cvr_gmres_device");
     HIP_TRY(hipSetDevice(h->device));
-    return with_value_type(h, [&](auto t) { return gmres_solve(h, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), m, opt, res, st); });
+    return with_value_type(h, [&](auto t) { return gmres_solve(h, pc, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), m, opt, res, st); });
 }
 
 }  // namespace
@@ -155,7 +245,7 @@ int cvr_gmres_device(cvr_handle *h, const void *b_dev, void *x_dev, int32_t rest
 {
     if (const int rc = check_solver_args(h, b_dev, x_dev, opt, res)) return rc;
     if (const int rc = check_restart(restart)) return rc;
-    return gmres_device(h, b_dev, x_dev, restart, opt, res, (hipStream_t)stream);
+    return gmres_device(h, nullptr, b_dev, x_dev, restart, opt, res, (hipStream_t)stream);
 }
 
 int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res)
@@ -163,7 +253,19 @@ int cvr_gmres(cvr_handle *h, const void *b_host, void *x_host, int32_t restart, 
     if (const int rc = check_solver_args(h, b_host, x_host, opt, res)) return rc;
     if (const int rc = check_restart(restart)) return rc;
     if (const int rc = check_handle(h)) return rc;
-    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return gmres_device(h, b, x, restart, opt, res, st); });
+    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return gmres_device(h, nullptr, b, x, restart, opt, res, st); });
+}
+
+int cvr_pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void *x_dev, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res, void *stream)
+{
+    if (const int rc = check_pgmres(h, p, b_dev, x_dev, restart, opt, res)) return rc;
+    return gmres_device(h, p, b_dev, x_dev, restart, opt, res, (hipStream_t)stream);
+}
+
+int cvr_pgmres(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res)
+{
+    if (const int rc = check_pgmres(h, p, b_host, x_host, restart, opt, res)) return rc;
+    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return gmres_device(h, p, b, x, restart, opt, res, st); });
 }
 
 }  // extern "C"

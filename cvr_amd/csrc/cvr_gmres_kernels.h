@@ -1,6 +1,5 @@
-// cvr_gmres_kernels.h -- the state cell, the vector kernels and the column-group macro of GMRES(m), shared by cvr_gmres.hip (cvr_gmres_device) and
-// cvr_pgmres.hip (cvr_pgmres_device): both solvers run the same code, so what they have in common has the same bits.  What each kernel does:
-// cvr_gmres.hip's head.
+// cvr_gmres_kernels.h -- the state cell, the vector kernels and the column-group macro of GMRES(m) (cvr_gmres.hip: cvr_gmres_device,
+// cvr_pgmres_device).  What each kernel does: cvr_gmres.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 

@@ -1,9 +1,11 @@
-// cvr_krylov.h -- what the Krylov solvers share (cvr_cg.hip, cvr_cg_multi.hip, cvr_bicgstab.hip, cvr_gmres.hip).  The device half: the fixed grid, the
+// cvr_krylov.h -- what the Krylov solvers share (cvr_cg.hip, cvr_cg_multi.hip, cvr_bicgstab.hip, cvr_gmres.hip, cvr_lsqr.hip, cvr_minres.hip) and the
+// preconditioner objects that run on their grid (cvr_precond.hip, cvr_chebyshev.hip, cvr_pcg_multi.hip).  The device half: the fixed grid, the
 // 16-byte packet helpers and the fixed-tree fp64 sums.  Every translation unit that includes it gets the same code, so a sum has the same bits
 // whichever solver forms it.  The host half, below it: the argument checks and the driver every solver runs --
 //   check the handle | carve one allocation (Arena) | begin the clock | zero the pad slots of the SpMV inputs | r = b - A x0 (start_residual) |
 //   the solver's start kernels | batches of steps with one read-back of the state cell each (run_batches) | clear x where b == 0 | fill_result
 // A solver supplies its cell, its kernels, the function that enqueues step k and the one that reads the cell back and says whether it has stopped.
+// Each method has one solve function; a preconditioner (none, the diagonal opt->minv_dev, a cvr_precond object: cvr_precond.h) is an argument of it.
 #pragma once
 #include "cvr_internal.h"
 
@@ -231,6 +233,17 @@ inline void fill_result(cvr_cg_result *res, int32_t iters, int32_t status, int s
     res->residual_norm = rnorm;
     res->b_norm = bnorm;
     res->seconds = seconds;
+}
+
+// The tail of a single-vector solve, behind run_batches: x = 0 where b == 0, the clock, the result from the cell (or its head) the host read back last
+template <typename Cell>
+int finish_solve(Arena &a, hipStream_t st, void *x, size_t vb, const Cell &cell, int spmvs, cvr_cg_result *res)
+{
+    if (cell.zero_x && vb) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
+    double seconds = 0;
+    if (const int rc = a.seconds(st, &seconds)) return rc;
+    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
+    return CVR_OK;
 }
 
 // A host entry point around its device form fn(b_dev, x_dev, stream): the handle's own vectors carry b and x (d_x has ncols + 1 values, d_y at least nrows)

@@ -110,10 +110,7 @@ int lsqr_solve(cvr_handle *a, cvr_handle *at, const T *b, T *x, double damp, con
             return CVR_OK;
         });
     if (rc) return rc;
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, sizeof(T) * (size_t)n, st));
-    double seconds = 0;
-    if (const int rc = ar.seconds(st, &seconds)) return rc;
-    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
+    if (const int rc = finish_solve(ar, st, x, sizeof(T) * (size_t)n, cell, spmvs, res)) return rc;
     if (info) {
         memset(info, 0, sizeof(*info));
         info->arnorm = cell.arnorm;

@@ -97,10 +97,7 @@ int minres_solve(cvr_handle *h, const T *b, T *x, double shift, const cvr_cg_opt
             return CVR_OK;
         });
     if (rc) return rc;
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    double seconds = 0;
-    if (const int rc = a.seconds(st, &seconds)) return rc;
-    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
+    if (const int rc = finish_solve(a, st, x, vb, cell, spmvs, res)) return rc;
     if (info) {
         memset(info, 0, sizeof(*info));
         info->anorm = cell.anorm;

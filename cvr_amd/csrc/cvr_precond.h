@@ -1,7 +1,8 @@
-// cvr_precond.h -- the preconditioner object as the solvers see it, shared by cvr_precond.hip (the block-Jacobi object, cvr_pcg_device),
-// cvr_chebyshev.hip (the Chebyshev kind), cvr_pcg_multi.hip, cvr_pbicgstab.hip and cvr_pgmres.hip: the struct with its kind, the block-Jacobi apply of one
-// packet (every solver forms z = W r by this code, so the same r gives the same bits in all of them) and the checks every preconditioned entry point
-// makes.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.
+// cvr_precond.h -- the preconditioner object as the solvers see it, shared by the files that hold the objects (cvr_precond.hip: block-Jacobi,
+// cvr_chebyshev.hip: the Chebyshev kind, cvr_pcg_multi.hip: the k-wide block-Jacobi apply) and the solvers that take one (cvr_cg.hip, cvr_cg_multi.hip,
+// cvr_bicgstab.hip, cvr_gmres.hip): the struct with its kind, the block-Jacobi apply of one packet (every solver forms z = W r by this code, so the same
+// r gives the same bits in all of them), the checks every preconditioned entry point makes, and the host calls by which the CG solvers enqueue an
+// object's apply.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
@@ -85,9 +86,28 @@ inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 
 }  // namespace
 
-// cvr_chebyshev.hip: the Chebyshev kind behind cvr_precond_apply_device, cvr_pcg_device / cvr_pcg (the checks are the callers') and cvr_precond_destroy
+// cvr_chebyshev.hip: the Chebyshev kind behind cvr_precond_apply_device (the checks are the caller's) and cvr_precond_destroy
 int  chebyshev_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st);
-int  chebyshev_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st);
 void chebyshev_release(cvr_precond *p);
+
+// "z = M r inside a CG solve", enqueued on `st`: z and the partial sums of r . z into part_rz (set 1 of cg_direction_kernel<T, true>); start: before
+// the state cell exists, p = z as well; otherwise nothing is written once the cell (a CgCell) holds a stop.  r, z and p are the solver's buffers.
+// *spmvs grows by the products enqueued.  One definition per kind (cvr_precond.hip: pcg_apply_kernel, cvr_chebyshev.hip: the polynomial's steps), for
+// float and double; the solver's T is the object's type (check_precond_pair).
+// (Hidden: calls between the library's own files.  chebyshev_apply and chebyshev_release above stay visible as they were, so that the list of names
+// the library exports only loses the function that went away.)
+template <typename T> __attribute__((visibility("hidden"))) int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st);
+template <typename T> __attribute__((visibility("hidden"))) int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
+template <typename T>
+static int precond_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
+{
+    if (pc->kind == kPrecondChebyshev) return chebyshev_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
+    return block_jacobi_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
+}
+
+// cvr_pcg_multi.hip: the same for the blocks of batched CG (block-Jacobi only), Z = W R and per column the partial sums of r . z into that column's
+// set 1 of `part`; lv: the library's blocks take 16-byte packets.  cells: the columns' CgCells
+template <typename T>
+__attribute__((visibility("hidden"))) hipError_t block_jacobi_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st);
 }  // namespace krylov
 }  // namespace cvrh

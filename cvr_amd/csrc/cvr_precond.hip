@@ -1,13 +1,13 @@
-// cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*) and the conjugate gradients that use it (cvr_pcg_device,
-// cvr_pcg); the entry points both kinds of object share hand the Chebyshev kind on to cvr_chebyshev.hip (apply, pcg_device, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into LDS, inverts them there in fp64 and stores the
-// inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for the elements CVR_KRYLOV_PACKETS gives it
-// (cvr_precond.h: the struct and the apply of one packet, shared with cvr_pbicgstab.hip and cvr_pgmres.hip).
+// cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*); the entry points both kinds of object share hand the
+// Chebyshev kind on to cvr_chebyshev.hip (apply, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into
+// LDS, inverts them there in fp64 and stores the inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for
+// the elements CVR_KRYLOV_PACKETS gives it (cvr_precond.h: the struct and the apply of one packet, shared with cvr_bicgstab.hip and cvr_gmres.hip).
 //   precond_build_kernel   one wavefront per workgroup; L = 8, 16 or 32 lanes per block (the power of two from bs up), 64 / L blocks per wavefront
 //   precond_apply_kernel   z = W r
 //   pcg_apply_kernel       the same inside the solver, with the partial sums of r . z (set 1 of cg_direction_kernel<T, true>) and, at the start, p = z
 // W lies block after block, each block TRANSPOSED (element (i, j) at j * bs + i): for a fixed j the threads that own neighbouring rows load neighbouring
-// values.  The solver is cvr_cg.hip's with four launches per step: cg_pq_kernel, cg_update_kernel<T, false, AL>, pcg_apply_kernel, cg_direction_kernel<T, true>
-// (cvr_cg_kernels.h: the kernels cvr_cg_device runs, unchanged).
+// values.  The solver is cvr_cg.hip's cg_solve, which enqueues pcg_apply_kernel through block_jacobi_cg_apply (cvr_precond.h); this file launches no
+// cg_* kernel and holds no solve loop (cvr_cg_kernels.h is included for the state cell the apply reads).
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
@@ -291,90 +291,23 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
     return CVR_OK;
 }
 
-// ---- preconditioned conjugate gradients: cvr_cg.hip's cg_solve with W in place of minv
-
-template <typename T>
-hipError_t launch_pcg_step(const Workspace<T> &w, const cvr_precond *pc, T *x, long long n, bool al, int k, double rtol, hipStream_t st)
-{
-    launch(cg_pq_kernel<T>, st, w.p, w.q, n, w.part_pq, w.cell);
-    with_flags([&](auto AL) { launch(cg_update_kernel<T, false, AL>, st, x, w.r, w.z, w.p, w.q, (const T *)nullptr, n, w.part_pq, w.part, w.cell, k); }, al);
-    launch(pcg_apply_kernel<T, false>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, w.r, w.z, w.p, n, w.part + kBlocks, w.cell);
-    launch(cg_direction_kernel<T, true>, st, w.p, w.z, n, w.part, w.cell, k, rtol);
-    return hipGetLastError();
-}
-
-template <typename T>
-int pcg_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
-{
-    const long long n = h->info.nrows;
-    const size_t    vb = sizeof(T) * (size_t)n;
-    const bool      al = (((uintptr_t)b | (uintptr_t)x) & 15u) == 0;
-
-    Arena        a;
-    const size_t op = a.add(x_ext_bytes(h)), oq = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h)), oz = a.add(vec_bytes(h));
-    const size_t opq = a.add(sizeof(double) * kBlocks), opart = a.add(sizeof(double) * 3 * kBlocks), ocell = a.add(sizeof(CgCell));
-    HIP_TRY(a.alloc());
-    const Workspace<T> w{a.at<T>(op), a.at<T>(oq), a.at<T>(orr), a.at<T>(oz), a.at<double>(opq), a.at<double>(opart), a.at<CgCell>(ocell)};
-    if (const int rc = a.begin(st)) return rc;
-
-    // p = x0 for the moment (with its pad slot), r = b; r = b - A x0; then p = r and the sums r . r and b . b, z = W r, p = z and r . z, the cell
-    if (const int rc = zero_pad_slot(w.p, vb, sizeof(T), st)) return rc;
-    if (const int rc = start_residual(h, w.p, w.r, x, b, n, st)) return rc;
-    int spmvs = 1;
-    with_flags([&](auto AL) { launch(cg_init_kernel<T, false, AL>, st, b, (const T *)nullptr, (const T *)w.r, w.z, w.p, n, w.part); }, al);
-    HIP_TRY(hipGetLastError());
-    launch(pcg_apply_kernel<T, true>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, w.r, w.z, w.p, n, w.part + kBlocks, (const CgCell *)w.cell);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, 1, opt->rtol, w.cell);
-    HIP_TRY(hipGetLastError());
-
-    CgCell cell{};
-    const int rc = run_batches(
-        opt,
-        [&](int k) -> int {
-            HIP_TRY(run_spmv(h, w.p, w.q, st));
-            spmvs++;
-            HIP_TRY(launch_pcg_step(w, pc, x, n, al, k, opt->rtol, st));
-            return CVR_OK;
-        },
-        [&](int, bool *stopped) -> int {
-            if (const int rc = read_cell(&cell, w.cell, sizeof(cell), st)) return rc;
-            *stopped = cell.stop != 0;
-            return CVR_OK;
-        });
-    if (rc) return rc;
-    if (cell.zero_x && n) HIP_TRY(hipMemsetAsync(x, 0, vb, st));
-    double seconds = 0;
-    if (const int rc = a.seconds(st, &seconds)) return rc;
-    fill_result(res, cell.iters, cell.status, spmvs, cell.rnorm, cell.bnorm, seconds);
-    return CVR_OK;
-}
-
-// what the entry points check before any device work and before the handle is looked at
-int check_pcg_args(const void *h, const cvr_precond *p, const void *b, const void *x, const cvr_cg_options *opt, const cvr_cg_result *res)
-{
-    if (const int rc = check_solver_args(h, b, x, opt, res)) return rc;
-    if (const int rc = check_precond_args(p, opt, "cvr_pcg")) return rc;
-    return CVR_OK;
-}
-
-// ... and what they ask of the handle and of the pair
-int check_pcg_handle(const cvr_handle *h, const cvr_precond *p)
-{
-    if (const int rc = check_square_preprocessed(h, "cvr_pcg", "conjugate gradients need")) return rc;
-    if (const int rc = check_precond_pair(h, p, "cvr_pcg")) return rc;
-    return CVR_OK;
-}
-
-int pcg_device(cvr_handle *h, const cvr_precond *p, const void *b, void *x, const cvr_cg_options *opt, cvr_cg_result *res, hipStream_t st)
-{
-    Range range("cvr_pcg_device");
-    HIP_TRY(hipSetDevice(h->device));
-    if (p->kind == kPrecondChebyshev) return chebyshev_pcg_device(h, p, b, x, opt, res, st);
-    return with_value_type(h, [&](auto t) { return pcg_solve(h, p, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), opt, res, st); });
-}
-
 }  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+template <typename T>
+int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st)
+{
+    with_flags([&](auto START) { launch(pcg_apply_kernel<T, START>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, r, z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+template int block_jacobi_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t);
+template int block_jacobi_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t);
+
+}  // namespace krylov
+}  // namespace cvrh
 
 extern "C" {
 
@@ -468,20 +401,6 @@ int cvr_precond_destroy(cvr_precond *p)
     }
     delete p;
     return CVR_OK;
-}
-
-int cvr_pcg_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, void *x_dev, const cvr_cg_options *opt, cvr_cg_result *res, void *stream)
-{
-    if (const int rc = check_pcg_args(h, p, b_dev, x_dev, opt, res)) return rc;
-    if (const int rc = check_pcg_handle(h, p)) return rc;
-    return pcg_device(h, p, b_dev, x_dev, opt, res, (hipStream_t)stream);
-}
-
-int cvr_pcg(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, const cvr_cg_options *opt, cvr_cg_result *res)
-{
-    if (const int rc = check_pcg_args(h, p, b_host, x_host, opt, res)) return rc;
-    if (const int rc = check_pcg_handle(h, p)) return rc;
-    return solve_from_host(h, b_host, x_host, [&](const void *b, void *x, hipStream_t st) { return pcg_device(h, p, b, x, opt, res, st); });
 }
 
 }  // extern "C"

@@ -119,7 +119,7 @@ def test_solver_kernels_without_scratch_or_spills(bicg_md):
     seen = {}
     for name, item in bicg_md.items():
         d = dem[name]
-        m = re.search(r"(bicg_\w+_kernel)(?:<(float|double)[^>]*>)?", d)
+        m = re.search(r"(?<!\w)(p?bicg_\w+_kernel)(?:<(float|double)[^>]*>)?", d)          # (anchored: pbicg_apply_kernel is no bicg_* kernel)
         assert m, d
         seen.setdefault(m.group(1), []).append(d)
         assert item.get("private_segment_fixed_size") == 0, (d, item)
@@ -128,10 +128,11 @@ def test_solver_kernels_without_scratch_or_spills(bicg_md):
         assert item.get("vgpr_count", 999) <= 128, (d, item)          # streaming passes live on occupancy
     # T x preconditioner x alignment of the caller's arrays where a pass touches them: b, x and minv at the start, x (and s^ apart from s) in the
     # update, x alone in the half step; minv alone in the s and direction passes (no alignment variant without a preconditioner); T for r^ . v
+    # The block-Jacobi object's apply, which lives in this file too (test_pkrylov_host.py), by T.
     assert {k: len(v) for k, v in seen.items()} == dict(bicg_init_kernel=8, bicg_check_kernel=1, bicg_rv_kernel=2, bicg_s_kernel=6, bicg_half_kernel=4,
-                                                        bicg_update_kernel=8, bicg_direction_kernel=6), seen
+                                                        bicg_update_kernel=8, bicg_direction_kernel=6, pbicg_apply_kernel=2), seen
     for k, v in seen.items():
         if k != "bicg_check_kernel":
             assert any("<float" in d for d in v) and any("<double" in d for d in v), k
-    # at most five vector launches per step
-    assert len(set(seen) - {"bicg_init_kernel", "bicg_check_kernel"}) <= 5
+    # at most five vector launches per step without a preconditioner and with the diagonal: the bicg_* kernels
+    assert len({k for k in seen if k.startswith("bicg_")} - {"bicg_init_kernel", "bicg_check_kernel"}) <= 5

@@ -88,14 +88,17 @@ def test_solver_kernels_without_scratch_or_spills(gmres_md):
     seen = {}
     for name, item in gmres_md.items():
         d = dem[name]
-        m = re.search(r"(gmres_\w+_kernel)<(float|double)", d)
+        m = re.search(r"(?<!\w)(p?gmres_\w+_kernel)<(float|double)", d)          # (anchored: the pgmres_* kernels are no gmres_* kernels)
         assert m, d
         seen.setdefault(m.group(1), set()).add(m.group(2))
         assert item.get("private_segment_fixed_size") == 0, (d, item)
         assert item.get("vgpr_spill_count", 0) == 0, (d, item)
         assert item.get("sgpr_spill_count", 0) == 0, (d, item)
         assert item.get("vgpr_count", 999) <= 128, (d, item)          # streaming passes live on occupancy
-    assert set(seen) == {"gmres_dots_kernel", "gmres_update_kernel", "gmres_finish_kernel", "gmres_rr_kernel", "gmres_begin_kernel", "gmres_x_kernel"}, seen
+    assert {k for k in seen if k.startswith("gmres_")} == {"gmres_dots_kernel", "gmres_update_kernel", "gmres_finish_kernel", "gmres_rr_kernel",
+                                                        "gmres_begin_kernel", "gmres_x_kernel"}, seen
+    # ... and the block-Jacobi object's kernels, which live in this file too (test_pkrylov_host.py)
+    assert {k for k in seen if not k.startswith("gmres_")} == {"pgmres_apply_kernel", "pgmres_u_kernel", "pgmres_x_kernel"}, seen
     assert all(v == {"float", "double"} for v in seen.values()), seen
 
 

@@ -1,6 +1,6 @@
 """cvr_pbicgstab_device / cvr_pbicgstab and cvr_pgmres_device / cvr_pgmres -- what can be checked without a GPU: the ABI (exports, the Python methods,
 the argument checks that come before any device work, in their order), the code of the new kernels for gfx950 (every fp32 / fp64 instantiation is
-there and runs without scratch or spills; the kernels the two files share with cvr_bicgstab.hip and cvr_gmres.hip are pinned by their own host tests),
+there and runs without scratch or spills; they live in cvr_bicgstab.hip and cvr_gmres.hip, whose own kernels are pinned by their own host tests),
 and the generator of the nonsymmetric block-diagonal test family."""
 import ctypes as C
 import os
@@ -120,26 +120,47 @@ def _types(ds):
     return {t for d in ds for t in re.findall(r"_kernel<(float|double)", d)}
 
 
+def _forms(ds, *flags):
+    """the instantiations among ds whose template arguments behind T begin with `flags`"""
+    want = ", ".join(("true" if f else "false") for f in flags)
+    return [d for d in ds if re.search(r"_kernel<(?:float|double), %s[,>]" % want, d)]
+
+
 def test_pbicgstab_kernels_without_scratch_or_spills():
-    seen = _counts("cvr_pbicgstab.hip", r"((?:pbicg|bicg)_\w+_kernel)(?:<(float|double)[^>]*>)?")
-    # T for the apply; beside it the forms of cvr_bicg_kernels.h's kernels the solver launches: no diagonal (PRE = false) in the start, s and the
-    # direction, s^ from its own buffer (PRE = true) in the update, T x alignment of the caller's b and x where a kernel touches them
-    assert {k: len(v) for k, v in seen.items()} == dict(pbicg_apply_kernel=2, bicg_init_kernel=4, bicg_check_kernel=1, bicg_rv_kernel=2, bicg_s_kernel=2,
-                                                         bicg_half_kernel=4, bicg_update_kernel=4, bicg_direction_kernel=2), seen
-    assert all("true" in d.split("bicg_update_kernel<")[1].split(",")[1] for d in seen["bicg_update_kernel"]), seen["bicg_update_kernel"]
+    # (the alternation tries pbicg first, so pbicg_apply_kernel is not taken for a bicg_* kernel)
+    seen = _counts("cvr_bicgstab.hip", r"((?:pbicg|bicg)_\w+_kernel)(?:<(float|double)[^>]*>)?")
+    # T for the apply; beside it, among the bicg_* kernels of the merged file (test_bicgstab_host.py pins all of them), the forms the solver launches
+    # with an object: no diagonal (PRE = false) in the start, s and the direction, s^ from its own buffer (PRE = true) in the update, T x alignment of
+    # the caller's b and x where a kernel touches them
+    assert len(seen["pbicg_apply_kernel"]) == 2, seen
+    assert len(_forms(seen["bicg_init_kernel"], False)) == 4 and len(seen["bicg_check_kernel"]) == 1 and len(seen["bicg_rv_kernel"]) == 2, seen
+    assert len(_forms(seen["bicg_s_kernel"], False, True)) == 2 and len(seen["bicg_half_kernel"]) == 4, seen
+    assert len(_forms(seen["bicg_update_kernel"], True)) == 4 and len(_forms(seen["bicg_direction_kernel"], False, True)) == 2, seen
+    assert set(seen) == {"pbicg_apply_kernel", "bicg_init_kernel", "bicg_check_kernel", "bicg_rv_kernel", "bicg_s_kernel", "bicg_half_kernel",
+                         "bicg_update_kernel", "bicg_direction_kernel"}, seen
     for k, v in seen.items():
         if k != "bicg_check_kernel":
             assert _types(v) == {"float", "double"}, (k, v)
+    for k, v in (("bicg_init_kernel", _forms(seen["bicg_init_kernel"], False)), ("bicg_s_kernel", _forms(seen["bicg_s_kernel"], False, True)),
+                 ("bicg_update_kernel", _forms(seen["bicg_update_kernel"], True)), ("bicg_direction_kernel", _forms(seen["bicg_direction_kernel"], False, True))):
+        assert _types(v) == {"float", "double"}, (k, v)
 
 
 def test_pgmres_kernels_without_scratch_or_spills():
-    seen = _counts("cvr_pgmres.hip", r"((?:pgmres|gmres)_\w+_kernel)<(float|double)")
-    # T for the apply and the u kernel, T x alignment of the caller's x for the x kernel; beside them cvr_gmres_kernels.h's kernels without a diagonal
-    assert {k: len(v) for k, v in seen.items()} == dict(pgmres_apply_kernel=2, pgmres_u_kernel=2, pgmres_x_kernel=4, gmres_dots_kernel=2, gmres_update_kernel=4,
-                                                         gmres_finish_kernel=2, gmres_rr_kernel=6, gmres_begin_kernel=2), seen
-    assert "gmres_x_kernel" not in seen
+    seen = _counts("cvr_gmres.hip", r"((?:pgmres|gmres)_\w+_kernel)<(float|double)")
+    # T for the apply and the u kernel, T x alignment of the caller's x for the x kernel; beside them, among the gmres_* kernels of the merged file
+    # (test_gmres_host.py pins them), the forms without a diagonal that the solver launches with an object
+    assert {k: len(seen[k]) for k in ("pgmres_apply_kernel", "pgmres_u_kernel", "pgmres_x_kernel")} == dict(pgmres_apply_kernel=2, pgmres_u_kernel=2, pgmres_x_kernel=4), seen
+    assert len(seen["gmres_dots_kernel"]) == 2 and len(seen["gmres_update_kernel"]) == 4 and len(seen["gmres_rr_kernel"]) == 6, seen
+    assert len(_forms(seen["gmres_finish_kernel"], False, True)) == 2 and len(_forms(seen["gmres_begin_kernel"], False, True)) == 2, seen
+    # (gmres_x_kernel is in the merged file for the plain and diagonal forms, so its absence from the object's path no longer shows in the
+    # instantiations: tests/test_gpu_pgmres.py holds cvr_pgmres_device to its model step by step, where x is W u and not u)
+    assert set(seen) == {"pgmres_apply_kernel", "pgmres_u_kernel", "pgmres_x_kernel", "gmres_dots_kernel", "gmres_update_kernel", "gmres_finish_kernel",
+                         "gmres_rr_kernel", "gmres_begin_kernel", "gmres_x_kernel"}, seen
     for k, v in seen.items():
         assert _types(v) == {"float", "double"}, (k, v)
+    for v in (_forms(seen["gmres_finish_kernel"], False, True), _forms(seen["gmres_begin_kernel"], False, True)):
+        assert _types(v) == {"float", "double"}, v
 
 
 def test_block_diag_nonsym_is_what_it_says():
