@@ -15,6 +15,63 @@ def csr_from_lengths(lens, ncols, rng, dtype=np.float64, sort=True):
     return len(lens), ncols, rp, ci, va
 
 
+def random_case(rng, max_nnz=400_000):
+    """one matrix of the fuzz tests: 1 .. 3999 rows, 1 .. 5999 columns, row lengths uniform, power-law, a few giants, constant or mostly empty, at most
+    about max_nnz entries, rows sorted or not: (nrows, ncols, row_ptr, col_idx, vals, sorted).  With the default max_nnz it consumes the generator
+    exactly as the loops of test_gpu_fuzz.py always did (tests/test_fuzz_checks_host.py pins a digest of its cases)."""
+    kind = rng.integers(0, 5)
+    nrows = int(rng.integers(1, 4000))
+    ncols = int(rng.integers(1, 6000))
+    if kind == 0:
+        lens = rng.integers(0, 12, size=nrows)
+    elif kind == 1:
+        lens = np.minimum((rng.pareto(1.1, size=nrows) + 0.5).astype(np.int64), 3000)
+    elif kind == 2:
+        lens = np.zeros(nrows, dtype=np.int64)
+        lens[rng.integers(0, nrows, size=max(1, nrows // 50))] = rng.integers(1, 5000, size=max(1, nrows // 50))
+    elif kind == 3:
+        lens = np.full(nrows, int(rng.integers(1, 70)))
+    else:
+        lens = rng.integers(0, 3, size=nrows) * rng.integers(0, 40, size=nrows)
+    lens = np.asarray(lens, dtype=np.int64)
+    if lens.sum() > max_nnz:
+        lens = lens // (lens.sum() // max_nnz + 1)
+    srt = bool(rng.integers(0, 2))
+    return csr_from_lengths(lens, ncols, rng, sort=srt) + (srt,)
+
+
+def random_options(rng, ncols, sorted_rows):
+    """CvrMatrix keyword options drawn as the two loops of test_gpu_fuzz.py draw them, for a matrix of `ncols` columns whose rows are sorted or not:
+    one time in eight the defaults ({}), four in eight the draw of test_fuzz_parity (chunk length, split threshold, panels, window, wavefronts per
+    workgroup, column phases, hub table, re-ordered x, tags, piece limit, swizzle), three in eight the draw of test_fuzz_interleaved_chunks
+    (interleaved and gang chunks).  The guards are those loops': column phases only on one panel, from 320 columns on and with sorted rows (the
+    library refuses them on a row whose columns descend), a hub table only without phases, re-ordered x only with a hub table on one panel, tags
+    and piece limit only with phases."""
+    family = int(rng.integers(0, 8))
+    if family == 0:
+        return {}
+    if family <= 4:
+        S = int(rng.choice([4, 8, 12, 16, 32, 64, 96, 128]))
+        thr = int(rng.choice([0, 1, 7, 64, 10**6]))
+        P = int(rng.choice([1, 1, 2, 3]))
+        win = int(rng.choice([0, 0, 64, 1000]))
+        wpb = int(rng.choice([1, 1, 2, 8, 16]))
+        ph = int(rng.choice([1, 1, 2, 5])) if P == 1 and ncols >= 320 and sorted_rows else 1
+        hub = int(rng.choice([0, 0, 7, 300])) if ph == 1 else 0
+        reo = int(rng.integers(0, 2)) if hub and P == 1 else 0
+        tags = int(rng.choice([-1, 0, 1])) if ph > 1 else -1
+        pmax = int(rng.choice([-1, 0, 2, 8])) if ph > 1 else -1
+        swz = int(rng.choice([-1, -1, 0, 3, 4, 5, 6]))
+        return dict(steps_per_chunk=S, split_threshold=thr, col_panels=P, x_window=win, waves_per_block=wpb, col_phases=ph, hub_table=hub, hub_reorder=reo,
+                    row_tags16=tags, piece_max=pmax, xcd_swizzle=swz)
+    S = int(rng.choice([4, 8, 16, 32, 64, 128, 256, 508]))
+    P = int(rng.choice([1, 1, 1, 2, 3, 8]))
+    wpb = int(rng.choice([0, 1, 2, 4, 8]))
+    tags = int(rng.choice([-1, -1, 0, 1]))          # (0 is refused only where column and row do not fit one word: never below 2^13 columns)
+    gang = int(rng.integers(0, 2))
+    return dict(steps_per_chunk=S, col_panels=P, waves_per_block=wpb, row_tags16=tags, interleave=1, gang=gang)
+
+
 def cases(dtype=np.float64):
     rng = np.random.default_rng(20261002)
     out = {}

@@ -201,6 +201,27 @@ def rect_sparse(m, n, dtype, seed=0, per_row=3):
     return m, n, np.array(rp, dtype=np.int64), np.array(ci, dtype=np.int32), np.array(va, dtype=dtype)
 
 
+def rect_long(dtype, m=701, n=449, long_rows=(348, 349, 350, 351), long_cols=(221, 222, 223), seed=0):
+    """(m, n, row_ptr, col_idx, vals): rect_sparse(m, n) plus four neighbouring rows of 300 and three neighbouring columns of 400 further entries of size
+    <= 0.02 (sorted columns, no duplicates).  Each is longer than a quarter of a chunk of 16 steps (256 of 1024 slots) and the neighbours together
+    are longer than a chunk, so the plain layout of A and of A^T cuts at least one of them over chunks; the added part has a Frobenius norm of
+    about 1 beside singular values of A in about [1, 2.5]: still well conditioned (tests/test_lsqr_model_host.py)"""
+    _, _, rp, ci, va = rect_sparse(m, n, np.float64)
+    rng = np.random.default_rng(20261020 + seed)
+    rows = [dict(zip(ci[rp[i]:rp[i + 1]].tolist(), va[rp[i]:rp[i + 1]].tolist())) for i in range(m)]
+    for r in long_rows:
+        for c in rng.choice(n, size=300, replace=False):
+            rows[r].setdefault(int(c), float(rng.random() * 0.04 - 0.02))
+    for c in long_cols:
+        for r in rng.choice(m, size=400, replace=False):
+            rows[int(r)].setdefault(int(c), float(rng.random() * 0.04 - 0.02))
+    rp2 = np.zeros(m + 1, dtype=np.int64)
+    rp2[1:] = np.cumsum([len(r) for r in rows])
+    ci2 = np.array([c for r in rows for c in sorted(r)], dtype=np.int32)
+    va2 = np.array([r[c] for r in rows for c in sorted(r)], dtype=dtype)
+    return m, n, rp2, ci2, va2
+
+
 def two_per_row(m, n, dtype):
     """(m, n, row_ptr, col_idx, vals) for m >= n: row i holds its diagonal-like entry at column i % n (value 1 + (i % 7) / 8) and its neighbour
     (i + 1) % n (value -0.25); with n == 1 the diagonal-like entry alone"""

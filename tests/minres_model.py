@@ -185,6 +185,17 @@ def kkt(n1, n2, dtype):
     return n, n, rpn, np.array(cin, dtype=np.int32), np.array(van, dtype=dtype)
 
 
+def banded_indefinite(n, dtype):
+    """(n, n, row_ptr, col_idx, vals): krylov_model.banded("spd", n) with 2 taken from the diagonal of every odd row.  That matrix is I + E with
+    ||E||_2 <= 0.5 (its spectrum lies in [0.5, 1.5]), this one J + E with J = diag(1, -1, 1, ...): symmetric, its spectrum inside
+    [-1.5, -0.5] and [0.5, 1.5] (Weyl), about half of it on either side"""
+    n, _, rp, ci, va = KM.banded("spd", n, np.float64)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    va = va.copy()
+    va[(rows == ci) & (rows % 2 == 1)] -= 2.0
+    return n, n, rp, ci, va.astype(dtype)
+
+
 def dense_of(n, rp, ci, va):
     A = np.zeros((n, n))
     A[np.repeat(np.arange(n), np.diff(rp)), ci] = va

@@ -18,26 +18,7 @@ except Exception:      # noqa: BLE001 -- the device-array cases are skipped with
     torch = None
 
 
-def _random_case(rng):
-    kind = rng.integers(0, 5)
-    nrows = int(rng.integers(1, 4000))
-    ncols = int(rng.integers(1, 6000))
-    if kind == 0:
-        lens = rng.integers(0, 12, size=nrows)
-    elif kind == 1:
-        lens = np.minimum((rng.pareto(1.1, size=nrows) + 0.5).astype(np.int64), 3000)
-    elif kind == 2:
-        lens = np.zeros(nrows, dtype=np.int64)
-        lens[rng.integers(0, nrows, size=max(1, nrows // 50))] = rng.integers(1, 5000, size=max(1, nrows // 50))
-    elif kind == 3:
-        lens = np.full(nrows, int(rng.integers(1, 70)))
-    else:
-        lens = rng.integers(0, 3, size=nrows) * rng.integers(0, 40, size=nrows)
-    lens = np.asarray(lens, dtype=np.int64)
-    if lens.sum() > 400_000:
-        lens = lens // (lens.sum() // 400_000 + 1)
-    srt = bool(rng.integers(0, 2))
-    return K.csr_from_lengths(lens, ncols, rng, sort=srt) + (srt,)
+_random_case = K.random_case          # (tests/cases.py: shared with test_gpu_fuzz_derived.py)
 
 
 def _check_non_finite_x(A, nrows, ncols, rp, ci, va, x, seed, case, ctx):

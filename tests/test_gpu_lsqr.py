@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import cases as K
 import cvr_amd
 import krylov_model as KM
 import lsqr_model as LM
@@ -57,15 +58,16 @@ class Side:
 class Pair:
     """the handles of A and A^T and the solver calls in the model's terms"""
 
-    def __init__(self, m, n, rp, ci, va, symmetric=False, explicit=False):
+    def __init__(self, m, n, rp, ci, va, symmetric=False, explicit=False, opts_a=None, opts_at=None):
+        """opts_a / opts_at: cvr_options by name for the handle of A / of A^T (None: the defaults)"""
         self.m, self.n, self.dtype = m, n, va.dtype.type
-        self.A = cvr_amd.CvrMatrix(m, n, rp, ci, va)
+        self.A = cvr_amd.CvrMatrix(m, n, rp, ci, va, **(opts_a or {}))
         if symmetric:
             self.AT = self.A
         elif explicit:
-            self.AT = cvr_amd.CvrMatrix(*LM.transpose_csr(m, n, rp, ci, va))
+            self.AT = cvr_amd.CvrMatrix(*LM.transpose_csr(m, n, rp, ci, va), **(opts_at or {}))
         else:
-            self.AT = cvr_amd.CvrMatrix(m, n, rp, ci, va, transpose=1)
+            self.AT = cvr_amd.CvrMatrix(m, n, rp, ci, va, transpose=1, **(opts_at or {}))
         assert (self.AT.nrows, self.AT.ncols) == (n, m)
         self.a, self.at = Side(self.A), (Side(self.AT) if self.AT is not self.A else None)
         if self.at is None:
@@ -178,6 +180,34 @@ def test_square_symmetric_with_one_handle(prec):
         b, x0, _ = KM.inputs(n, dtype)
         for damp, start in ((0.0, x0), (0.25, None)):
             _trajectory(pair, b, start, damp, ("symmetric", prec, damp), shifts=_shifts(dtype)[:1])
+    finally:
+        pair.close()
+
+
+MIXED_PAIRS = {"plain+panels": ("plain", "panels"), "gang+phases": ("gang", "phases"), "hub_reorder+default": ("hub_reorder", "default"),
+               "interleaved_panels+window": ("interleaved_panels", "window")}
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("layout", sorted(K.ALL_LAYOUTS) + sorted(MIXED_PAIRS))
+def test_layouts_against_the_model(layout, prec):
+    """every layout on both handles, and four mixed pairs: u^ is A's y_ext and A^T's x_ext at once, and info.yext_elems / info.x_elems of the two
+    handles differ with the layout (scratch rows of cut rows, panels, the pad element).  lsqr_model.rect_long: 701 x 449, well conditioned, rows
+    and columns cut over chunks (tests/test_lsqr_model_host.py).  A layout that cannot be built for this matrix is a failure."""
+    dtype = _dtype(prec)
+    la, lat = MIXED_PAIRS.get(layout, (layout, layout))
+    m, n, rp, ci, va = LM.rect_long(dtype)
+    pair = Pair(m, n, rp, ci, va, opts_a=K.ALL_LAYOUTS[la], opts_at=K.ALL_LAYOUTS[lat])
+    try:
+        ia, iat = pair.A.info, pair.AT.info
+        if layout == "plain":
+            assert ia.nshared > 0 and iat.nshared > 0, (ia.nshared, iat.nshared)
+        for name, i in ((la, ia), (lat, iat)):          # the layout really formed
+            want = dict(phases=i.col_phases > 1, window=i.x_window > 0, panels=i.col_panels == 3, interleaved_panels=i.col_panels == 8 and i.interleave == 1, gang=i.gang > 0,
+                        interleaved=i.interleave == 1).get(name, True)
+            assert want, (name, i.col_phases, i.x_window, i.col_panels, i.interleave, i.gang)
+        b, x0 = LM.inputs(m, n, rp, ci, va, dtype, False)
+        _trajectory(pair, b, x0, 0.5, (layout, prec), kmax=2, shifts=((1, 1),))
     finally:
         pair.close()
 

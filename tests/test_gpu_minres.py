@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import cases as K
 import cvr_amd
 import krylov_model as KM
 import minres_model as MM
@@ -143,6 +144,28 @@ def test_kkt_against_the_model(shape, prec):
         b, x0, minv = KM.inputs(n, dtype)
         for pre, start, shift in ((None, None, 0.0), (minv, x0, 0.0), (None, x0, 0.25), (minv, None, 0.25)):
             _trajectory(S, b, start, pre, shift, ("kkt", shape, prec, pre is not None, start is not None, shift))
+    finally:
+        S.close()
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("layout", sorted(K.ALL_LAYOUTS))
+def test_every_layout_against_the_model(layout, prec):
+    """the vector kernels are the same across layouts; info.x_elems, info.yext_elems, the scratch tail and the library's buffers are not.
+    minres_model.banded_indefinite(2500): half of the spectrum on either side of 0 (tests/test_minres_model_host.py), and wide enough for the
+    phase and window layouts to form"""
+    dtype = _dtype(prec)
+    n, _, rp, ci, va = MM.banded_indefinite(2500, dtype)
+    S = System(n, rp, ci, va, **K.ALL_LAYOUTS[layout])
+    try:
+        i = S.H.info
+        if layout in ("phases", "phases_tags_pieces"):
+            assert i.col_phases > 1, i.col_phases
+        if layout in ("window", "phases", "phases_tags_pieces"):
+            assert i.x_window > 0, i.x_window
+        b, x0, minv = KM.inputs(n, dtype)
+        for pre, start, shift in ((None, None, 0.0), (minv, x0, 0.25)):
+            _trajectory(S, b, start, pre, shift, ("layout", layout, prec, shift), kmax=3, offs=_offs(dtype)[:1])
     finally:
         S.close()
 

@@ -13,6 +13,7 @@ import pytest
 import cases as K
 import cvr_amd
 from cvr_amd import capi, synth
+from fuzz_checks import _bits_equal, _expect          # (shared with test_gpu_fuzz_derived.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,10 +34,6 @@ def _cases(dtype):
 
 def _tdt(H):
     return torch.float64 if H.dtype == np.float64 else torch.float32
-
-
-def _bits_equal(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def _plain(H, x, stream=None):
@@ -60,17 +57,6 @@ def _scaled(H, x, y0, alpha, beta, x_null=False, stream=None):
     H.spmv_scaled_device(None if x_null else xt.data_ptr(), yt.data_ptr(), alpha, beta, stream=stream)
     torch.cuda.synchronize()
     return yt[: H.nrows].cpu().numpy()
-
-
-def _expect(s, y0, alpha, beta, dtype):
-    """the contract in numpy: alpha and beta rounded to the type, two rounded products and a rounded sum; beta = 0 reads no y, alpha = 0 no s"""
-    a, b = dtype(alpha), dtype(beta)
-    with np.errstate(all="ignore"):
-        if a == 0:
-            return (b * y0).astype(dtype) if b != 0 else np.zeros_like(y0)
-        if b == 0:
-            return (a * s).astype(dtype)
-        return (a * s + b * y0).astype(dtype)
 
 
 def _y0(n, dtype, seed):

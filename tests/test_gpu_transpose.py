@@ -17,6 +17,7 @@ import pytest
 import cases as K
 import cvr_amd
 from cvr_amd import capi, synth
+from fuzz_checks import _bits, _from_device, assert_same_handle, assert_transposed_product, stable_transpose          # (shared with test_gpu_fuzz_derived.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -39,38 +40,6 @@ def _cases(dtype):
     return out
 
 
-def stable_transpose(nrows, ncols, rp, ci, va):
-    """T = the CSR of A^T as the contract defines it (numpy, stable)"""
-    j0, j1 = int(rp[0]), int(rp[-1])
-    cols = ci[j0:j1].astype(np.int64)
-    pos = j0 + np.argsort(cols, kind="stable")
-    rows = np.searchsorted(rp, pos, side="right") - 1
-    rpt = np.zeros(ncols + 1, dtype=np.int64)
-    rpt[1:] = np.cumsum(np.bincount(cols, minlength=ncols))
-    return ncols, nrows, rpt, rows.astype(np.int32), np.ascontiguousarray(va[pos]), pos
-
-
-def _dev(*arrays):
-    return [torch.from_numpy(np.ascontiguousarray(a)).to("cuda") for a in arrays]
-
-
-def _from_device(nrows, ncols, rp, ci, va, opts, transpose=0, mutable_values=0):
-    """a handle from device arrays with ANY options (CvrMatrix.from_device takes a subset)"""
-    dtype = va.dtype.type
-    trp, tci, tva = _dev(rp.astype(np.int64), ci.astype(np.int32), va)
-    torch.cuda.synchronize()
-    H = cvr_amd.CvrMatrix.__new__(cvr_amd.CvrMatrix)
-    H._h = C.c_void_p()
-    H.tuning_s = 0.0
-    H.f32 = dtype == np.float32
-    H.dtype = np.float32 if H.f32 else np.float64
-    view = capi.CsrView(nrows, ncols, trp.data_ptr(), tci.data_ptr(), tva.data_ptr(), int(H.f32), 1)
-    kw = dict(opts)
-    H._build(view, nrows, ncols, 0, kw.pop("steps_per_chunk", 0), kw.pop("split_threshold", 0), kw.pop("xcd_swizzle", -1), kw.pop("x_window", -1), False, 0,
-             kw.pop("col_panels", -1), kw.pop("value_dict", -1), False, transpose=transpose, mutable_values=mutable_values, **kw)
-    return H
-
-
 def _try(fn):
     try:
         return fn(), None
@@ -78,54 +47,8 @@ def _try(fn):
         return None, e.code
 
 
-TIME_FIELDS = {name for name, _ in capi.Info._fields_ if name.endswith("_s")}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _diff_keys(H, R):
-    """the parts of the exported images that differ (column panels export no image: their y is compared)"""
-    if H.info.col_panels > 1:
-        return set()
-    a, b = H.export_image(), R.export_image()
-    assert sorted(a) == sorted(b)
-    return {k for k in a if not (a[k].shape == b[k].shape and np.array_equal(_bits(a[k]), _bits(b[k])))}
-
-
-def assert_same_handle(H, R, remake=None):
-    """every cvr_info field but the times, and the exported image bit for bit.  Interleaved images leave `target` unwritten (nothing reads it;
-    not compared) and may leave gang tables unwritten: such a key may differ only when it differs between R and a second handle of R's CSR
-    (remake())."""
-    for name, _ in capi.Info._fields_:
-        if name not in TIME_FIELDS:
-            assert getattr(H.info, name) == getattr(R.info, name), name
-    diff = _diff_keys(H, R) - ({"target"} if H.info.interleave else set())
-    if diff:
-        assert H.info.interleave and remake is not None, diff
-        R2 = remake()
-        loose = _diff_keys(R, R2)
-        R2.close()
-        assert diff <= loose <= {"target", "gbase"}, (diff, loose)
-
-
 def _x(n, dtype, seed):
     return (np.random.default_rng(seed).random(n) * 2 - 1).astype(dtype)
-
-
-def assert_transposed_product(y, nrows, ncols, rp, ci, va, x):
-    """y against numpy's A.T @ x in fp64: within 1e-12 (fp64) of sum |a x| per row of A^T; fp32 within its own rounding"""
-    j0, j1 = int(rp[0]), int(rp[-1])
-    rows = np.searchsorted(rp, np.arange(j0, j1), side="right") - 1
-    a = va[j0:j1].astype(np.float64)
-    prod = a * x.astype(np.float64)[rows]
-    want = np.bincount(ci[j0:j1], weights=prod, minlength=ncols)
-    scale = np.bincount(ci[j0:j1], weights=np.abs(prod), minlength=ncols)
-    cnt = np.bincount(ci[j0:j1], minlength=ncols)
-    tol = 1e-12 * scale if va.dtype == np.float64 else 1.2e-7 * (cnt + 2) * scale
-    err = np.abs(y.astype(np.float64) - want)
-    assert (err <= tol + 1e-300).all(), (np.flatnonzero(err > tol)[:5], err.max())
 
 
 def _check_pair(name, A, opts, dtype, check_numpy=True):

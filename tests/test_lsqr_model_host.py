@@ -226,3 +226,26 @@ def test_generators_are_what_they_say():
         assert np.linalg.matrix_rank(A) == n and ((A != 0).sum(axis=1) == (1 if n == 1 else 2)).all()
         for r in range(m):
             assert np.all(np.diff(ci[rp[r]:rp[r + 1]]) > 0)
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+def test_the_system_of_the_layout_test_converges_and_cuts_rows(prec):
+    """lsqr_model.rect_long, the system of test_gpu_lsqr.test_layouts_against_the_model: the model converges within that file's MAX_ITERS with numpy
+    products standing in for the handles, the matrix is well conditioned, and the host planner cuts rows of A and of A^T at 16 steps per chunk"""
+    dtype = np.float64 if prec == "fp64" else np.float32
+    m, n, rp, ci, va = LM.rect_long(dtype)
+    assert (m, n) == (701, 449)
+    rows = np.repeat(np.arange(m), np.diff(rp))
+    assert np.all((np.diff(ci.astype(np.int64)) > 0) | (np.diff(rows) > 0))          # sorted, no duplicates: every layout takes it
+    assert np.diff(rp).max() > 256 and np.bincount(ci, minlength=n).max() > 256
+    sv = np.linalg.svd(LM.dense_of(m, n, rp, ci, va.astype(np.float64)), compute_uv=False)
+    assert sv[-1] > 0.5 and sv[0] / sv[-1] < 8, (sv[0], sv[-1])
+    _, _, rpt, _, _ = LM.transpose_csr(m, n, rp, ci, va)
+    for p in (rp, rpt):
+        nzb = capi.plan_chunks(p, 16)["nz_begin"]
+        assert (~np.isin(nzb[1:-1], p)).any(), "no row cut over chunks"
+    prod, prod_t = _products(m, n, rp, ci, va)
+    b, x0 = LM.inputs(m, n, rp, ci, va, dtype, False)
+    for damp, start in ((0.0, x0), (0.5, None)):
+        full = LM.LsqrModel(prod, prod_t, dtype).run(b, start, damp, rtol=RTOL[dtype], max_iters=400)
+        assert full.last.terminal and full.last.status == KM.CONVERGED and 3 < len(full.steps) < 200, (damp, full.last, len(full.steps))

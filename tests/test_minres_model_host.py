@@ -271,3 +271,18 @@ def test_compare_rejects_a_stop_test_on_the_wrong_norm():
     rtol = float(e.residual_norm) / np.sqrt(float(e.b_norm) * b2)
     k, msg = _first_difference(_StopOnThe2Norm, dtype, True, 0.0, rtol)
     assert k is not None and k <= 3, (k, msg)
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+def test_the_system_of_the_layout_test_is_indefinite_and_converges(prec):
+    """minres_model.banded_indefinite(2500), the system of test_gpu_minres.test_every_layout_against_the_model"""
+    dtype = _dtype(prec)
+    n, _, rp, ci, va = MM.banded_indefinite(2500, dtype)
+    A = MM.dense_of(n, rp, ci, va.astype(np.float64))
+    assert np.array_equal(A, A.T)
+    ev = np.linalg.eigvalsh(A)
+    assert (ev < -0.4).sum() == n // 2 and (ev > 0.4).sum() == n - n // 2 and np.abs(ev).max() < 1.6, (ev.min(), ev.max(), np.abs(ev).min())
+    b, x0, minv = KM.inputs(n, dtype)
+    for pre, start, shift in ((None, None, 0.0), (minv, x0, 0.25)):
+        full = MM.MinresModel(_product(rp, ci, va), dtype).run(b, start, pre, shift, rtol=RTOL[dtype], max_iters=400)
+        assert full.last.terminal and full.last.status == KM.CONVERGED and 3 < len(full.steps) < 200, (shift, full.last, len(full.steps))
