@@ -117,6 +117,23 @@ class MinresInfo(C.Structure):
     _fields_ = [("anorm", C.c_double), ("acond", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+EIG_MAX_NCV = 64            # include/cvr_amd.h: CVR_EIG_MAX_NCV
+EIG_LARGEST, EIG_SMALLEST = 0, 1
+EIG_CONVERGED, EIG_MAX_RESTARTS, EIG_BREAKDOWN, EIG_INVARIANT = 0, 1, 2, 3
+EIG_EPS23 = 3.666852862501036e-11   # include/cvr_amd.h: CVR_EIG_EPS23
+
+
+class EigOptions(C.Structure):
+    """cvr_eig_options"""
+    _fields_ = [("nev", C.c_int32), ("ncv", C.c_int32), ("which", C.c_int32), ("max_restarts", C.c_int32), ("tol", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class EigResult(C.Structure):
+    """cvr_eig_result"""
+    _fields_ = [("nconv", C.c_int32), ("status", C.c_int32), ("restarts", C.c_int32), ("spmv_count", C.c_int32), ("seconds", C.c_double),
+                ("max_estimate", C.c_double)]
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -131,6 +148,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
+           "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -208,6 +226,11 @@ def lib():
         L.cvr_lsqr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo)]
         L.cvr_minres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo), C.c_void_p]
         L.cvr_minres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo)]
+        L.cvr_eig_default_options.argtypes = [C.POINTER(EigOptions)]
+        L.cvr_eig_default_options.restype = None
+        L.cvr_eigsh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult), C.c_void_p]
+        L.cvr_eigsh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult)]
+        L.cvr_sym_eig_host.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -350,6 +373,22 @@ def load_mm(path, mode=MM_REFCOMPAT, cache=None):
     if hit is not None:
         out["cache_hit"] = hit
     return out
+
+
+def sym_eig_host(a, vectors=True):
+    """all eigenpairs of the symmetric matrix a (m x m, m <= EIG_MAX_NCV) by cvr_sym_eig_host: only a[i, j] with i >= j is read.  Returns (w ascending,
+    Z with the eigenvector of w[c] in column c), or w alone without vectors."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("a must be a square matrix")
+    m = a.shape[0]
+    col = np.asfortranarray(a)          # element (i, j) at i + j * m
+    w = np.zeros(max(m, 1))
+    z = np.zeros((m, m), order="F") if vectors else None
+    rc = lib().cvr_sym_eig_host(m, col.ctypes.data, max(m, 1), w.ctypes.data, None if z is None else z.ctypes.data, max(m, 1))
+    if rc:
+        raise CvrError(rc, "cvr_sym_eig_host")
+    return (w[:m], z) if vectors else w[:m]
 
 
 def fill_x(n, mode=0):
@@ -937,6 +976,59 @@ class CvrMatrix:
         if rc:
             raise CvrError(rc, "cvr_minres")
         return x[: self.nrows], res, info
+
+    def _eig_options(self, nev, which, ncv, tol, max_restarts):
+        opt = EigOptions()
+        lib().cvr_eig_default_options(C.byref(opt))
+        try:
+            opt.which = {"LA": EIG_LARGEST, "SA": EIG_SMALLEST}[which]
+        except KeyError:
+            raise ValueError(f"which = {which!r}: must be 'LA' or 'SA'") from None
+        opt.nev, opt.ncv, opt.tol, opt.max_restarts = int(nev), int(ncv), float(tol), int(max_restarts)
+        return opt
+
+    def _eig_start(self, v0):
+        """the start vector on the host: v0, or a seeded standard normal one"""
+        if v0 is None:
+            return np.random.default_rng(20261019).standard_normal(max(self.nrows, 1)).astype(self.dtype)
+        v0 = np.ascontiguousarray(v0, dtype=self.dtype)
+        if len(v0) < self.nrows:
+            raise ValueError("v0 is shorter than nrows")
+        return v0
+
+    def eigsh(self, nev, which="LA", ncv=0, tol=1e-8, v0=None, max_restarts=100, vectors=True, stream=None):
+        """the nev algebraically largest ("LA") or smallest ("SA") eigenvalues of a symmetric A and their eigenvectors by thick-restart Lanczos on the
+        device (cvr_eigsh_device).  v0: a torch device array of nrows values of the handle's type (anything with data_ptr()), or None: a seeded
+        numpy vector, copied up.  Returns (evals: numpy, ascending; evecs: a torch device array of shape (count, nrows) whose row c is the vector of
+        evals[c], or None without vectors; EigResult); count is nev, less at EIG_INVARIANT (nconv) and 0 at EIG_BREAKDOWN.  Synchronises the stream."""
+        import torch
+        opt, res = self._eig_options(nev, which, ncv, tol, max_restarts), EigResult()
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        if v0 is None:
+            v0 = torch.from_numpy(self._eig_start(None)).to("cuda")
+        n = max(self.nrows, 1)
+        evals = np.zeros(max(int(nev), 1))
+        evecs = torch.zeros((max(int(nev), 1), n), dtype=tdt, device="cuda") if vectors else None
+        torch.cuda.synchronize()
+        rc = lib().cvr_eigsh_device(self._h, v0.data_ptr(), evals.ctypes.data, None if evecs is None else evecs.data_ptr(), n, C.byref(opt), C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_eigsh_device")
+        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        return evals[:count], (None if evecs is None else evecs[:count, : self.nrows]), res
+
+    def eigsh_host(self, nev, which="LA", ncv=0, tol=1e-8, v0=None, max_restarts=100, vectors=True):
+        """the same through host arrays (cvr_eigsh).  Returns (evals, evecs: numpy of shape (nrows, count) with the vector of evals[c] in column c, or
+        None without vectors; EigResult)."""
+        opt, res = self._eig_options(nev, which, ncv, tol, max_restarts), EigResult()
+        v0 = self._eig_start(v0)
+        n = max(self.nrows, 1)
+        evals = np.zeros(max(int(nev), 1))
+        evecs = np.zeros((max(int(nev), 1), n), dtype=self.dtype) if vectors else None
+        rc = lib().cvr_eigsh(self._h, v0.ctypes.data, evals.ctypes.data, None if evecs is None else evecs.ctypes.data, n, C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_eigsh")
+        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        return evals[:count], (None if evecs is None else evecs[:count, : self.nrows].T), res
 
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
         """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device

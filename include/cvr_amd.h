@@ -872,6 +872,101 @@ int cvr_minres_device(cvr_handle *h, const void *b_dev, void *x_dev, double shif
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg; opt->minv_dev stays a device pointer */
 int cvr_minres(cvr_handle *h, const void *b_host, void *x_host, double shift, const cvr_cg_options *opt, cvr_cg_result *res, cvr_minres_info *info);
 
+/* ---- a few extreme eigenpairs of a symmetric A on the device: thick-restart Lanczos --------------------------
+ * cvr_eigsh_device / cvr_eigsh find the nev algebraically largest or smallest eigenvalues of a symmetric A and their eigenvectors: the Lanczos process
+ * with full reorthogonalisation (classical Gram-Schmidt applied twice, GMRES's kernels) and the thick restart of Wu and Simon (SIAM J. Matrix Anal. Appl.
+ * 22, 2000).  Any single-GPU handle of a square matrix works, in fp32 or fp64 and in any layout (fused-preprocess, image-cache, mutable and transposed
+ * handles included): the solver only goes through cvr_spmv_device's launch path.  The caller guarantees symmetry; nothing checks it.  (cvr_power_iteration
+ * gives one dominant pair and has no stop test.) */
+#define CVR_EIG_MAX_NCV 64
+#define CVR_EIG_LARGEST  0   /* algebraically largest  ("LA") */
+#define CVR_EIG_SMALLEST 1   /* algebraically smallest ("SA") */
+#define CVR_EIG_CONVERGED    0
+#define CVR_EIG_MAX_RESTARTS 1
+#define CVR_EIG_BREAKDOWN    2   /* a sum that is not finite: NaN/Inf in A or v0, or v0 == 0 */
+#define CVR_EIG_INVARIANT    3   /* the Krylov space closed with fewer than nev columns; nconv exact pairs returned */
+#define CVR_EIG_EPS23 3.666852862501036e-11   /* eps23 below: ARPACK's eps^(2/3) for eps = 2^-52, as this literal */
+
+typedef struct {
+    int32_t nev;              /* pairs wanted, >= 1                                                          */
+    int32_t ncv;              /* m, the columns of the basis: 0 = min(n, max(2 * nev + 1, 20), 64), else nev + 2 .. CVR_EIG_MAX_NCV */
+    int32_t which;            /* CVR_EIG_LARGEST or CVR_EIG_SMALLEST                                         */
+    int32_t max_restarts;     /* >= 0; 0: one cycle of m steps                                               */
+    double  tol;              /* finite, >= 0: pair c has converged when e_c <= tol * max(eps23, |theta_c|)  */
+    int32_t reserved[4];      /* must be 0 (CVR_ERR_INVALID otherwise)                                       */
+} cvr_eig_options;        /* 40 bytes */
+typedef struct {
+    int32_t nconv;            /* wanted pairs that have converged (CVR_EIG_INVARIANT: the pairs returned)    */
+    int32_t status;           /* CVR_EIG_*                                                                   */
+    int32_t restarts;         /* restarts done                                                               */
+    int32_t spmv_count;       /* steps enqueued, those behind a stop included                                */
+    double  seconds;          /* HIP events around everything enqueued                                       */
+    double  max_estimate;     /* the largest e_c / max(eps23, |theta_c|) among the returned pairs            */
+} cvr_eig_result;         /* 32 bytes */
+
+/* nev = 1, ncv = 0, CVR_EIG_LARGEST, max_restarts = 100, tol = 1e-8, reserved = 0 */
+void cvr_eig_default_options(cvr_eig_options *opt);
+/* v0_dev: the start vector, n = nrows values of the handle's type T in the memory of the handle's device, any alignment of T; it is not written.
+ * evals_host receives the eigenvalues found, nev doubles in ascending order (CVR_EIG_INVARIANT: the first nconv; CVR_EIG_BREAKDOWN: nothing is written,
+ * to evals_host or to evecs_dev).  evecs_dev may be NULL (values only: the same evals); otherwise the vector of evals_host[c] is column c, n values of T
+ * at evecs_dev + c * ldv, ldv >= n, any alignment; values at positions >= n of a column are not touched.
+ * The buffers of the call are the library's, in one allocation per call: m + 1 basis vectors of info.x_elems values whose element ncols stays 0, w of
+ * info.yext_elems values, and nev + (m - nev) / 2 more vectors that take the restart's output (which is then copied back over the basis: no kernel reads
+ * a column that another workgroup of the same launch may be writing).
+ * Arithmetic, T = the handle's type, m = ncv; every operation below is rounded on its own (no fused multiply-add); scalars are fp64.  Every sum a.b is
+ * cvr_cg_device's fixed tree over the terms double(a_i) * double(b_i), and each sum has its own 1024 partials.
+ *   Start: s = v0.v0.  s not finite or not > 0: CVR_EIG_BREAKDOWN, nothing is written.  Otherwise v_0 = T(double(v0) / sqrt(s)).  The first cycle runs
+ *     the steps j = 0 .. m-1; a cycle behind a restart that kept k columns runs j = k .. m-1.
+ *   Step j (basis column j): w = A v_j through cvr_spmv_device's launch path (bit for bit its y).  Then cvr_gmres_device's two Gram-Schmidt passes
+ *     against v_0 .. v_j, unchanged.  Pass 1: h_i = v_i . w for i = 0..j, all on the same w; then t = double(w), t = t - h_0 * double(v_0), ...,
+ *     t = t - h_j * double(v_j) in that order, w = T(t) (one rounding to T).  Pass 2, the same on the new w with d_i = v_i . w.
+ *     alpha_j = h_j + d_j (the other coefficients only orthogonalise: they do not enter the projected matrix).
+ *     ww1 = w.w between the two passes, ww = w.w of the new w;  beta_(j+1) = sqrt(ww).  ww1, ww or alpha_j not finite: CVR_EIG_BREAKDOWN.
+ *     ww <= 0.25 * ww1 -- which beta_(j+1) == 0 satisfies --: the Krylov space is invariant (closed) with q = j + 1 columns, and the cycle ends there
+ *     (below).  (The second pass takes away only what rounding left of the first; where it halves the norm once more, w is rounding noise inside
+ *     the span of the basis -- "twice is enough", Daniel, Gragg, Kaufman and Stewart, Math. Comp. 30, 1976 -- and normalising it would put a column
+ *     of noise into the basis.  A test for an exact zero alone would miss every closed space but the exactly representable ones.)
+ *     Otherwise v_(j+1) = T(double(w) / beta_(j+1)).
+ *   The projected matrix P of q columns (q = m at the end of a full cycle), symmetric: in the first cycle tridiagonal, P_(j,j) = alpha_j,
+ *     P_(j+1,j) = beta_(j+1).  Behind a restart that kept k columns: P_(c,c) = theta_c for c < k, the arrow P_(k,c) = s_c in row and column k, and from
+ *     there tridiagonal as before (P_(j,j) = alpha_j for j >= k, P_(j+1,j) = beta_(j+1)).  alpha and beta stay in a state cell on the device, which the
+ *     host reads once per cycle; theta and s are the host's from the restart.
+ *   End of a cycle: cvr_sym_eig_host of P gives theta_0 <= .. <= theta_(q-1) and the orthonormal S.  The wanted pairs are the min(nev, q) at the chosen
+ *     end (CVR_EIG_LARGEST: q - nev .. q - 1), kept in ascending order.  The estimate of pair c is e_c = |beta_q * S[q-1,c]| (a closed space: beta_q = 0),
+ *     and the pair has converged when e_c <= tol * max(eps23, |theta_c|) with eps23 = CVR_EIG_EPS23, the decimal literal above (not a pow call).
+ *     nconv = the wanted pairs that have converged.  The cycle ends the call
+ *       when nconv == nev, or the space is closed with q >= nev: CVR_EIG_CONVERGED (a closed space: every pair is exact and nconv = nev);
+ *       when the space is closed with q < nev: CVR_EIG_INVARIANT, the q pairs are returned and nconv = q;
+ *       when restarts == max_restarts: CVR_EIG_MAX_RESTARTS, the wanted pairs as they are, nconv as counted.
+ *     max_estimate = the largest e_c / max(eps23, |theta_c|) among the returned pairs.
+ *   Thick restart: k = nev + min(nconv, (m - nev) / 2) in integers (at most m - 1, because m >= nev + 2).  The k Ritz pairs at the wanted end are kept, in
+ *     ascending order (CVR_EIG_LARGEST: c-th kept pair = pair m - k + c): theta_c, s_c = beta_m * S[m-1,c], and per value
+ *     u = +0, u = u + S[l,c] * double(v_l) for l = 0 .. m-1 ascending (each product and each addition rounded on its own), new v_c = T(u).
+ *     The new v_k is the old v_m.  The cycle continues at step k.
+ *   The eigenvectors returned are formed by the same rule from the q columns into evecs_dev; they are not renormalised.
+ * restarts = the restarts done; spmv_count = the steps enqueued: m in the first cycle and m - k in each later one, whether or not a breakdown or a closed
+ * space ends the cycle early (the kernels behind it return without writing).  Five vector launches beside the SpMV per step, whatever j; a restart is one
+ * launch of the product and two device copies.
+ * Ordering: everything is enqueued on `stream` (NULL = HIP's null stream), which is synchronised once per cycle and once before the call returns: it
+ * cannot be captured in a HIP graph.  A mutable handle's image is ordered with other launches of the handle as cvr_spmv_device orders it.  Makes the
+ * handle's device current.
+ * Errors, in this order, before any device work and before the handle is looked at, each CVR_ERR_INVALID with the name in cvr_last_error: null h, v0,
+ * evals, opt or res; nev < 1; ncv other than 0 or nev + 2 .. CVR_EIG_MAX_NCV; which not one of the two values; max_restarts < 0; tol negative or not
+ * finite; a non-zero reserved word; ldv < 1 when evecs is not NULL.  Then: before cvr_preprocess: CVR_ERR_STATE; nrows != ncols: CVR_ERR_INVALID;
+ * ncv > n, or the default ncv below nev + 2 (n too small): CVR_ERR_INVALID; ldv < n with evecs: CVR_ERR_INVALID; no device memory for the call's
+ * buffers: CVR_ERR_NOMEM, nothing allocated. */
+int cvr_eigsh_device(cvr_handle *h, const void *v0_dev, double *evals_host, void *evecs_dev, int64_t ldv, const cvr_eig_options *opt, cvr_eig_result *res,
+                     void *stream);
+/* the same with host v0 and evecs (column c at evecs_host + c * ldv): copied up, cvr_eigsh_device on the handle's stream, the vectors copied back */
+int cvr_eigsh(cvr_handle *h, const void *v0_host, double *evals_host, void *evecs_host, int64_t ldv, const cvr_eig_options *opt, cvr_eig_result *res);
+/* The dense symmetric eigensolver of the projected problem, on the host: all eigenpairs of a symmetric m x m matrix, 1 <= m <= CVR_EIG_MAX_NCV, by the
+ * cyclic Jacobi method by rows in Rutishauser's form (threshold sweeps, rotations skipped where they cannot move the diagonal), plain fp64 in a fixed
+ * order: the same input gives the same bits every time.  Element (i, j) with i >= j is read at a[i + j * lda]; the other triangle is never read.
+ * w receives the eigenvalues ascending; equal values keep the order of the diagonal positions they ended at.  z (may be NULL) receives the
+ * orthonormal eigenvector of w[c] at z + c * ldz, its sign fixed so that its component of largest magnitude (the first of them) is positive.
+ * Errors: m out of range, null a or w, lda < m, ldz < m with z, an element of the triangle that is not finite: CVR_ERR_INVALID. */
+int cvr_sym_eig_host(int32_t m, const double *a, int32_t lda, double *w, double *z, int32_t ldz);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
