@@ -104,6 +104,14 @@ class ChebyshevInfo(C.Structure):
     _fields_ = [("degree", C.c_int32), ("is_f32", C.c_int32), ("lmin", C.c_double), ("lmax", C.c_double),
                 ("a", C.c_double * CHEBYSHEV_MAX_DEGREE), ("b", C.c_double * CHEBYSHEV_MAX_DEGREE)]
 
+
+class Ilu0Info(C.Structure):
+    """cvr_ilu0_info"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("levels_lower", C.c_int32), ("levels_upper", C.c_int32), ("launches_lower", C.c_int32),
+                ("launches_upper", C.c_int32), ("max_level_width", C.c_int32), ("lanes_per_row", C.c_int32), ("wide_threshold", C.c_int32),
+                ("is_f32", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
@@ -146,6 +154,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_spmv_scaled_device", "cvr_spmv_scaled", "cvr_cg_default_options", "cvr_cg_device", "cvr_cg", "cvr_cg_multi_device", "cvr_cg_multi", "cvr_bicgstab_device", "cvr_bicgstab", "cvr_gmres_device", "cvr_gmres",
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
+           "cvr_precond_ilu0", "cvr_precond_ilu0_info", "cvr_precond_ilu0_export", "cvr_ilu0_levels_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
@@ -215,6 +224,10 @@ def lib():
         L.cvr_precond_chebyshev.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32, C.c_double, C.c_double]
         L.cvr_precond_chebyshev_info.argtypes = [C.c_void_p, C.POINTER(ChebyshevInfo)]
         L.cvr_chebyshev_bounds.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
+        L.cvr_precond_ilu0.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_void_p]
+        L.cvr_precond_ilu0_info.argtypes = [C.c_void_p, C.POINTER(Ilu0Info)]
+        L.cvr_precond_ilu0_export.argtypes = [C.c_void_p, C.c_void_p]
+        L.cvr_ilu0_levels_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -304,6 +317,21 @@ def row_partition(row_ptr, nparts, row_cost_milli=0):
     if rc < 0:
         raise CvrError(int(rc), "cvr_row_partition_cost")
     return bounds
+
+
+def ilu0_levels_host(rp, ci):
+    """cvr_ilu0_levels_host: (lower_level, upper_level, n_lower, n_upper) of a square CSR pattern with sorted rows and a diagonal in every row -- the
+    level of each row in the L and the U sweep of Precond.ilu0, and the number of levels of each.  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    n = len(rp) - 1
+    lo, up = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    nlo, nup = C.c_int32(), C.c_int32()
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
+    rc = lib().cvr_ilu0_levels_host(C.byref(view), lo.ctypes.data, up.ctypes.data, C.byref(nlo), C.byref(nup))
+    if rc:
+        raise CvrError(rc, "cvr_ilu0_levels_host")
+    return lo[:n], up[:n], nlo.value, nup.value
 
 
 def last_error():
@@ -568,6 +596,53 @@ class Precond:
             raise CvrError(rc, "cvr_precond_chebyshev_info")
         return dict(degree=ci.degree, is_f32=ci.is_f32, lmin=ci.lmin, lmax=ci.lmax, a=np.array(ci.a[: ci.degree], dtype=np.float64),
                     b=np.array(ci.b[: ci.degree], dtype=np.float64))
+
+    @classmethod
+    def ilu0(cls, rp, ci, vals, device=0):
+        """cvr_precond_ilu0 from host CSR arrays of a square matrix whose rows are sorted, without duplicates and with a diagonal entry each
+        (n = len(rp) - 1; the type is vals' dtype, float32 or else float64).  Serves one stream at a time."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._ilu0_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+
+    @classmethod
+    def ilu0_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
+        """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
+        return cls._ilu0_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
+
+    @classmethod
+    def _ilu0_from_view(cls, view, device):
+        self = cls()
+        rc = lib().cvr_precond_ilu0(C.byref(self._p), C.byref(view), int(device), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_ilu0")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        return self
+
+    def ilu0_info(self):
+        """cvr_precond_ilu0_info: an Ilu0Info (n, nnz, levels_*, launches_*, max_level_width, lanes_per_row, wide_threshold, is_f32)"""
+        info = Ilu0Info()
+        rc = lib().cvr_precond_ilu0_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_ilu0_info")
+        return info
+
+    def ilu0_export(self):
+        """cvr_precond_ilu0_export: nnz values of the object's dtype in the CSR's own positions -- L strictly below the diagonal (without its unit
+        diagonal), U from the diagonal up"""
+        out = np.zeros(self.ilu0_info().nnz, dtype=self.dtype)
+        if out.size:
+            rc = lib().cvr_precond_ilu0_export(self._p, out.ctypes.data)
+            if rc:
+                raise CvrError(rc, "cvr_precond_ilu0_export")
+        return out
 
     def export(self):
         """the inverse blocks W as an array of shape (nblocks, block_size, block_size) of the object's dtype, each block row-major"""

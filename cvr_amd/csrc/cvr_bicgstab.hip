@@ -17,7 +17,8 @@
 // object (cvr_pbicgstab*).  An element of W p needs its whole block of p, so with an object s^ = W s and p^ = W p are launches of their own
 // (pbicg_apply_kernel, by cvr_precond.h's apply_pack) behind bicg_s_kernel and bicg_direction_kernel, which then run in their forms without a
 // diagonal, <T, false, true>; bicg_update_kernel<T, true, AL> reads s^ from its own buffer: seven vector launches per step.  The apply returns at its
-// top once the cell holds a stop or a half-step stop, as the bicg_* kernels do.
+// top once the cell holds a stop or a half-step stop, as the bicg_* kernels do.  An ILU(0) object (cvr_ilu0.hip) is taken in the same two places: its
+// apply is launches_lower + launches_upper launches of its own under the same rule.
 // The host side is cvr_krylov.h's driver: this file adds the step and the read-back; the cell and the bicg_* kernels are in cvr_bicg_kernels.h.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
@@ -52,12 +53,21 @@ struct Workspace {
     BiCell *cell;
 };
 
-// to = W from, with an object
+// to = W from, with an object; an ILU(0) object's apply is its own launches (cvr_precond.h: ilu0_apply), under the same rule: behind a stop or a
+// half-step stop nothing is written
 template <typename T>
 void launch_apply(const Workspace<T> &w, const cvr_precond *pc, const T *from, T *to, long long n, hipStream_t st)
 {
+    if (pc->kind == kPrecondIlu0) {
+        Ilu0Gate gate;
+        gate.stop = &w.cell->stop;          // stop and half: two adjacent words
+        gate.nstop = 2;
+        (void)ilu0_apply<T, T>(pc, from, to, gate, st);          // (a launch error stays in hipGetLastError for the caller)
+        return;
+    }
     launch(pbicg_apply_kernel<T>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, from, to, n, (const BiCell *)w.cell);
 }
+static_assert(offsetof(BiCell, half) == offsetof(BiCell, stop) + sizeof(int32_t), "the gate reads stop and half as two adjacent words");
 
 // step k up to the second SpMV: r^ . v, then alpha and s, s^ (the SpMV v = A p^ is enqueued in front).  (A kernel whose only caller's array is minv
 // has no <T, false, false> form: AL || !PRE.  With an object minv is null.)
@@ -145,7 +155,7 @@ int check_pbicgstab(const cvr_handle *h, const cvr_precond *p, const void *b, co
     if (const int rc = check_precond_args(p, opt, "cvr_pbicgstab")) return rc;
     if (const int rc = check_square_preprocessed(h, "cvr_pbicgstab", "BiCGSTAB needs")) return rc;
     if (const int rc = check_precond_pair(h, p, "cvr_pbicgstab")) return rc;
-    return check_block_jacobi(p, "cvr_pbicgstab");
+    return check_block_jacobi_or_ilu0(p, "cvr_pbicgstab");
 }
 
 int check_handle(const cvr_handle *h) { return check_square_preprocessed(h, "cvr_bicgstab", "BiCGSTAB needs"); }

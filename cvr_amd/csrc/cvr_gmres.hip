@@ -19,6 +19,9 @@
 // (not enqueued where the host knows that no v_(j+1) is formed: the cycle's or the call's last step).  x is then formed by two launches, because W
 // needs the combination u of a whole block: pgmres_u_kernel (gmres_x_kernel's loop over the owed columns, u kept in fp64 in a buffer of n doubles)
 // and pgmres_x_kernel (x = T(double(x) + W u), the apply's sum with u where it has double(r)), both under gmres_x_kernel's guard.
+// An ILU(0) object (cvr_ilu0.hip) is taken in the same places, its apply being launches_lower + launches_upper launches of its own: z_j = M^-1 v_j
+// under the stop rule, and for x the sweeps on the fp64 u (L's sweep reads u where it has double(r)) into a buffer zu of the call, then
+// cvr_ilu0.hip's ilu0_add_to_x (x = T(double(x) + double(zu))), all under gmres_x_kernel's guard.
 // The host side is cvr_krylov.h's driver: this file adds the step and the read-back (with the owed x in front of it); the cell and the gmres_*
 // kernels are in cvr_gmres_kernels.h.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
@@ -90,16 +93,24 @@ __global__ __launch_bounds__(kThreads) void pgmres_x_kernel(T *__restrict__ x, c
 template <typename T>
 struct Workspace {
     T         *V, *z, *w, *r;
+    T         *zu;          // with an ILU(0) object: M^-1 u on its way into x (n values)
     double    *u, *part_h, *part_s;
     GmresCell *cell;
     long long  stride;          // of the basis, in values
     T         *basis(int i) const { return V + (long long)i * stride; }
 };
 
-// z = W v, with an object
+// z = W v, with an object; an ILU(0) object's apply is its own launches (cvr_precond.h: ilu0_apply), under the same rule: behind a stop nothing is written
 template <typename T>
 void launch_apply(const Workspace<T> &w, const cvr_precond *pc, const T *v, long long n, hipStream_t st)
 {
+    if (pc->kind == kPrecondIlu0) {
+        Ilu0Gate gate;
+        gate.stop = &w.cell->hd.stop;
+        gate.nstop = 1;
+        (void)ilu0_apply<T, T>(pc, v, w.z, gate, st);          // (a launch error stays in hipGetLastError for the caller)
+        return;
+    }
     launch(pgmres_apply_kernel<T>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, v, w.z, n, (const GmresCell *)w.cell);
 }
 
@@ -150,7 +161,7 @@ int gmres_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, int m, c
     Arena        a;
     const size_t nx = Arena::slot(x_ext_bytes(h));          // a basis vector: whole slots, so the stride is a whole number of values
     const size_t oV = a.add((size_t)(m + 1) * nx), oz = a.add(has_z ? nx : 0), ow = a.add(y_ext_bytes(h)), orr = a.add(y_ext_bytes(h));
-    const size_t ou = a.add(pc ? sizeof(double) * (size_t)std::max<long long>(n, 1) : 0);
+    const size_t ou = a.add(pc ? sizeof(double) * (size_t)std::max<long long>(n, 1) : 0), ozu = a.add(pc && pc->kind == kPrecondIlu0 ? vec_bytes(h) : 0);
     const size_t oh = a.add(sizeof(double) * (size_t)m * kBlocks), os = a.add(sizeof(double) * 2 * kBlocks), ocell = a.add(sizeof(GmresCell));
     const hipError_t e = a.alloc();
     if (e == hipErrorOutOfMemory) {
@@ -158,7 +169,7 @@ int gmres_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, int m, c
         return fail(CVR_ERR_NOMEM, "%s: no device memory for %d basis vectors (%zu bytes)", pc ? "cvr_pgmres" : "cvr_gmres", m + 1, a.total());
     }
     HIP_TRY(e);
-    const Workspace<T> w{a.at<T>(oV), has_z ? a.at<T>(oz) : nullptr, a.at<T>(ow), a.at<T>(orr), pc ? a.at<double>(ou) : nullptr, a.at<double>(oh), a.at<double>(os),
+    const Workspace<T> w{a.at<T>(oV), has_z ? a.at<T>(oz) : nullptr, a.at<T>(ow), a.at<T>(orr), a.at<T>(ozu), pc ? a.at<double>(ou) : nullptr, a.at<double>(oh), a.at<double>(os),
                          a.at<GmresCell>(ocell), (long long)(nx / sizeof(T))};
     if (const int rc = a.begin(st)) return rc;
 
@@ -180,7 +191,16 @@ int gmres_solve(cvr_handle *h, const cvr_precond *pc, const T *b, T *x, int m, c
     int       x_lo = 0;          // the steps whose finish the x-forming kernels have looked at
     auto form_x = [&](int hi) -> int {
         if (hi > x_lo) {
-            if (pc) {
+            if (pc && pc->kind == kPrecondIlu0) {          // u, then the two sweeps on the fp64 u, then x: all under gmres_x_kernel's guard
+                launch(pgmres_u_kernel<T>, st, w.u, (const T *)w.V, w.stride, n, (const GmresCell *)w.cell, x_lo, hi);
+                HIP_TRY(hipGetLastError());
+                Ilu0Gate gate;
+                gate.owed = &w.cell->hd.owed;          // owed and owed_at: two adjacent words
+                gate.lo = x_lo;
+                gate.hi = hi;
+                if (const int rc = ilu0_apply<T, double>(pc, (const double *)w.u, w.zu, gate, st)) return rc;
+                if (const int rc = ilu0_add_to_x<T>(x, (const T *)w.zu, n, gate, al, st)) return rc;
+            } else if (pc) {
                 launch(pgmres_u_kernel<T>, st, w.u, (const T *)w.V, w.stride, n, (const GmresCell *)w.cell, x_lo, hi);
                 with_flags([&](auto AL) { launch(pgmres_x_kernel<T, AL>, st, x, static_cast<const T *>(pc->d_w), (int)pc->bs, (const double *)w.u, n, (const GmresCell *)w.cell, x_lo, hi); }, al);
             } else {
@@ -224,7 +244,7 @@ int check_pgmres(const cvr_handle *h, const cvr_precond *p, const void *b, const
     if (const int rc = check_restart(restart)) return rc;
     if (const int rc = check_square_preprocessed(h, "cvr_pgmres", "GMRES needs")) return rc;
     if (const int rc = check_precond_pair(h, p, "cvr_pgmres")) return rc;
-    return check_block_jacobi(p, "cvr_pgmres");
+    return check_block_jacobi_or_ilu0(p, "cvr_pgmres");
 }
 
 // behind the argument checks (and, with an object, behind those of the handle and the pair: check_pgmres)
@@ -236,6 +256,8 @@ int gmres_device(cvr_handle *h, const cvr_precond *pc, const void *b, void *x, i
     HIP_TRY(hipSetDevice(h->device));
     return with_value_type(h, [&](auto t) { return gmres_solve(h, pc, static_cast<const decltype(t) *>(b), static_cast<decltype(t) *>(x), m, opt, res, st); });
 }
+
+static_assert(offsetof(GmresHead, owed_at) == offsetof(GmresHead, owed) + sizeof(int32_t), "the gate reads owed and owed_at as two adjacent words");
 
 }  // namespace
 

@@ -2,11 +2,18 @@
 // cvr_chebyshev.hip: the Chebyshev kind, cvr_pcg_multi.hip: the k-wide block-Jacobi apply) and the solvers that take one (cvr_cg.hip, cvr_cg_multi.hip,
 // cvr_bicgstab.hip, cvr_gmres.hip): the struct with its kind, the block-Jacobi apply of one packet (every solver forms z = W r by this code, so the same
 // r gives the same bits in all of them), the checks every preconditioned entry point makes, and the host calls by which the CG solvers enqueue an
-// object's apply.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.
+// object's apply.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.  The ILU(0) kind (two
+// level-scheduled triangular sweeps, launches of their own in every solver): cvr_ilu0.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
-constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1;          // cvr_precond::kind
+constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2;          // cvr_precond::kind
+
+namespace cvrh {
+namespace krylov {
+struct Ilu0;          // cvr_ilu0.hip: the factors, the two schedules and the launch plans
+}
+}
 
 struct cvr_precond {
     int      device = 0;
@@ -19,6 +26,8 @@ struct cvr_precond {
     int32_t     degree = 0;
     double      lmin = 0, lmax = 0, a[CVR_CHEBYSHEV_MAX_DEGREE] = {}, b[CVR_CHEBYSHEV_MAX_DEGREE] = {};
     void       *d_zi = nullptr, *d_q = nullptr, *d_d = nullptr;          // z between the steps (x_ext values, element ncols stays 0), q = A z (y_ext), d (n)
+    // kind == kPrecondIlu0 (bs, nblocks and identity_blocks are 0, d_w is null)
+    cvrh::krylov::Ilu0 *ilu = nullptr;
 };
 
 namespace cvrh {
@@ -79,8 +88,19 @@ inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const c
 // ... and, behind both, the entry points that take block-Jacobi objects only
 inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 {
+    if (p->kind == kPrecondIlu0)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (ILU(0)): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
     if (p->kind != kPrecondBlockJacobi)
         return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (Chebyshev): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
+    return CVR_OK;
+}
+
+// ... or block-Jacobi and ILU(0) objects: BiCGSTAB and GMRES, which apply M^-1 to one vector at a time
+inline int check_block_jacobi_or_ilu0(const cvr_precond *p, const char *entry)
+{
+    if (p->kind != kPrecondBlockJacobi && p->kind != kPrecondIlu0)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (Chebyshev): this entry point takes block-Jacobi and ILU(0) objects (kinds %d and %d) only", entry, p->kind,
+                    kPrecondBlockJacobi, kPrecondIlu0);
     return CVR_OK;
 }
 
@@ -98,12 +118,32 @@ void chebyshev_release(cvr_precond *p);
 // the library exports only loses the function that went away.)
 template <typename T> __attribute__((visibility("hidden"))) int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st);
 template <typename T> __attribute__((visibility("hidden"))) int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
+// cvr_ilu0.hip: the sweeps into z, then one kernel on the solvers' grid with the partial sums and, at the start, p = z
+template <typename T> __attribute__((visibility("hidden"))) int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st);
 template <typename T>
 static int precond_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
 {
+    if (pc->kind == kPrecondIlu0) return ilu0_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
     if (pc->kind == kPrecondChebyshev) return chebyshev_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
     return block_jacobi_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
 }
+
+// cvr_ilu0.hip: z = U^-1 L^-1 r of an ILU(0) object enqueued on `st` as launches of its own (launches_lower + launches_upper of them, nothing
+// else), for the solvers that apply M^-1 to one vector at a time and for cvr_precond_apply_device.  R: the type of r -- T, or double where GMRES
+// hands over its fp64 combination.  A sweep kernel returns at its top, having written nothing, when the gate says so: a state cell that holds a
+// stop (`stop`: nstop adjacent words, any of them set), or GMRES's guard of the x-forming kernels (`owed`: the words owed and owed_at of its cell;
+// the sweep runs only when owed > 0 and lo < owed_at <= hi).  Both null: it always runs.  r must not be the object's own buffer, nor z.
+struct Ilu0Gate {
+    const int32_t *stop = nullptr;
+    int32_t        nstop = 0;
+    const int32_t *owed = nullptr;
+    int32_t        lo = 0, hi = 0;
+};
+template <typename T, typename R> __attribute__((visibility("hidden"))) int ilu0_apply(const cvr_precond *pc, const R *r, T *z, const Ilu0Gate &gate, hipStream_t st);
+// ... and what GMRES does with M^-1 u: x_i = T(double(x_i) + double(zu_i)) under the gate (one launch on the solvers' grid); al: x is 16-byte aligned
+template <typename T> __attribute__((visibility("hidden"))) int ilu0_add_to_x(T *x, const T *zu, long long n, const Ilu0Gate &gate, bool al, hipStream_t st);
+__attribute__((visibility("hidden"))) int  ilu0_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st);          // by the object's type, no gate
+__attribute__((visibility("hidden"))) void ilu0_release(cvr_precond *p);
 
 // cvr_pcg_multi.hip: the same for the blocks of batched CG (block-Jacobi only), Z = W R and per column the partial sums of r . z into that column's
 // set 1 of `part`; lv: the library's blocks take 16-byte packets.  cells: the columns' CgCells

@@ -690,6 +690,65 @@ int cvr_precond_chebyshev_info(const cvr_precond *p, cvr_chebyshev_info *info);
 #define CVR_CHEBYSHEV_LMAX_FACTOR 1.1
 int cvr_chebyshev_bounds(cvr_handle *h, int32_t power_iters, double eig_ratio, double *lmin, double *lmax, void *stream);
 
+/* ---- a third kind of cvr_precond: ILU(0), z = U^-1 L^-1 r by two level-scheduled triangular solves ------
+ * A ~ L U on A's own pattern (no fill): L unit lower triangular, U upper triangular.  Unlike the two kinds above it couples unknowns across the whole
+ * matrix, which is what PDE-type systems need: on the 5-point Laplacian it cuts CG's iterations to about a third.  Block-Jacobi objects are kind 0,
+ * Chebyshev objects kind 1, both unchanged; this is kind 2.  Like a block-Jacobi object it is independent of any handle (built from the CSR view,
+ * usable by every handle of the same n, type and device) and is not refreshed by cvr_update_values.  T = float or double by csr->is_f32.
+ * CSR input: read and checked as cvr_precond_block_jacobi reads it (arrays_on_device 0 or 1; row_ptr comes to the host once on `stream`, which is
+ *   synchronised before anything else reads the arrays) and, for the analysis, col_idx comes to the host once as well.  In addition, CVR_ERR_INVALID
+ *   with cvr_last_error naming the first offending row: the matrix is not square; a row's columns are not strictly increasing (so: sorted, no
+ *   duplicates); a row has no diagonal entry.  n = 0 is valid.
+ * Analysis, on the host, once, O(nnz).  The level of row i in L is 0 when the row has no entry left of the diagonal, else 1 + the largest level among
+ *   those columns; in U the same from the last row backwards over the entries right of the diagonal.  The rows of a level are independent; within a
+ *   level they are ordered by row number.  cvr_ilu0_levels_host returns exactly these numbers (pure host code, no device needed: host arrays only,
+ *   csr->vals is not read and may be NULL; lower_level and upper_level take n values each, *n_lower and *n_upper the number of levels).
+ * Launch plan, per sweep, built once: a level of at least wide_threshold rows is a launch of its own over all its rows; a run of consecutive narrower
+ *   levels is ONE launch of ONE workgroup (1024 threads) that walks its levels in order with a workgroup barrier between them.  No kernel ever waits
+ *   on another workgroup (no flags, no spinning, no cooperative grid, no graph).  wide_threshold = 512 unless CVR_DEBUG=ilu_wide=<w> is set when the
+ *   object is built (w = 1: one launch per level; a huge w: everything merged).  The plan changes launches, never bits.
+ * Factorisation, on the device, on L's plan, on an fp64 copy of the values.  For row i, for each k < i of the row in column order:
+ *       a_ik = a_ik / a_kk;   then for every j > k of row k that row i has as well:   a_ij = a_ij - a_ik * a_kj,
+ *   every operation rounded on its own (no fused multiply-add), so each a_ij has one fixed update order; rounded once to T at the end.  A pivot a_ii
+ *   that is zero or not finite: CVR_ERR_STATE, cvr_last_error names the lowest such row, nothing is left allocated.
+ *   cvr_precond_ilu0_export writes row_ptr[n] values of T in the CSR's own positions: L strictly below the diagonal (without its unit diagonal), U from
+ *   the diagonal up.
+ * Apply, G = lanes_per_row lanes per row: G is the power of two from ceil((nnz - n) / (2 n)) up, at least 1 and at most 64, fixed per object.  Lane l
+ *   of a row takes the entries l, l + G, .. of the row's part of the sweep's triangle in column order and forms s_l = +0 + t + t' + .. with
+ *   t = double(f_ij) * double(v_j), left to right in fp64, every product and addition rounded on its own; the lanes are combined by the xor butterfly
+ *   (s += s of lane ^ o for o = G/2 .. 1).  Then
+ *       L's sweep:  y_i = T(double(r_i) - s),       v = y;       U's sweep:  z_i = T((double(y_i) - s) / double(u_ii)),   v = z.
+ *   y is a buffer of the object, so one object serves one stream at a time (as the Chebyshev kind).  The result has the same bits every call, for every
+ *   alignment of r_dev and z_dev and for every ilu_wide.  cvr_precond_apply_device takes this kind: it enqueues launches_lower + launches_upper
+ *   launches on `stream` and nothing else, without a read-back.
+ * cvr_pcg_device / cvr_pcg take this kind: cvr_pcg_device's text holds with this apply in place of z = W r; one kernel behind the sweeps forms the
+ *   partial sums of r.z as the block-Jacobi apply does and, at the start, p = z; behind a stop x, r and p stay untouched (z is scratch).
+ *   3 + launches_lower + launches_upper + 1 launches per step; spmv_count as with block-Jacobi.
+ * cvr_pbicgstab_device / cvr_pbicgstab and cvr_pgmres_device / cvr_pgmres take this kind: their texts hold with p^ = M^-1 p, s^ = M^-1 s, z_j = M^-1 v_j
+ *   by this apply, enqueued as launches of its own where the block-Jacobi apply is.  GMRES forms x from the fp64 combination u by the same two sweeps
+ *   with u where L's sweep has double(r) (y_i = T(u_i - s)), the result zu in a buffer of the call, then x_i = T(double(x_i) + double(zu_i)).
+ *   A kernel behind a stop writes nothing that reaches x or the result; spmv_count as with block-Jacobi.
+ * cvr_precond_get_info works for this kind (block_size, nblocks and identity_blocks are 0); cvr_precond_destroy frees everything.
+ * cvr_precond_export, cvr_precond_apply_multi_device and cvr_pcg_multi_device / cvr_pcg_multi take block-Jacobi objects only: CVR_ERR_STATE behind
+ * their other checks, cvr_last_error naming the kind.  cvr_precond_chebyshev_info on this kind: CVR_ERR_INVALID.
+ * Errors of cvr_precond_ilu0: a null argument, nrows != ncols: CVR_ERR_INVALID before any device work; `device` out of range: CVR_ERR_NO_DEVICE; the
+ * view's checks above: CVR_ERR_INVALID; CVR_ERR_NOMEM: an allocation failed (nothing is left allocated).  cvr_precond_ilu0_info and
+ * cvr_precond_ilu0_export: a null argument, or an object of another kind: CVR_ERR_INVALID. */
+typedef struct {
+    int64_t n, nnz;                            /* nnz = row_ptr[n]                                                          */
+    int32_t levels_lower, levels_upper;        /* the number of levels of each sweep                                        */
+    int32_t launches_lower, launches_upper;    /* ... and of launches of each sweep per apply                               */
+    int32_t max_level_width;                   /* rows of the widest level of either sweep                                  */
+    int32_t lanes_per_row;                     /* G                                                                         */
+    int32_t wide_threshold;                    /* rows from which a level is a launch of its own                            */
+    int32_t is_f32;
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_ilu0_info;
+int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device, void *stream);
+int cvr_precond_ilu0_info(const cvr_precond *p, cvr_ilu0_info *info);
+int cvr_precond_ilu0_export(const cvr_precond *p, void *vals_host);
+int cvr_ilu0_levels_host(const cvr_csr_view *csr, int32_t *lower_level, int32_t *upper_level, int32_t *n_lower, int32_t *n_upper);
+
 /* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
