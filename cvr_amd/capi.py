@@ -112,6 +112,15 @@ class Ilu0Info(C.Structure):
                 ("is_f32", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+FSAI_MAX_ROW = 32           # include/cvr_amd.h: CVR_FSAI_MAX_ROW
+
+
+class FsaiInfo(C.Structure):
+    """cvr_fsai_info"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("max_row", C.c_int32), ("lanes_per_row", C.c_int32), ("truncated_rows", C.c_int64),
+                ("is_f32", C.c_int32), ("reserved", C.c_int32 * 9)]
+
+
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
@@ -155,6 +164,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_ilu0", "cvr_precond_ilu0_info", "cvr_precond_ilu0_export", "cvr_ilu0_levels_host",
+           "cvr_precond_fsai", "cvr_precond_fsai_info", "cvr_precond_fsai_export", "cvr_fsai_factor_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
@@ -228,6 +238,10 @@ def lib():
         L.cvr_precond_ilu0_info.argtypes = [C.c_void_p, C.POINTER(Ilu0Info)]
         L.cvr_precond_ilu0_export.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_ilu0_levels_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cvr_precond_fsai.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_void_p]
+        L.cvr_precond_fsai_info.argtypes = [C.c_void_p, C.POINTER(FsaiInfo)]
+        L.cvr_precond_fsai_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_fsai_factor_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -332,6 +346,30 @@ def ilu0_levels_host(rp, ci):
     if rc:
         raise CvrError(rc, "cvr_ilu0_levels_host")
     return lo[:n], up[:n], nlo.value, nup.value
+
+
+def fsai_factor_host(rp, ci, vals):
+    """cvr_fsai_factor_host: (row_ptr, col_idx, wa, wb, bad_row) of the FSAI factor W of a square CSR matrix with sorted rows and a diagonal in every
+    row -- what Precond.fsai computes on the device, in host code (the type is vals' dtype, float32 or else float64).  bad_row is None, or the lowest
+    row whose pivot is not finite or not > 0: the arrays then hold the rows before it.  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    f32 = np.asarray(vals).dtype == np.float32
+    dtype = np.float32 if f32 else np.float64
+    va = np.ascontiguousarray(vals, dtype=dtype)
+    n = len(rp) - 1
+    room = max(int(rp[-1]), 1) if n > 0 else 1
+    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    wrp, wci = np.zeros(n + 1, dtype=np.int64), np.zeros(room, dtype=np.int32)
+    wa, wb = np.zeros(room, dtype=dtype), np.zeros(room, dtype=dtype)
+    bad = C.c_int64(-1)
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
+    rc = lib().cvr_fsai_factor_host(C.byref(view), wrp.ctypes.data, wci.ctypes.data, wa.ctypes.data, wb.ctypes.data, C.byref(bad))
+    if rc and not (rc == ERR_STATE and bad.value >= 0):
+        raise CvrError(rc, "cvr_fsai_factor_host")
+    nnz = int(wrp[n])
+    return wrp, wci[:nnz], wa[:nnz], wb[:nnz], (None if bad.value < 0 else int(bad.value))
 
 
 def last_error():
@@ -643,6 +681,56 @@ class Precond:
             if rc:
                 raise CvrError(rc, "cvr_precond_ilu0_export")
         return out
+
+    @classmethod
+    def fsai(cls, rp, ci, vals, device=0):
+        """cvr_precond_fsai from host CSR arrays of a symmetric positive definite matrix whose rows are sorted, without duplicates and with a
+        diagonal entry each; only the entries with column <= row are read (n = len(rp) - 1; the type is vals' dtype, float32 or else float64).
+        Serves one stream at a time."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._fsai_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+
+    @classmethod
+    def fsai_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
+        """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
+        return cls._fsai_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
+
+    @classmethod
+    def _fsai_from_view(cls, view, device):
+        self = cls()
+        rc = lib().cvr_precond_fsai(C.byref(self._p), C.byref(view), int(device), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_fsai")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        return self
+
+    def fsai_info(self):
+        """cvr_precond_fsai_info: an FsaiInfo (n, nnz of W, max_row, lanes_per_row, truncated_rows, is_f32)"""
+        info = FsaiInfo()
+        rc = lib().cvr_precond_fsai_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_fsai_info")
+        return info
+
+    def fsai_export(self):
+        """cvr_precond_fsai_export: (row_ptr, col_idx, wa, wb) of W -- its own CSR pattern (A's lower triangle, a row's CVR_FSAI_MAX_ROW entries
+        nearest the diagonal at most) and the two value arrays of the object's dtype: z = Wb^T (Wa r)"""
+        i = self.fsai_info()
+        rp, ci = np.zeros(i.n + 1, dtype=np.int64), np.zeros(i.nnz, dtype=np.int32)
+        wa, wb = np.zeros(i.nnz, dtype=self.dtype), np.zeros(i.nnz, dtype=self.dtype)
+        rc = lib().cvr_precond_fsai_export(self._p, rp.ctypes.data, ci.ctypes.data if i.nnz else None, wa.ctypes.data if i.nnz else None,
+                                           wb.ctypes.data if i.nnz else None)
+        if rc:
+            raise CvrError(rc, "cvr_precond_fsai_export")
+        return rp, ci, wa, wb
 
     def export(self):
         """the inverse blocks W as an array of shape (nblocks, block_size, block_size) of the object's dtype, each block row-major"""

@@ -3,15 +3,17 @@
 // cvr_bicgstab.hip, cvr_gmres.hip): the struct with its kind, the block-Jacobi apply of one packet (every solver forms z = W r by this code, so the same
 // r gives the same bits in all of them), the checks every preconditioned entry point makes, and the host calls by which the CG solvers enqueue an
 // object's apply.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.  The ILU(0) kind (two
-// level-scheduled triangular sweeps, launches of their own in every solver): cvr_ilu0.hip's head.
+// level-scheduled triangular sweeps, launches of their own in every solver): cvr_ilu0.hip's head.  The FSAI kind (two products on the SpMV path through
+// two handles of the object's own): cvr_fsai.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
-constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2;          // cvr_precond::kind
+constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2, kPrecondFsai = 3;          // cvr_precond::kind
 
 namespace cvrh {
 namespace krylov {
 struct Ilu0;          // cvr_ilu0.hip: the factors, the two schedules and the launch plans
+struct Fsai;          // cvr_fsai.hip: W's pattern, Wa and Wb, the two handles and the three buffers
 }
 }
 
@@ -28,6 +30,8 @@ struct cvr_precond {
     void       *d_zi = nullptr, *d_q = nullptr, *d_d = nullptr;          // z between the steps (x_ext values, element ncols stays 0), q = A z (y_ext), d (n)
     // kind == kPrecondIlu0 (bs, nblocks and identity_blocks are 0, d_w is null)
     cvrh::krylov::Ilu0 *ilu = nullptr;
+    // kind == kPrecondFsai (bs, nblocks and identity_blocks are 0, d_w is null)
+    cvrh::krylov::Fsai *fsai = nullptr;
 };
 
 namespace cvrh {
@@ -88,6 +92,8 @@ inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const c
 // ... and, behind both, the entry points that take block-Jacobi objects only
 inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 {
+    if (p->kind == kPrecondFsai)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (FSAI): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
     if (p->kind == kPrecondIlu0)
         return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (ILU(0)): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
     if (p->kind != kPrecondBlockJacobi)
@@ -98,6 +104,9 @@ inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 // ... or block-Jacobi and ILU(0) objects: BiCGSTAB and GMRES, which apply M^-1 to one vector at a time
 inline int check_block_jacobi_or_ilu0(const cvr_precond *p, const char *entry)
 {
+    if (p->kind == kPrecondFsai)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (FSAI): this entry point takes block-Jacobi and ILU(0) objects (kinds %d and %d) only", entry, p->kind,
+                    kPrecondBlockJacobi, kPrecondIlu0);
     if (p->kind != kPrecondBlockJacobi && p->kind != kPrecondIlu0)
         return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (Chebyshev): this entry point takes block-Jacobi and ILU(0) objects (kinds %d and %d) only", entry, p->kind,
                     kPrecondBlockJacobi, kPrecondIlu0);
@@ -120,9 +129,12 @@ template <typename T> __attribute__((visibility("hidden"))) int block_jacobi_cg_
 template <typename T> __attribute__((visibility("hidden"))) int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
 // cvr_ilu0.hip: the sweeps into z, then one kernel on the solvers' grid with the partial sums and, at the start, p = z
 template <typename T> __attribute__((visibility("hidden"))) int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st);
+// cvr_fsai.hip: xin = r, the two products, then one kernel on the solvers' grid with z, the partial sums and, at the start, p = z
+template <typename T> __attribute__((visibility("hidden"))) int fsai_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
 template <typename T>
 static int precond_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
 {
+    if (pc->kind == kPrecondFsai) return fsai_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
     if (pc->kind == kPrecondIlu0) return ilu0_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
     if (pc->kind == kPrecondChebyshev) return chebyshev_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
     return block_jacobi_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
@@ -144,6 +156,9 @@ template <typename T, typename R> __attribute__((visibility("hidden"))) int ilu0
 template <typename T> __attribute__((visibility("hidden"))) int ilu0_add_to_x(T *x, const T *zu, long long n, const Ilu0Gate &gate, bool al, hipStream_t st);
 __attribute__((visibility("hidden"))) int  ilu0_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st);          // by the object's type, no gate
 __attribute__((visibility("hidden"))) void ilu0_release(cvr_precond *p);
+// cvr_fsai.hip: the FSAI kind behind cvr_precond_apply_device (the checks are the caller's; by the object's type) and cvr_precond_destroy
+__attribute__((visibility("hidden"))) int  fsai_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st);
+__attribute__((visibility("hidden"))) void fsai_release(cvr_precond *p);
 
 // cvr_pcg_multi.hip: the same for the blocks of batched CG (block-Jacobi only), Z = W R and per column the partial sums of r . z into that column's
 // set 1 of `part`; lv: the library's blocks take 16-byte packets.  cells: the columns' CgCells
