@@ -121,6 +121,23 @@ class FsaiInfo(C.Structure):
                 ("is_f32", C.c_int32), ("reserved", C.c_int32 * 9)]
 
 
+AMG_MAX_LEVELS = 16         # include/cvr_amd.h: CVR_AMG_MAX_LEVELS
+AMG_MAX_COARSE = 256        # include/cvr_amd.h: CVR_AMG_MAX_COARSE
+
+
+class AmgOptions(C.Structure):
+    """cvr_amg_options"""
+    _fields_ = [("max_levels", C.c_int32), ("coarse_size", C.c_int32), ("sweeps", C.c_int32), ("reserved0", C.c_int32), ("strength", C.c_double),
+                ("coarse_scale", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class AmgInfo(C.Structure):
+    """cvr_amg_info"""
+    _fields_ = [("levels", C.c_int32), ("coarse_direct", C.c_int32), ("sweeps", C.c_int32), ("is_f32", C.c_int32), ("max_levels", C.c_int32),
+                ("coarse_size", C.c_int32), ("strength", C.c_double), ("coarse_scale", C.c_double), ("operator_complexity", C.c_double),
+                ("n", C.c_int64 * AMG_MAX_LEVELS), ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("reserved", C.c_int32 * 8)]
+
+
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
@@ -165,6 +182,8 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_ilu0", "cvr_precond_ilu0_info", "cvr_precond_ilu0_export", "cvr_ilu0_levels_host",
            "cvr_precond_fsai", "cvr_precond_fsai_info", "cvr_precond_fsai_export", "cvr_fsai_factor_host",
+           "cvr_amg_default_options", "cvr_precond_amg", "cvr_precond_amg_info", "cvr_precond_amg_export_level", "cvr_amg_setup_host", "cvr_amg_hierarchy_info",
+           "cvr_amg_hierarchy_export_level", "cvr_amg_hierarchy_destroy",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
@@ -242,6 +261,14 @@ def lib():
         L.cvr_precond_fsai_info.argtypes = [C.c_void_p, C.POINTER(FsaiInfo)]
         L.cvr_precond_fsai_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_fsai_factor_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.cvr_amg_default_options.argtypes = [C.POINTER(AmgOptions)]
+        L.cvr_precond_amg.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_void_p]
+        L.cvr_precond_amg_info.argtypes = [C.c_void_p, C.POINTER(AmgInfo)]
+        L.cvr_precond_amg_export_level.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+        L.cvr_amg_setup_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(AmgOptions), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.cvr_amg_hierarchy_info.argtypes = [C.c_void_p, C.POINTER(AmgInfo)]
+        L.cvr_amg_hierarchy_export_level.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
+        L.cvr_amg_hierarchy_destroy.argtypes = [C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -370,6 +397,70 @@ def fsai_factor_host(rp, ci, vals):
         raise CvrError(rc, "cvr_fsai_factor_host")
     nnz = int(wrp[n])
     return wrp, wci[:nnz], wa[:nnz], wb[:nnz], (None if bad.value < 0 else int(bad.value))
+
+
+def amg_options(**kw):
+    """cvr_amg_default_options with the given fields replaced (max_levels, coarse_size, sweeps, strength, coarse_scale)"""
+    o = AmgOptions()
+    lib().cvr_amg_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(AmgOptions._fields_):
+            raise TypeError(f"cvr_amg_options has no field {k}")
+        setattr(o, k, v)
+    return o
+
+
+class AmgLevel:
+    """one exported level: row_ptr, col_idx, vals, dinv, agg (None on the coarsest level) and winv (the n x n inverse of a directly solved coarsest
+    level, else None)"""
+
+    def __init__(self, n, rp, ci, va, dinv, agg, winv):
+        self.n, self.rp, self.ci, self.va, self.dinv, self.agg, self.winv = n, rp, ci, va, dinv, agg, winv
+
+
+def _amg_export(call, obj, info, level, dtype):
+    """the arrays of one level through cvr_precond_amg_export_level or cvr_amg_hierarchy_export_level"""
+    n, nnz, last = int(info.n[level]), int(info.nnz[level]), level == info.levels - 1
+    rp, ci, va = np.zeros(n + 1, dtype=np.int64), np.zeros(nnz, dtype=np.int32), np.zeros(nnz, dtype=dtype)
+    dinv = np.zeros(n, dtype=dtype)
+    agg = None if last else np.zeros(n, dtype=np.int32)
+    winv = np.zeros((n, n), dtype=dtype) if last and info.coarse_direct else None
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None          # noqa: E731
+    rc = call(obj, level, rp.ctypes.data, ptr(ci), ptr(va), ptr(dinv), ptr(agg), ptr(winv))
+    if rc:
+        raise CvrError(rc, "cvr_amg export_level")
+    return AmgLevel(n, rp, ci, va, dinv, agg, winv)
+
+
+def amg_setup_host(rp, ci, vals, **options):
+    """cvr_amg_setup_host: (AmgInfo, [AmgLevel, ...]) of the AMG hierarchy of a square CSR matrix with sorted rows and a diagonal in every row -- what
+    Precond.amg builds, in host code (the type is vals' dtype, float32 or else float64; options as amg_options).  A diagonal entry or a pivot of the
+    coarsest matrix that is not finite or not > 0 raises CvrError (ERR_STATE) with .bad = (level, row).  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    f32 = np.asarray(vals).dtype == np.float32
+    dtype = np.float32 if f32 else np.float64
+    va = np.ascontiguousarray(vals, dtype=dtype)
+    n = len(rp) - 1
+    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    L = lib()
+    opt = amg_options(**options)
+    h, bad_level, bad_row = C.c_void_p(), C.c_int32(-1), C.c_int64(-1)
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
+    rc = L.cvr_amg_setup_host(C.byref(h), C.byref(view), C.byref(opt), C.byref(bad_level), C.byref(bad_row))
+    if rc:
+        e = CvrError(rc, "cvr_amg_setup_host")
+        e.bad = (bad_level.value, bad_row.value) if bad_level.value >= 0 else None
+        raise e
+    try:
+        info = AmgInfo()
+        rc = L.cvr_amg_hierarchy_info(h, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_amg_hierarchy_info")
+        return info, [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
+    finally:
+        L.cvr_amg_hierarchy_destroy(h)
 
 
 def last_error():
@@ -731,6 +822,50 @@ class Precond:
         if rc:
             raise CvrError(rc, "cvr_precond_fsai_export")
         return rp, ci, wa, wb
+
+    @classmethod
+    def amg(cls, matrix, rp, ci, vals, **options):
+        """cvr_precond_amg: one V-cycle of plain aggregation AMG for the symmetric positive definite `matrix` (a CvrMatrix, borrowed for level 0's
+        products and kept alive here; close the object before the matrix), from host CSR arrays of the same matrix whose rows are sorted, without
+        duplicates and with a diagonal entry each.  options: max_levels, coarse_size, sweeps, strength, coarse_scale.  Serves one stream at a time."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options)
+
+    @classmethod
+    def amg_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, **options):
+        """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
+        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options)
+
+    @classmethod
+    def _amg_from_view(cls, matrix, view, options):
+        self = cls()
+        opt = amg_options(**options)
+        rc = lib().cvr_precond_amg(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_amg")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        self._matrix = matrix
+        return self
+
+    def amg_info(self):
+        """cvr_precond_amg_info: an AmgInfo (levels, coarse_direct, the options, operator_complexity, n and nnz of every level)"""
+        info = AmgInfo()
+        rc = lib().cvr_precond_amg_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_amg_info")
+        return info
+
+    def amg_export_level(self, level):
+        """cvr_precond_amg_export_level: an AmgLevel (row_ptr, col_idx, vals, dinv, agg, winv) of level 0 .. levels - 1"""
+        return _amg_export(lib().cvr_precond_amg_export_level, self._p, self.amg_info(), level, self.dtype)
 
     def export(self):
         """the inverse blocks W as an array of shape (nblocks, block_size, block_size) of the object's dtype, each block row-major"""

@@ -1,0 +1,481 @@
+// cvr_amg.hip -- plain (unsmoothed) aggregation AMG, the fifth kind of cvr_precond (include/cvr_amd.h: cvr_precond_amg, cvr_precond_amg_info,
+// cvr_precond_amg_export_level; the set-up, all of it on the host: cvr_amg_host.cpp).  The apply is one V-cycle that never leaves the SpMV path:
+// every level's operator is a handle (level 0: the caller's, borrowed; the coarse levels: the object's own, from device arrays with the default
+// options), the smoother is l1-Jacobi (one product and one element-wise kernel), the restriction a segmented sum over an aggregate-members CSR (one
+// lane per aggregate, rows ascending: no atomics, one order), the prolongation a gather.  No triangular sweep, no level schedule, no dot product, no
+// read-back, no kernel that waits on another workgroup.
+//   Per level: r (n values), z (an SpMV input: element n stays 0 -- the kernels write elements 0 .. n - 1 only, and no product writes into a z),
+//     q (an SpMV output), dinv, and above the coarsest level agg, mrp and mem.  No buffer is one product's output and another one's input, so
+//     there is no pad slot to zero between products.
+//   Apply: amg_in_kernel (r_0 = r) | down: amg_first_kernel, [product, amg_smooth_kernel] x (sweeps - 1), product, amg_restrict_kernel | the
+//     coarsest level: amg_dense_kernel (z = W r, one workgroup, a thread per row) or 2 * sweeps sweeps | up: amg_prolong_kernel, [product,
+//     amg_smooth_kernel] x sweeps | amg_out_kernel (z = z_0), or inside cvr_pcg_device amg_rz_kernel in its place (z = z_0 with the partial sums of
+//     r . z and, at the start, p = z; nothing behind a stop).  The level kernels take a thread per element on a grid cut to the level's size; the
+//     first and the last run on the solvers' grid.
+// (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
+#include "cvr_krylov.h"
+#include "cvr_cg_kernels.h"
+#include "cvr_precond.h"
+#include "cvr_amg.h"
+
+using namespace cvrh;
+using namespace cvrh::krylov;
+
+namespace cvrh {
+namespace krylov {
+
+struct AmgLevel {
+    int64_t     n = 0, nc = 0;
+    cvr_handle *h = nullptr;          // level 0: borrowed; a directly solved coarsest level: none
+    bool        own = false;
+    void       *d_dinv = nullptr, *d_agg = nullptr, *d_mrp = nullptr, *d_mem = nullptr;
+    void       *d_r = nullptr, *d_z = nullptr, *d_q = nullptr;
+};
+
+struct Amg {
+    amg::Hierarchy        H;          // the host's copy: what the info and the export return
+    std::vector<AmgLevel> lv;
+    void                 *d_winv = nullptr;
+    int                   products = 0;          // of one apply
+};
+
+}  // namespace krylov
+}  // namespace cvrh
+
+namespace {
+
+// ---- the device half
+
+// r0 = r.  AL: r, the caller's array, is 16-byte aligned
+template <typename T, bool AL>
+__global__ __launch_bounds__(kThreads) void amg_in_kernel(const T *__restrict__ r, T *__restrict__ r0, long long n)
+{
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T v[kPack<T>];
+        load_pack<T, AL>(r, e, (int)cnt, v);
+        store_pack<T, true>(r0, e, (int)cnt, v);
+    }
+}
+
+// z = z0.  AL: z, the caller's array, is 16-byte aligned
+template <typename T, bool AL>
+__global__ __launch_bounds__(kThreads) void amg_out_kernel(const T *__restrict__ z0, T *__restrict__ z, long long n)
+{
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T v[kPack<T>];
+        load_pack<T, true>(z0, e, (int)cnt, v);
+        store_pack<T, AL>(z, e, (int)cnt, v);
+    }
+}
+
+// the same inside cvr_pcg_device: z = z0, the partial sums of r . z (the term double(r_i) * double(z_i) added in the thread that owns element i in
+// element order: pcg_apply_kernel's), and at the start p = z; behind a stop nothing is written
+template <typename T, bool START>
+__global__ __launch_bounds__(kThreads) void amg_rz_kernel(const T *__restrict__ r, const T *__restrict__ z0, T *__restrict__ z, T *__restrict__ p, long long n,
+                                                          double *__restrict__ out, const CgCell *__restrict__ cell)
+{
+    __shared__ double sh[1][kWaves];
+    if constexpr (!START)
+        if (cell->stop) return;          // (no workgroup of this kernel sets it)
+    double acc[1] = {0};
+    CVR_KRYLOV_PACKETS(T, e, cnt) {
+        T rv[kPack<T>], zv[kPack<T>];
+        load_pack<T, true>(r, e, (int)cnt, rv);
+        load_pack<T, true>(z0, e, (int)cnt, zv);
+#pragma unroll
+        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[0] += (double)rv[j] * (double)zv[j];
+        store_pack<T, true>(z, e, (int)cnt, zv);
+        if constexpr (START) store_pack<T, true>(p, e, (int)cnt, zv);
+    }
+    store_partials<1>(acc, out, sh);
+}
+
+// the elements of a thread of a level kernel: a grid-stride loop, whatever grid the level was given
+#define CVR_AMG_ELEMENTS(i, n) for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < (n); i += (long long)gridDim.x * kThreads)
+
+// z_i = T(dinv_i * r_i)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_first_kernel(const T *__restrict__ dinv, const T *__restrict__ r, T *__restrict__ z, long long n)
+{
+    CVR_AMG_ELEMENTS(i, n) z[i] = (T)((double)dinv[i] * (double)r[i]);
+}
+
+// behind q = A z: z_i = T(z_i + dinv_i * (r_i - q_i))
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_smooth_kernel(const T *__restrict__ dinv, const T *__restrict__ r, const T *__restrict__ q, T *__restrict__ z, long long n)
+{
+    CVR_AMG_ELEMENTS(i, n) z[i] = (T)((double)z[i] + (double)dinv[i] * ((double)r[i] - (double)q[i]));
+}
+
+// behind q = A z: rc_I = T(+0 + (r_i - q_i) + ..) over the rows of aggregate I, ascending; a lane per aggregate
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_restrict_kernel(const int64_t *__restrict__ mrp, const int32_t *__restrict__ mem, const T *__restrict__ r, const T *__restrict__ q,
+                                                                T *__restrict__ rc, long long nc)
+{
+    CVR_AMG_ELEMENTS(I, nc) {
+        double s = 0;
+        for (long long m = mrp[I]; m < mrp[I + 1]; m++) {
+            const int i = mem[m];
+            s = s + ((double)r[i] - (double)q[i]);
+        }
+        rc[I] = (T)s;
+    }
+}
+
+// z_i = T(z_i + scale * zc[agg_i])
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_prolong_kernel(const int32_t *__restrict__ agg, const T *__restrict__ zc, T *__restrict__ z, long long n, double scale)
+{
+    CVR_AMG_ELEMENTS(i, n) z[i] = (T)((double)z[i] + scale * (double)zc[agg[i]]);
+}
+
+// the directly solved coarsest level, n <= CVR_AMG_MAX_COARSE: z_i = T(t_0 + t_1 + ..), t_j = W_ij * r_j; W is symmetric bit for bit, so thread i
+// reads W_ji, which neighbouring threads find side by side
+template <typename T>
+__global__ __launch_bounds__(CVR_AMG_MAX_COARSE) void amg_dense_kernel(const T *__restrict__ w, const T *__restrict__ r, T *__restrict__ z, int n)
+{
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    double s = (double)w[i] * (double)r[0];
+    for (int j = 1; j < n; j++) s = s + (double)w[(size_t)j * n + i] * (double)r[j];
+    z[i] = (T)s;
+}
+
+// ---- the host half
+
+template <typename... P, typename... A>
+void launch_level(void (*kernel)(P...), long long n, hipStream_t st, A... args)
+{
+    const long long blocks = std::min<long long>((n + kThreads - 1) / kThreads, kBlocks);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<long long>(blocks, 1)), dim3(kThreads), 0, st, args...);
+}
+
+int device_alloc(void **out, size_t bytes, const char *what)
+{
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+    if (e == hipSuccess) return CVR_OK;
+    *out = nullptr;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_amg: no device memory for %s (%zu bytes)", what, bytes);
+    return fail(CVR_ERR_HIP, "cvr_precond_amg: hipMalloc of %s: %s", what, hipGetErrorString(e));
+}
+
+// a device array of the object's with the host's bytes in it
+int upload(void **out, const void *src, size_t bytes, const char *what)
+{
+    if (const int rc = device_alloc(out, bytes, what)) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    return CVR_OK;
+}
+
+int zeroed(void **out, size_t bytes, const char *what)
+{
+    if (const int rc = device_alloc(out, bytes, what)) return rc;
+    HIP_TRY(hipMemset(*out, 0, bytes ? bytes : 1));
+    return CVR_OK;
+}
+
+// The view on the host: the caller's own arrays, or copies of row_ptr, col_idx and vals brought down once on `st`, checked as cvr_precond_fsai
+// checks them
+struct HostCsr {
+    const int64_t       *rp = nullptr;
+    const int32_t       *ci = nullptr;
+    const void          *va = nullptr;
+    std::vector<int64_t> rp_own;
+    std::vector<int32_t> ci_own;
+    std::vector<uint8_t> va_own;
+};
+
+int stage_host(const cvr_csr_view *c, HostCsr &h, hipStream_t st)
+{
+    const int64_t n = c->nrows;
+    if (!c->arrays_on_device) {          // (checked before any device work: cvr_precond_amg)
+        h.rp = c->row_ptr;
+        h.ci = c->col_idx;
+        h.va = c->vals;
+        return CVR_OK;
+    }
+    try {
+        h.rp_own.assign((size_t)n + 1, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory for row_ptr (%lld rows)", (long long)n);
+    }
+    if (n > 0) {
+        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
+        HIP_TRY(hipMemcpyAsync(h.rp_own.data(), c->row_ptr, sizeof(int64_t) * h.rp_own.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    cvr_csr_view hv = *c;
+    hv.row_ptr = h.rp_own.data();
+    if (const int rc = check_csr(&hv, false)) return rc;
+    h.rp = h.rp_own.data();
+    if (n > 0) {
+        if (const int rc = check_columns_device(c->col_idx, h.rp_own.front(), h.rp_own.back(), c->ncols)) return rc;
+        const int64_t j0 = h.rp_own.front(), nnz = h.rp_own.back() - j0;
+        const size_t  vsz = c->is_f32 ? 4 : 8;
+        try {
+            h.ci_own.assign((size_t)h.rp_own.back(), 0);
+            h.va_own.assign(vsz * (size_t)h.rp_own.back(), 0);
+        } catch (const std::bad_alloc &) {
+            return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory for col_idx and vals (%lld entries)", (long long)nnz);
+        }
+        if (nnz > 0) {
+            if (!c->vals) return fail(CVR_ERR_INVALID, "vals is null");
+            HIP_TRY(hipMemcpy(h.ci_own.data() + j0, c->col_idx + j0, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(h.va_own.data() + vsz * (size_t)j0, static_cast<const uint8_t *>(c->vals) + vsz * (size_t)j0, vsz * (size_t)nnz, hipMemcpyDeviceToHost));
+        }
+    }
+    h.ci = h.ci_own.data();
+    h.va = h.va_own.data();
+    return amg::check_structure(n, h.rp, h.ci, "cvr_precond_amg");
+}
+
+// device memory that lives for the build only
+struct Scratch {
+    std::vector<void *> bufs;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch()
+    {
+        for (void *p : bufs)
+            if (p) (void)hipFree(p);
+    }
+};
+
+// a coarse level's handle: cvr_create + cvr_preprocess of device arrays with the default options on the object's device
+int make_handle(cvr_handle **out, const amg::Level &l, int is_f32, int device, Scratch &s)
+{
+    void *d_rp = nullptr, *d_ci = nullptr, *d_va = nullptr;
+    if (const int rc = upload(&d_rp, l.rp.data(), sizeof(int64_t) * l.rp.size(), "a level's row_ptr")) return rc;
+    s.bufs.push_back(d_rp);
+    if (const int rc = upload(&d_ci, l.ci.data(), sizeof(int32_t) * l.ci.size(), "a level's col_idx")) return rc;
+    s.bufs.push_back(d_ci);
+    if (const int rc = upload(&d_va, l.va.data(), l.va.size(), "a level's values")) return rc;
+    s.bufs.push_back(d_va);
+    cvr_csr_view v{};
+    v.nrows = v.ncols = l.n;
+    v.row_ptr = static_cast<const int64_t *>(d_rp);
+    v.col_idx = static_cast<const int32_t *>(d_ci);
+    v.vals = d_va;
+    v.is_f32 = is_f32;
+    v.arrays_on_device = 1;
+    cvr_options opt;
+    cvr_default_options(&opt);
+    opt.device = device;
+    if (const int rc = cvr_create(out, &v, &opt)) {
+        *out = nullptr;
+        return rc;
+    }
+    return cvr_preprocess(*out, 0, nullptr);
+}
+
+int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, hipStream_t st)
+{
+    Amg *a = p->amg;
+    {
+        HostCsr hc;
+        if (const int rc = stage_host(csr, hc, st)) return rc;
+        int32_t bad_level = -1;
+        int64_t bad_row = -1;
+        if (const int rc = amg::setup(a->H, p->n, hc.rp, hc.ci, hc.va, p->is_f32, opt, "cvr_precond_amg", &bad_level, &bad_row)) return rc;
+    }
+    const amg::Hierarchy &H = a->H;
+    const size_t          vsz = p->is_f32 ? 4 : 8, L = H.lv.size();
+    const int             sweeps = H.opt.sweeps;
+    a->products = 2 * sweeps * ((int)L - 1) + (H.coarse_direct ? 0 : 2 * sweeps - 1);
+    if (p->n == 0) return CVR_OK;
+    try {
+        a->lv.resize(L);
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory");
+    }
+    Scratch s;
+    for (size_t l = 0; l < L; l++) {
+        const amg::Level &hl = H.lv[l];
+        AmgLevel         &dl = a->lv[l];
+        const bool        last = l + 1 == L;
+        dl.n = hl.n;
+        dl.nc = hl.nc;
+        if (l == 0) dl.h = h;
+        else if (!(last && H.coarse_direct)) {
+            dl.own = true;
+            if (const int rc = make_handle(&dl.h, hl, p->is_f32, p->device, s)) return rc;
+        }
+        if (const int rc = upload(&dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
+        if (!last) {
+            if (const int rc = upload(&dl.d_agg, hl.agg.data(), sizeof(int32_t) * hl.agg.size(), "agg")) return rc;
+            if (const int rc = upload(&dl.d_mrp, hl.mrp.data(), sizeof(int64_t) * hl.mrp.size(), "the aggregates' row_ptr")) return rc;
+            if (const int rc = upload(&dl.d_mem, hl.mem.data(), sizeof(int32_t) * hl.mem.size(), "the aggregates' members")) return rc;
+        }
+        // r, z, q, zeroed: z[n] is the pad slot of an SpMV input and is never written again
+        if (const int rc = zeroed(&dl.d_r, vsz * (size_t)std::max<int64_t>(hl.n, 1), "r")) return rc;
+        if (const int rc = zeroed(&dl.d_z, dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1), "z")) return rc;
+        if (const int rc = zeroed(&dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+    }
+    if (H.coarse_direct)
+        if (const int rc = upload(&a->d_winv, H.winv.data(), H.winv.size(), "the coarsest level's inverse")) return rc;
+    HIP_TRY(hipDeviceSynchronize());          // (the handles' copies of the levels are complete before the scratch goes; the buffers are zeroed)
+    return CVR_OK;
+}
+
+template <typename T>
+int smooth_more(const AmgLevel &l, int times, hipStream_t st)
+{
+    for (int k = 0; k < times; k++) {
+        HIP_TRY(run_spmv(l.h, l.d_z, l.d_q, st));
+        launch_level(amg_smooth_kernel<T>, l.n, st, static_cast<const T *>(l.d_dinv), static_cast<const T *>(l.d_r), static_cast<const T *>(l.d_q), static_cast<T *>(l.d_z), (long long)l.n);
+    }
+    return CVR_OK;
+}
+
+// r_0 = r | the cycle: z_0 holds the result
+template <typename T>
+int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
+{
+    const Amg      *a = pc->amg;
+    const size_t    L = a->lv.size();
+    const int       sweeps = a->H.opt.sweeps;
+    const long long n = pc->n;
+    with_flags([&](auto AL) { launch(amg_in_kernel<T, AL>, st, r, static_cast<T *>(a->lv[0].d_r), n); }, al);
+    HIP_TRY(hipGetLastError());
+    for (size_t l = 0; l + 1 < L; l++) {
+        const AmgLevel &f = a->lv[l], &c = a->lv[l + 1];
+        launch_level(amg_first_kernel<T>, f.n, st, static_cast<const T *>(f.d_dinv), static_cast<const T *>(f.d_r), static_cast<T *>(f.d_z), (long long)f.n);
+        if (const int rc = smooth_more<T>(f, sweeps - 1, st)) return rc;
+        HIP_TRY(run_spmv(f.h, f.d_z, f.d_q, st));
+        launch_level(amg_restrict_kernel<T>, f.nc, st, static_cast<const int64_t *>(f.d_mrp), static_cast<const int32_t *>(f.d_mem), static_cast<const T *>(f.d_r), static_cast<const T *>(f.d_q),
+                     static_cast<T *>(c.d_r), (long long)f.nc);
+    }
+    const AmgLevel &last = a->lv[L - 1];
+    if (a->H.coarse_direct)
+        hipLaunchKernelGGL(amg_dense_kernel<T>, dim3(1), dim3(CVR_AMG_MAX_COARSE), 0, st, static_cast<const T *>(a->d_winv), static_cast<const T *>(last.d_r), static_cast<T *>(last.d_z), (int)last.n);
+    else {
+        launch_level(amg_first_kernel<T>, last.n, st, static_cast<const T *>(last.d_dinv), static_cast<const T *>(last.d_r), static_cast<T *>(last.d_z), (long long)last.n);
+        if (const int rc = smooth_more<T>(last, 2 * sweeps - 1, st)) return rc;
+    }
+    for (size_t l = L - 1; l-- > 0;) {
+        const AmgLevel &f = a->lv[l], &c = a->lv[l + 1];
+        launch_level(amg_prolong_kernel<T>, f.n, st, static_cast<const int32_t *>(f.d_agg), static_cast<const T *>(c.d_z), static_cast<T *>(f.d_z), (long long)f.n, a->H.opt.coarse_scale);
+        if (const int rc = smooth_more<T>(f, sweeps, st)) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+int amg_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
+{
+    const Amg *a = p->amg;
+    if (!a || p->n == 0) return CVR_OK;
+    const bool      ral = ((uintptr_t)r & 15u) == 0, zal = ((uintptr_t)z & 15u) == 0;
+    const long long n = p->n;
+    if (p->is_f32) {
+        if (const int rc = enqueue_cycle<float>(p, static_cast<const float *>(r), ral, st)) return rc;
+        with_flags([&](auto AL) { launch(amg_out_kernel<float, AL>, st, static_cast<const float *>(a->lv[0].d_z), static_cast<float *>(z), n); }, zal);
+    } else {
+        if (const int rc = enqueue_cycle<double>(p, static_cast<const double *>(r), ral, st)) return rc;
+        with_flags([&](auto AL) { launch(amg_out_kernel<double, AL>, st, static_cast<const double *>(a->lv[0].d_z), static_cast<double *>(z), n); }, zal);
+    }
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+
+template <typename T>
+int amg_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
+{
+    const Amg *a = pc->amg;
+    if (!a || pc->n == 0) return CVR_OK;
+    if (const int rc = enqueue_cycle<T>(pc, r, true, st)) return rc;
+    if (spmvs) *spmvs += a->products;
+    with_flags([&](auto START) { launch(amg_rz_kernel<T, START>, st, r, static_cast<const T *>(a->lv[0].d_z), z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+template int amg_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
+template int amg_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
+
+void amg_release(cvr_precond *p)
+{
+    Amg *a = p->amg;
+    if (!a) return;
+    for (AmgLevel &l : a->lv) {
+        if (l.own && l.h) (void)cvr_destroy(l.h);
+        for (void *buf : {l.d_dinv, l.d_agg, l.d_mrp, l.d_mem, l.d_r, l.d_z, l.d_q})
+            if (buf) (void)hipFree(buf);
+    }
+    if (a->d_winv) (void)hipFree(a->d_winv);
+    delete a;
+    p->amg = nullptr;
+}
+
+}  // namespace krylov
+}  // namespace cvrh
+
+extern "C" {
+
+int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream)
+{
+    if (!out || !h || !csr) return fail(CVR_ERR_INVALID, "null argument");
+    *out = nullptr;
+    cvr_amg_options o;
+    cvr_amg_default_options(&o);
+    if (opt) o = *opt;
+    if (const int rc = amg::check_options(&o, "cvr_precond_amg")) return rc;
+    if (csr->nrows != csr->ncols) return fail(CVR_ERR_INVALID, "AMG needs a square matrix (%lld x %lld)", (long long)csr->nrows, (long long)csr->ncols);
+    if (csr->nrows < 0) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
+    if (csr->nrows >= (int64_t)0x7fffffff) return fail(CVR_ERR_INVALID, "cvr_precond_amg: nrows (%lld) must stay below 2^31 - 1: the rows are the members of the aggregates", (long long)csr->nrows);
+    if (const int rc = check_square_preprocessed(h, "cvr_precond_amg", "an AMG preconditioner needs")) return rc;
+    if (h->info.nrows != csr->nrows) return fail(CVR_ERR_INVALID, "cvr_precond_amg: the view has nrows = %lld, the handle nrows = %lld", (long long)csr->nrows, (long long)h->info.nrows);
+    if ((csr->is_f32 != 0) != (h->vsz == 4)) return fail(CVR_ERR_INVALID, "cvr_precond_amg: the view's type is %s, the handle's %s", csr->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
+    if (!csr->arrays_on_device) {
+        if (const int rc = check_csr(csr, true)) return rc;
+        if (const int rc = amg::check_structure(csr->nrows, csr->row_ptr, csr->col_idx, "cvr_precond_amg")) return rc;
+    }
+    Range range("cvr_precond_amg");
+    HIP_TRY(hipSetDevice(h->device));
+    cvr_precond *p = new (std::nothrow) cvr_precond;
+    Amg         *a = new (std::nothrow) Amg;
+    if (!p || !a) {
+        delete p;
+        delete a;
+        return fail(CVR_ERR_NOMEM, "out of host memory");
+    }
+    p->kind = kPrecondAmg;
+    p->device = h->device;
+    p->n = csr->nrows;
+    p->bs = 0;
+    p->is_f32 = csr->is_f32 ? 1 : 0;
+    p->amg = a;
+    if (const int rc = build(p, h, csr, &o, (hipStream_t)stream)) {
+        char keep[sizeof(g_err)];          // (cvr_destroy of a half-made handle must not replace the message)
+        memcpy(keep, g_err, sizeof(keep));
+        cvr_precond_destroy(p);
+        memcpy(g_err, keep, sizeof(keep));
+        (void)hipSetDevice(h->device);
+        return rc;
+    }
+    *out = p;
+    return CVR_OK;
+}
+
+int cvr_precond_amg_info(const cvr_precond *p, cvr_amg_info *info)
+{
+    if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_info: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    amg::fill_info(p->amg->H, info);
+    return CVR_OK;
+}
+
+int cvr_precond_amg_export_level(const cvr_precond *p, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals, void *dinv, int32_t *agg, void *winv)
+{
+    if (!p) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_export_level: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    return amg::export_level(p->amg->H, level, row_ptr, col_idx, vals, dinv, agg, winv, "cvr_precond_amg_export_level");
+}
+
+}  // extern "C"

@@ -223,7 +223,7 @@ int cvr_precond_chebyshev_info(const cvr_precond *p, cvr_chebyshev_info *info)
 {
     if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
     if (p->kind != kPrecondChebyshev)
-        return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev_info: the preconditioner is of kind %d (%s), not a Chebyshev object", p->kind, p->kind == kPrecondIlu0 ? "ILU(0)" : p->kind == kPrecondFsai ? "FSAI" : "block-Jacobi");
+        return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev_info: the preconditioner is of kind %d (%s), not a Chebyshev object", p->kind, p->kind == kPrecondIlu0 ? "ILU(0)" : p->kind == kPrecondFsai ? "FSAI" : p->kind == kPrecondAmg ? "AMG" : "block-Jacobi");
     memset(info, 0, sizeof(*info));
     info->degree = p->degree;
     info->is_f32 = p->is_f32;

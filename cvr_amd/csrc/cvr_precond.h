@@ -4,16 +4,18 @@
 // r gives the same bits in all of them), the checks every preconditioned entry point makes, and the host calls by which the CG solvers enqueue an
 // object's apply.  How W is built and laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.  The ILU(0) kind (two
 // level-scheduled triangular sweeps, launches of their own in every solver): cvr_ilu0.hip's head.  The FSAI kind (two products on the SpMV path through
-// two handles of the object's own): cvr_fsai.hip's head.
+// two handles of the object's own): cvr_fsai.hip's head.  The AMG kind (one V-cycle: a handle per level, l1-Jacobi sweeps, a segmented sum down and a
+// gather up): cvr_amg.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
-constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2, kPrecondFsai = 3;          // cvr_precond::kind
+constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2, kPrecondFsai = 3, kPrecondAmg = 4;          // cvr_precond::kind
 
 namespace cvrh {
 namespace krylov {
 struct Ilu0;          // cvr_ilu0.hip: the factors, the two schedules and the launch plans
 struct Fsai;          // cvr_fsai.hip: W's pattern, Wa and Wb, the two handles and the three buffers
+struct Amg;           // cvr_amg.hip: the hierarchy, a handle and three buffers per level
 }
 }
 
@@ -32,6 +34,8 @@ struct cvr_precond {
     cvrh::krylov::Ilu0 *ilu = nullptr;
     // kind == kPrecondFsai (bs, nblocks and identity_blocks are 0, d_w is null)
     cvrh::krylov::Fsai *fsai = nullptr;
+    // kind == kPrecondAmg (bs, nblocks and identity_blocks are 0, d_w is null)
+    cvrh::krylov::Amg *amg = nullptr;
 };
 
 namespace cvrh {
@@ -92,6 +96,8 @@ inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const c
 // ... and, behind both, the entry points that take block-Jacobi objects only
 inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 {
+    if (p->kind == kPrecondAmg)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (AMG): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
     if (p->kind == kPrecondFsai)
         return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (FSAI): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, kPrecondBlockJacobi);
     if (p->kind == kPrecondIlu0)
@@ -104,6 +110,9 @@ inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 // ... or block-Jacobi and ILU(0) objects: BiCGSTAB and GMRES, which apply M^-1 to one vector at a time
 inline int check_block_jacobi_or_ilu0(const cvr_precond *p, const char *entry)
 {
+    if (p->kind == kPrecondAmg)
+        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (AMG): this entry point takes block-Jacobi and ILU(0) objects (kinds %d and %d) only", entry, p->kind,
+                    kPrecondBlockJacobi, kPrecondIlu0);
     if (p->kind == kPrecondFsai)
         return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (FSAI): this entry point takes block-Jacobi and ILU(0) objects (kinds %d and %d) only", entry, p->kind,
                     kPrecondBlockJacobi, kPrecondIlu0);
@@ -131,9 +140,12 @@ template <typename T> __attribute__((visibility("hidden"))) int chebyshev_cg_app
 template <typename T> __attribute__((visibility("hidden"))) int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st);
 // cvr_fsai.hip: xin = r, the two products, then one kernel on the solvers' grid with z, the partial sums and, at the start, p = z
 template <typename T> __attribute__((visibility("hidden"))) int fsai_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
+// cvr_amg.hip: r_0 = r, the cycle, then one kernel on the solvers' grid with z, the partial sums and, at the start, p = z
+template <typename T> __attribute__((visibility("hidden"))) int amg_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
 template <typename T>
 static int precond_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
 {
+    if (pc->kind == kPrecondAmg) return amg_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
     if (pc->kind == kPrecondFsai) return fsai_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
     if (pc->kind == kPrecondIlu0) return ilu0_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st);
     if (pc->kind == kPrecondChebyshev) return chebyshev_cg_apply<T>(pc, r, z, p, part_rz, cell, start, st, spmvs);
@@ -159,6 +171,9 @@ __attribute__((visibility("hidden"))) void ilu0_release(cvr_precond *p);
 // cvr_fsai.hip: the FSAI kind behind cvr_precond_apply_device (the checks are the caller's; by the object's type) and cvr_precond_destroy
 __attribute__((visibility("hidden"))) int  fsai_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st);
 __attribute__((visibility("hidden"))) void fsai_release(cvr_precond *p);
+// cvr_amg.hip: the same for the AMG kind
+__attribute__((visibility("hidden"))) int  amg_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st);
+__attribute__((visibility("hidden"))) void amg_release(cvr_precond *p);
 
 // cvr_pcg_multi.hip: the same for the blocks of batched CG (block-Jacobi only), Z = W R and per column the partial sums of r . z into that column's
 // set 1 of `part`; lv: the library's blocks take 16-byte packets.  cells: the columns' CgCells

@@ -1,5 +1,5 @@
 // cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*); the entry points all kinds of object share hand the
-// Chebyshev kind on to cvr_chebyshev.hip, the ILU(0) kind on to cvr_ilu0.hip and the FSAI kind on to cvr_fsai.hip (apply, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into
+// Chebyshev kind on to cvr_chebyshev.hip, the ILU(0) kind on to cvr_ilu0.hip, the FSAI kind on to cvr_fsai.hip and the AMG kind on to cvr_amg.hip (apply, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into
 // LDS, inverts them there in fp64 and stores the inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for
 // the elements CVR_KRYLOV_PACKETS gives it (cvr_precond.h: the struct and the apply of one packet, shared with cvr_bicgstab.hip and cvr_gmres.hip).
 //   precond_build_kernel   one wavefront per workgroup; L = 8, 16 or 32 lanes per block (the power of two from bs up), 64 / L blocks per wavefront
@@ -380,6 +380,7 @@ int cvr_precond_apply_device(const cvr_precond *p, const void *r_dev, void *z_de
     if (p->kind == kPrecondChebyshev) return chebyshev_apply(p, r_dev, z_dev, st);
     if (p->kind == kPrecondIlu0) return ilu0_apply_any(p, r_dev, z_dev, st);
     if (p->kind == kPrecondFsai) return fsai_apply_any(p, r_dev, z_dev, st);
+    if (p->kind == kPrecondAmg) return amg_apply_any(p, r_dev, z_dev, st);
     const bool        al = ((uintptr_t)z_dev & 15u) == 0;
     const long long   n = p->n;
     if (p->is_f32)
@@ -408,6 +409,10 @@ int cvr_precond_destroy(cvr_precond *p)
     if (p->fsai) {
         (void)hipSetDevice(p->device);
         fsai_release(p);
+    }
+    if (p->amg) {
+        (void)hipSetDevice(p->device);
+        amg_release(p);
     }
     delete p;
     return CVR_OK;

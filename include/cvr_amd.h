@@ -807,6 +807,104 @@ int cvr_precond_fsai_info(const cvr_precond *p, cvr_fsai_info *info);
 int cvr_precond_fsai_export(const cvr_precond *p, int64_t *row_ptr, int32_t *col_idx, void *wa, void *wb);
 int cvr_fsai_factor_host(const cvr_csr_view *csr, int64_t *row_ptr, int32_t *col_idx, void *wa, void *wb, int64_t *bad_row);
 
+/* ---- a fifth kind of cvr_precond: aggregation AMG, one V-cycle on the SpMV path ------------------------
+ * Plain (unsmoothed) aggregation algebraic multigrid for a symmetric positive definite A: the only multilevel kind.  The four kinds above are
+ * one-level methods, whose step count on a mesh problem grows with the mesh width; a V-cycle's grows far more slowly (5-point Laplacian, PCG steps
+ * to 1e-8, plain CG / this kind: 24 x 24: 77 / 27, 40 x 40: 125 / 32, 100 x 100: 307 / 54).  Every level's operator is a handle, the smoother is
+ * l1-Jacobi (one product and one element-wise kernel), restriction is a segmented sum and prolongation a gather, because the prolongator is
+ * piecewise constant.  Kinds 0 .. 3 are unchanged; this is kind 4.  T = float or double by csr->is_f32.
+ * The object borrows `h`, the caller's preprocessed handle of the same matrix (any layout), as a Chebyshev object does: it is used for level 0's
+ *   products and must outlive the object; n, type and device are the handle's and must be the view's.  It is not refreshed by cvr_update_values.
+ * CSR input: read and checked exactly as cvr_precond_fsai reads it (host or device arrays; square; the columns of every row strictly increasing; a
+ *   diagonal entry in every row; CVR_ERR_INVALID naming the first offending row); pattern and values of device arrays come to the host once on
+ *   `stream`.  n = 0 is valid: one empty level, an apply enqueues nothing.
+ * Set-up, on the host, O(nnz) per level (cvr_amg_setup_host is this very code and needs no device).  fp64 on the values converted to double, every
+ *   operation rounded on its own (no fused multiply-add), every stored value rounded to T once.  Level 0 is A.  At level l, in this order:
+ *   Smoother diagonal.  a_ii not finite or not > 0: CVR_ERR_STATE, cvr_last_error names the level and the lowest such row, nothing is left
+ *     allocated.  d_i = +0 + |a_i0| + |a_i1| + .. in column order; dinv_i = T(1 / d_i).
+ *   Stopping.  The level is the coarsest when n_l <= coarse_size or max_levels levels exist.
+ *   Strength.  Entry j != i of row i is strong when a_ij != 0 and a_ij * a_ij >= ((strength * strength) * a_ii) * a_jj.
+ *   Aggregation, three passes over the rows in ascending order.  1: if i and all its strong neighbours are free they form the next aggregate (a row
+ *     without strong neighbours becomes a singleton).  2: a free i with a strong neighbour that pass 1 aggregated joins the aggregate of the one
+ *     with the largest |a_ij|, ties to the lowest j; only pass-1 membership counts.  3: a free i forms the next aggregate with its still-free strong
+ *     neighbours.  agg[i] is the aggregate of row i.
+ *   Stall.  With n_(l+1) aggregates, double(n_(l+1)) > 0.8 * double(n_l): the level is the coarsest and its aggregation is dropped.
+ *   Coarse operator.  A_(l+1)(I, J) = +0 + a_ij + .. over i in I ascending, each row's entries in column order, for agg[j] = J; rounded to T once;
+ *     the columns of a row ascending; an entry that sums to zero stays.  The next level reads the rounded values.
+ *   Coarsest level, n <= CVR_AMG_MAX_COARSE (coarse_direct = 1): the explicit inverse W of its dense matrix, read from the lower triangle (+0 where
+ *     the row has no such column).  Right-looking LDL^T in cvr_precond_fsai's order: for k = 0 .. n-1: d_k = S[k][k], not finite or not > 0:
+ *     CVR_ERR_STATE naming the level and k; l_ak = S[a][k] / d_k; S[a][b] = S[a][b] - l_ak * S[b][k] for k < b <= a.  Y = L^-1 by columns: Y = I; for
+ *     k ascending, a > k, c <= k: Y[a][c] = Y[a][c] - l_ak * Y[k][c].  For j <= i: W_ij = W_ji = T(+0 + t_i + .. + t_(n-1)), t_k = (Y[k][i] / d_k) *
+ *     Y[k][j], k ascending.  Otherwise (a stall or max_levels; coarse_direct = 0) the coarsest level is "solved" by 2 * sweeps smoother sweeps.
+ * The object owns, per coarse level, the level's arrays on the device and a handle of its own -- cvr_create + cvr_preprocess from device arrays with
+ *   cvr_default_options on the object's device, so its products are bit for bit those of a caller's handle of the exported level (a directly solved
+ *   coarsest level has no handle) -- and per level the buffers r (n), z (the handle's x_elems values; element n stays 0) and q (yext_elems).  One
+ *   object serves one stream at a time.
+ * Cycle at level l for the right-hand side r (level 0: the caller's), per element in fp64, each operation rounded on its own, each stored value
+ *   rounded to T once; q = A_l z is the level's product through cvr_spmv_device's launch path:
+ *     1. z_i = T(dinv_i * r_i).
+ *     2. sweeps - 1 times:  q = A_l z;  z_i = T(z_i + dinv_i * (r_i - q_i)).
+ *     3. q = A_l z;  r_(l+1)(I) = T(+0 + (r_i - q_i) + ..) over the rows i of I ascending: one kernel, one lane per aggregate, no atomics.
+ *     4. z_(l+1) = the cycle at level l + 1.  The coarsest level: z_i = T(t_0 + t_1 + .. + t_(n-1)), t_j = W_ij * r_j, left to right starting from
+ *        t_0, when coarse_direct; else step 1 and 2 * sweeps - 1 times step 2.
+ *     5. z_i = T(z_i + coarse_scale * z_(l+1)(agg[i])).
+ *     6. sweeps times:  q = A_l z;  z_i = T(z_i + dinv_i * (r_i - q_i)).
+ *   With sweeps = 1 a level above the coarsest costs two products and four element-wise launches.  Level 0 begins with a copy kernel (r_0 = r_dev)
+ *   and ends with one (z_dev = z_0) on the solvers' grid, for every alignment of r_dev and z_dev.  An apply enqueues 2 * sweeps * (levels - 1)
+ *   products, and 2 * sweeps - 1 more when the coarsest level is smoothed.
+ * cvr_precond_apply_device takes this kind: it only enqueues, reads nothing back, forms no dot product, has no kernel that waits on another
+ *   workgroup, and gives the same bits on every call.
+ * cvr_pcg_device / cvr_pcg take this kind: cvr_pcg_device's text holds with this apply in place of z = W r.  The last launch writes z, the partial
+ *   sums of r.z into set 1 as the block-Jacobi apply does and, at the start, p = z; behind a stop it writes nothing; everything before it touches
+ *   only the object's buffers.  So x, iterations, status, residual_norm and b_norm do not depend on check_every.  spmv_count = 1 + P + (1 + P) *
+ *   (steps enqueued), P the products of an apply.
+ * cvr_precond_get_info works for this kind (block_size, nblocks and identity_blocks are 0); cvr_precond_destroy frees the handles and the buffers.
+ * cvr_precond_export, cvr_precond_apply_multi_device, cvr_pcg_multi_device / cvr_pcg_multi, cvr_pbicgstab_device / cvr_pbicgstab and
+ * cvr_pgmres_device / cvr_pgmres decline this kind: CVR_ERR_STATE behind their other checks, cvr_last_error naming "kind 4 (AMG)".  The *_info and
+ * *_export calls of the other kinds return CVR_ERR_INVALID on this kind, and this kind's return it on the others.
+ * Errors of cvr_precond_amg, in this order, before any device work: a null out, h or csr; the options (opt NULL: the defaults; max_levels outside
+ * 1 .. CVR_AMG_MAX_LEVELS, coarse_size outside 1 .. CVR_AMG_MAX_COARSE, sweeps outside 1 .. 4, strength not in [0, 1), coarse_scale not finite or
+ * not > 0, a reserved word not 0); nrows != ncols, nrows < 0, nrows >= 2^31 - 1: CVR_ERR_INVALID; h before cvr_preprocess: CVR_ERR_STATE; h not
+ * square, or its nrows or type not the view's: CVR_ERR_INVALID; the view's checks (host arrays: before any device work): CVR_ERR_INVALID.  Then
+ * CVR_ERR_STATE as above, CVR_ERR_NOMEM: an allocation failed (nothing is left allocated).
+ * cvr_precond_amg_info fills a cvr_amg_info.  cvr_precond_amg_export_level writes host arrays of level `level` (0 .. levels - 1): row_ptr (n + 1),
+ * col_idx and vals (nnz), dinv (n), agg (n; untouched and may be NULL on the coarsest level) and winv (n * n values of T, row-major, symmetric bit
+ * for bit; written for a directly solved coarsest level only and may be NULL otherwise).
+ * cvr_amg_setup_host is the pure-host set-up (host arrays only): it returns a cvr_amg_hierarchy with the same levels byte for byte, read by
+ * cvr_amg_hierarchy_info and cvr_amg_hierarchy_export_level (the arguments of the two calls above) and released by cvr_amg_hierarchy_destroy.  On
+ * CVR_ERR_STATE *bad_level and *bad_row name the level and the row (else -1) and no hierarchy is returned. */
+#define CVR_AMG_MAX_LEVELS 16
+#define CVR_AMG_MAX_COARSE 256
+typedef struct {
+    int32_t max_levels;                        /* 1 .. CVR_AMG_MAX_LEVELS, default 16                                       */
+    int32_t coarse_size;                       /* 1 .. CVR_AMG_MAX_COARSE, default 64: stop coarsening at n_l <= this       */
+    int32_t sweeps;                            /* 1 .. 4, default 1: pre- = post-smoothing sweeps                           */
+    int32_t reserved0;                         /* must be 0                                                                 */
+    double  strength;                          /* 0 <= s < 1, default 0.08                                                  */
+    double  coarse_scale;                      /* finite, > 0, default 1.0: factor on the coarse correction                 */
+    int32_t reserved[8];                       /* must be 0                                                                 */
+} cvr_amg_options;
+typedef struct {
+    int32_t levels;                            /* 1 .. max_levels                                                           */
+    int32_t coarse_direct;                     /* 1: the coarsest level applies its dense inverse; 0: 2 * sweeps sweeps     */
+    int32_t sweeps, is_f32;
+    int32_t max_levels, coarse_size;           /* the options the object was built with ...                                 */
+    double  strength, coarse_scale;
+    double  operator_complexity;               /* the sum of the levels' nnz over level 0's (0 when that is 0)              */
+    int64_t n[CVR_AMG_MAX_LEVELS];             /* rows of level l; entries from `levels` on are 0                           */
+    int64_t nnz[CVR_AMG_MAX_LEVELS];
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_amg_info;
+typedef struct cvr_amg_hierarchy cvr_amg_hierarchy;
+int cvr_amg_default_options(cvr_amg_options *opt);
+int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream);
+int cvr_precond_amg_info(const cvr_precond *p, cvr_amg_info *info);
+int cvr_precond_amg_export_level(const cvr_precond *p, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals, void *dinv, int32_t *agg, void *winv);
+int cvr_amg_setup_host(cvr_amg_hierarchy **out, const cvr_csr_view *csr, const cvr_amg_options *opt, int32_t *bad_level, int64_t *bad_row);
+int cvr_amg_hierarchy_info(const cvr_amg_hierarchy *hier, cvr_amg_info *info);
+int cvr_amg_hierarchy_export_level(const cvr_amg_hierarchy *hier, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals, void *dinv, int32_t *agg, void *winv);
+int cvr_amg_hierarchy_destroy(cvr_amg_hierarchy *hier);
+
 /* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
