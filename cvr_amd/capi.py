@@ -138,6 +138,13 @@ class AmgInfo(C.Structure):
                 ("n", C.c_int64 * AMG_MAX_LEVELS), ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("reserved", C.c_int32 * 8)]
 
 
+class SpGemmInfo(C.Structure):
+    """cvr_spgemm_info_t"""
+    _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("inner", C.c_int64), ("nnz", C.c_int64), ("products", C.c_int64), ("max_row_products", C.c_int64),
+                ("rows_empty", C.c_int64), ("rows_group", C.c_int64), ("rows_block", C.c_int64), ("rows_spill", C.c_int64), ("group_limit", C.c_int64),
+                ("block_limit", C.c_int64), ("is_f32", C.c_int32), ("lanes_per_row", C.c_int32), ("symbolic_s", C.c_double), ("numeric_s", C.c_double)]
+
+
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
 
 
@@ -184,6 +191,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_fsai", "cvr_precond_fsai_info", "cvr_precond_fsai_export", "cvr_fsai_factor_host",
            "cvr_amg_default_options", "cvr_precond_amg", "cvr_precond_amg_info", "cvr_precond_amg_export_level", "cvr_amg_setup_host", "cvr_amg_hierarchy_info",
            "cvr_amg_hierarchy_export_level", "cvr_amg_hierarchy_destroy",
+           "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
@@ -267,6 +275,13 @@ def lib():
         L.cvr_precond_amg_export_level.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         L.cvr_amg_setup_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(AmgOptions), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.cvr_amg_hierarchy_info.argtypes = [C.c_void_p, C.POINTER(AmgInfo)]
+        L.cvr_spgemm_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(CsrView), C.c_int32, C.c_void_p]
+        L.cvr_spgemm_get_info.argtypes = [C.c_void_p, C.POINTER(SpGemmInfo)]
+        L.cvr_spgemm_csr_device.argtypes = [C.c_void_p, C.POINTER(CsrView)]
+        L.cvr_spgemm_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_spgemm_numeric_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_spgemm_destroy.argtypes = [C.c_void_p]
+        L.cvr_spgemm_host.argtypes = [C.POINTER(CsrView), C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.cvr_amg_hierarchy_export_level.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         L.cvr_amg_hierarchy_destroy.argtypes = [C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -461,6 +476,120 @@ def amg_setup_host(rp, ci, vals, **options):
         return info, [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
     finally:
         L.cvr_amg_hierarchy_destroy(h)
+
+
+def _host_csr(csr):
+    """(nrows, ncols, rp, ci, va, f32) of a (nrows, ncols, row_ptr, col_idx, vals) tuple, the arrays contiguous and of the ABI's types"""
+    nrows, ncols, rp, ci, va = csr
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    f32 = np.asarray(va).dtype == np.float32
+    va = np.ascontiguousarray(va, dtype=np.float32 if f32 else np.float64)
+    if len(rp) != nrows + 1:
+        raise ValueError("row_ptr must have nrows + 1 entries")
+    if nrows > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    return int(nrows), int(ncols), rp, ci, va, f32
+
+
+def spgemm_host(a_csr, b_csr):
+    """cvr_spgemm_host: (row_ptr, col_idx, vals) of C = A B for two (nrows, ncols, row_ptr, col_idx, vals) tuples of host arrays of one dtype (float32
+    or else float64) -- what SpGemm computes on the device, in host code, by the two calls of the ABI.  B's rows must be strictly ascending in
+    column: a violation raises CvrError (ERR_INVALID) with .bad_row.  Host only."""
+    m, k, arp, aci, ava, af32 = _host_csr(a_csr)
+    k2, n, brp, bci, bva, bf32 = _host_csr(b_csr)
+    va_ = CsrView(m, k, arp.ctypes.data, aci.ctypes.data, ava.ctypes.data, int(af32), 0)
+    vb_ = CsrView(k2, n, brp.ctypes.data, bci.ctypes.data, bva.ctypes.data, int(bf32), 0)
+    crp, bad = np.zeros(m + 1, dtype=np.int64), C.c_int64(-1)
+
+    def call(ci_ptr, va_ptr):
+        rc = lib().cvr_spgemm_host(C.byref(va_), C.byref(vb_), crp.ctypes.data, ci_ptr, va_ptr, C.byref(bad))
+        if rc:
+            e = CvrError(rc, "cvr_spgemm_host")
+            e.bad_row = None if bad.value < 0 else int(bad.value)
+            raise e
+    call(None, None)
+    nnz = int(crp[m])
+    cci, cva = np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=np.float32 if af32 else np.float64)
+    call(cci.ctypes.data, cva.ctypes.data)
+    return crp, cci[:nnz], cva[:nnz]
+
+
+class SpGemm:
+    """cvr_spgemm: C = A B in CSR on one GPU, bit for bit tests/spgemm_model.py.  The object owns C and copies of the two patterns."""
+
+    def __init__(self):
+        self._g = C.c_void_p()
+
+    @classmethod
+    def create(cls, a_csr, b_csr, device=0, stream=None):
+        """from two (nrows, ncols, row_ptr, col_idx, vals) tuples of host arrays of one dtype; A may be unsorted with duplicates, B's rows must
+        be strictly ascending in column"""
+        m, k, arp, aci, ava, af32 = _host_csr(a_csr)
+        k2, n, brp, bci, bva, bf32 = _host_csr(b_csr)
+        return cls._from_views(CsrView(m, k, arp.ctypes.data, aci.ctypes.data, ava.ctypes.data, int(af32), 0),
+                               CsrView(k2, n, brp.ctypes.data, bci.ctypes.data, bva.ctypes.data, int(bf32), 0), device, stream)
+
+    @classmethod
+    def from_device(cls, a_dev, b_dev, is_f32=False, device=0, stream=None):
+        """from two (nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev) tuples of raw pointers into the memory of `device` (as CvrMatrix.from_device)"""
+        va_ = CsrView(a_dev[0], a_dev[1], a_dev[2], a_dev[3], a_dev[4], int(bool(is_f32)), 1)
+        vb_ = CsrView(b_dev[0], b_dev[1], b_dev[2], b_dev[3], b_dev[4], int(bool(is_f32)), 1)
+        return cls._from_views(va_, vb_, device, stream)
+
+    @classmethod
+    def _from_views(cls, va_, vb_, device, stream):
+        self = cls()
+        rc = lib().cvr_spgemm_create(C.byref(self._g), C.byref(va_), C.byref(vb_), device, stream)
+        if rc:
+            self._g = C.c_void_p()
+            raise CvrError(rc, "cvr_spgemm_create")
+        self.dtype = np.float32 if self.info().is_f32 else np.float64
+        return self
+
+    def info(self):
+        """cvr_spgemm_get_info: a SpGemmInfo"""
+        info = SpGemmInfo()
+        rc = lib().cvr_spgemm_get_info(self._g, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_spgemm_get_info")
+        return info
+
+    def csr_device(self):
+        """cvr_spgemm_csr_device: (nrows, ncols, row_ptr_dev, col_idx_dev, vals_dev) of C, owned by this object: the arguments of
+        CvrMatrix.from_device and of the *_from_device constructors"""
+        v = CsrView()
+        rc = lib().cvr_spgemm_csr_device(self._g, C.byref(v))
+        if rc:
+            raise CvrError(rc, "cvr_spgemm_csr_device")
+        return v.nrows, v.ncols, v.row_ptr, v.col_idx, v.vals
+
+    def export(self):
+        """cvr_spgemm_export: (row_ptr, col_idx, vals) of C as host arrays"""
+        i = self.info()
+        rp, ci, va = np.zeros(i.nrows + 1, dtype=np.int64), np.zeros(i.nnz, dtype=np.int32), np.zeros(i.nnz, dtype=self.dtype)
+        rc = lib().cvr_spgemm_export(self._g, rp.ctypes.data, ci.ctypes.data if i.nnz else None, va.ctypes.data if i.nnz else None)
+        if rc:
+            raise CvrError(rc, "cvr_spgemm_export")
+        return rp, ci, va
+
+    def numeric(self, a_vals_ptr, b_vals_ptr, stream=None):
+        """cvr_spgemm_numeric_device: the numeric step again, asynchronously, with new device value arrays of A and B (same patterns, indexed like
+        the arrays at creation), into the existing C"""
+        rc = lib().cvr_spgemm_numeric_device(self._g, a_vals_ptr, b_vals_ptr, stream)
+        if rc:
+            raise CvrError(rc, "cvr_spgemm_numeric_device")
+
+    def close(self):
+        if getattr(self, "_g", None) and self._g.value:
+            lib().cvr_spgemm_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
 
 
 def last_error():

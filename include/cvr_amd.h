@@ -1087,6 +1087,54 @@ int cvr_minres_device(cvr_handle *h, const void *b_dev, void *x_dev, double shif
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg; opt->minv_dev stays a device pointer */
 int cvr_minres(cvr_handle *h, const void *b_host, void *x_host, double shift, const cvr_cg_options *opt, cvr_cg_result *res, cvr_minres_info *info);
 
+/* ---- the sparse matrix-matrix product C = A B in CSR, on the device, with reproducible bits -----------------
+ * A (m x k) and B (k x n) are cvr_csr_views of the same is_f32, both of host arrays or both of arrays in the memory of `device`; T = float or double.
+ * A may have unsorted rows and duplicate entries.  B's rows must be strictly ascending in column (sorted, no duplicates): checked on the device, a
+ *   violation is CVR_ERR_INVALID and cvr_last_error names the lowest offending row ("B row <r>").  A result satisfies this, so products chain.
+ * C is a CSR with int64 row pointers, row_ptr[0] = 0, every row strictly ascending in column.  Entry (i, j) exists iff some position p of A's row i
+ *   and some position q of B's row col_A[p] have col_B[q] = j: the pattern is structural, an entry whose terms cancel to 0.0 stays.  Its value is
+ *   acc = +0; acc = T(acc + T(a[p] * b[q])) over those (p, q) in ascending p (q is unique for each p): the product and the sum each rounded once in
+ *   T, no fused multiply-add.  The bits are the same on every call, for host and device arrays, for every alignment of the input arrays and for
+ *   every launch plan; tests/spgemm_model.py states them in numpy and cvr_spgemm_host computes them in host code.
+ * cvr_spgemm_create checks the views, copies the two patterns (the object keeps nothing of the caller's) and runs, as one submission on `stream`:
+ *   the bound pass (products[i] = the sum over A's row i of nnz(B row col_A[p]), int64; its total and maximum), the rows binned into classes by
+ *   products[i] in row order -- empty; group (products < group_limit): lanes_per_row lanes of a wavefront and a table in LDS per row; block
+ *   (products < block_limit): a workgroup and one LDS table per row; spill: a workgroup and a table in a global arena --, a symbolic kernel per LDS
+ *   class that counts each row's distinct columns, the scan to row_ptr, ONE read-back (nnz(C) with the statistics), the allocation of C and a
+ *   numeric kernel per class that writes each row out sorted.  Only when rows spill does a second read-back follow: the arena is allocated behind the
+ *   first one, sized by the largest row it reported (a table of twice that row's possible columns, as many tables as fit 256 MiB, at least one;
+ *   CVR_ERR_NOMEM when one table does not fit), then the spill rows are counted and row_ptr is scanned again.  A product without spill rows allocates
+ *   no arena.  It returns with the stream idle.  CVR_DEBUG=spgemm_limits=<group>:<block>, read by every
+ *   cvr_spgemm_create, lowers the two limits: it changes the plan and never a bit.  The row pointers and columns of device arrays are checked as
+ *   cvr_create checks them, with that call's small read-backs in front of the submission.
+ * cvr_spgemm_get_info fills a cvr_spgemm_info_t.  cvr_spgemm_csr_device fills a view of C (arrays owned by the object, arrays_on_device = 1) that
+ *   goes straight into cvr_create or a cvr_precond_* constructor.  cvr_spgemm_export copies C to host arrays (row_ptr: m + 1, col_idx and vals: nnz;
+ *   each pointer may be NULL); it waits for the device first.
+ * cvr_spgemm_numeric_device runs the numeric step alone, into the existing C, with new value arrays of A and B in device memory, indexed like the
+ *   views' vals at creation (same patterns): it only enqueues on `stream`, and gives the bits a fresh create with those values would give.
+ * cvr_spgemm_host is the pure-host twin (host arrays only), in two calls: with c_col_idx == NULL and c_vals == NULL it fills c_row_ptr (m + 1)
+ *   alone, with both it fills all three.  The same checks, the same errors, the same bits; *bad_row = the offending row of B, else -1.
+ * Errors.  CVR_ERR_INVALID: a null argument; the views' is_f32 differ; a->ncols != b->nrows; one view of host and one of device arrays; a malformed
+ *   CSR (cvr_create's checks of a view, without its limit that a vector of ncols values fit 4 GiB: the product has no x); B not strictly ascending; b->ncols >= 2^31 - 1; a null value array to cvr_spgemm_numeric_device.
+ *   CVR_ERR_NO_DEVICE, CVR_ERR_NOMEM (nothing is left allocated) and CVR_ERR_HIP as elsewhere.  m = 0, k = 0, n = 0 and nnz = 0 are valid: an empty
+ *   C, nothing launched past the bound pass.  cvr_spgemm_destroy(NULL) is CVR_OK. */
+typedef struct cvr_spgemm cvr_spgemm;
+typedef struct {
+    int64_t nrows, ncols, inner, nnz;          /* m, n, k, nnz(C)                                                           */
+    int64_t products, max_row_products;        /* the bound pass: the sum and the maximum of products[i]                    */
+    int64_t rows_empty, rows_group, rows_block, rows_spill;
+    int64_t group_limit, block_limit;          /* the limits in force for this object (32 and 4096 unless lowered)          */
+    int32_t is_f32, lanes_per_row;             /* the lanes of a group row (8)                                              */
+    double  symbolic_s, numeric_s;             /* host seconds of cvr_spgemm_create up to the read-back, and behind it      */
+} cvr_spgemm_info_t;
+int cvr_spgemm_create(cvr_spgemm **out, const cvr_csr_view *a, const cvr_csr_view *b, int32_t device, void *stream);
+int cvr_spgemm_get_info(const cvr_spgemm *g, cvr_spgemm_info_t *info);
+int cvr_spgemm_csr_device(const cvr_spgemm *g, cvr_csr_view *c);
+int cvr_spgemm_export(const cvr_spgemm *g, int64_t *row_ptr, int32_t *col_idx, void *vals);
+int cvr_spgemm_numeric_device(cvr_spgemm *g, const void *a_vals_dev, const void *b_vals_dev, void *stream);
+int cvr_spgemm_destroy(cvr_spgemm *g);
+int cvr_spgemm_host(const cvr_csr_view *a, const cvr_csr_view *b, int64_t *c_row_ptr, int32_t *c_col_idx, void *c_vals, int64_t *bad_row);
+
 /* ---- a few extreme eigenpairs of a symmetric A on the device: thick-restart Lanczos --------------------------
  * cvr_eigsh_device / cvr_eigsh find the nev algebraically largest or smallest eigenvalues of a symmetric A and their eigenvectors: the Lanczos process
  * with full reorthogonalisation (classical Gram-Schmidt applied twice, GMRES's kernels) and the thick restart of Wu and Simon (SIAM J. Matrix Anal. Appl.
