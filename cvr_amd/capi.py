@@ -138,6 +138,12 @@ class AmgInfo(C.Structure):
                 ("n", C.c_int64 * AMG_MAX_LEVELS), ("nnz", C.c_int64 * AMG_MAX_LEVELS), ("reserved", C.c_int32 * 8)]
 
 
+class AmgSmoothedInfo(C.Structure):
+    """cvr_amg_smoothed_info"""
+    _fields_ = [("smoothed", C.c_int32), ("products_per_apply", C.c_int32), ("omega", C.c_double), ("p_nnz", C.c_int64 * AMG_MAX_LEVELS),
+                ("reserved", C.c_int32 * 8)]
+
+
 class SpGemmInfo(C.Structure):
     """cvr_spgemm_info_t"""
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("inner", C.c_int64), ("nnz", C.c_int64), ("products", C.c_int64), ("max_row_products", C.c_int64),
@@ -191,6 +197,8 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_fsai", "cvr_precond_fsai_info", "cvr_precond_fsai_export", "cvr_fsai_factor_host",
            "cvr_amg_default_options", "cvr_precond_amg", "cvr_precond_amg_info", "cvr_precond_amg_export_level", "cvr_amg_setup_host", "cvr_amg_hierarchy_info",
            "cvr_amg_hierarchy_export_level", "cvr_amg_hierarchy_destroy",
+           "cvr_precond_amg_smoothed", "cvr_amg_smoothed_setup_host", "cvr_precond_amg_smoothed_info", "cvr_amg_hierarchy_smoothed_info",
+           "cvr_precond_amg_export_prolongator", "cvr_amg_hierarchy_export_prolongator",
            "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
@@ -284,6 +292,12 @@ def lib():
         L.cvr_spgemm_host.argtypes = [C.POINTER(CsrView), C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.cvr_amg_hierarchy_export_level.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         L.cvr_amg_hierarchy_destroy.argtypes = [C.c_void_p]
+        L.cvr_precond_amg_smoothed.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_double, C.c_void_p]
+        L.cvr_amg_smoothed_setup_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.cvr_precond_amg_smoothed_info.argtypes = [C.c_void_p, C.POINTER(AmgSmoothedInfo)]
+        L.cvr_amg_hierarchy_smoothed_info.argtypes = [C.c_void_p, C.POINTER(AmgSmoothedInfo)]
+        L.cvr_precond_amg_export_prolongator.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_amg_hierarchy_export_prolongator.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -474,6 +488,55 @@ def amg_setup_host(rp, ci, vals, **options):
         if rc:
             raise CvrError(rc, "cvr_amg_hierarchy_info")
         return info, [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
+    finally:
+        L.cvr_amg_hierarchy_destroy(h)
+
+
+class AmgProlongator:
+    """one exported prolongator P_l: n x nc in CSR (row_ptr, col_idx, vals)"""
+
+    def __init__(self, n, nc, rp, ci, va):
+        self.n, self.nc, self.rp, self.ci, self.va = n, nc, rp, ci, va
+
+
+def _amg_export_prolongator(call, obj, info, sinfo, level, dtype):
+    """P of one level through cvr_precond_amg_export_prolongator or cvr_amg_hierarchy_export_prolongator; the sizes from the two infos"""
+    n, nnz = int(info.n[level]), int(sinfo.p_nnz[level])
+    rp, ci, va = np.zeros(n + 1, dtype=np.int64), np.zeros(nnz, dtype=np.int32), np.zeros(nnz, dtype=dtype)
+    rc = call(obj, level, rp.ctypes.data, ci.ctypes.data if nnz else None, va.ctypes.data if nnz else None)
+    if rc:
+        raise CvrError(rc, "cvr_amg export_prolongator")
+    return AmgProlongator(n, int(info.n[level + 1]), rp, ci, va)
+
+
+def amg_smoothed_setup_host(rp, ci, vals, omega=0.0, **options):
+    """cvr_amg_smoothed_setup_host: (AmgInfo, AmgSmoothedInfo, [AmgLevel, ...], [AmgProlongator, ...]) of the smoothed-aggregation hierarchy of a
+    square CSR matrix with sorted rows and a diagonal in every row -- what Precond.amg_smoothed builds, in host code.  omega = 0.0: the default 4/3.
+    Errors as amg_setup_host.  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    f32 = np.asarray(vals).dtype == np.float32
+    dtype = np.float32 if f32 else np.float64
+    va = np.ascontiguousarray(vals, dtype=dtype)
+    n = len(rp) - 1
+    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    L = lib()
+    opt = amg_options(**options)
+    h, bad_level, bad_row = C.c_void_p(), C.c_int32(-1), C.c_int64(-1)
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
+    rc = L.cvr_amg_smoothed_setup_host(C.byref(h), C.byref(view), C.byref(opt), float(omega), C.byref(bad_level), C.byref(bad_row))
+    if rc:
+        e = CvrError(rc, "cvr_amg_smoothed_setup_host")
+        e.bad = (bad_level.value, bad_row.value) if bad_level.value >= 0 else None
+        raise e
+    try:
+        info, sinfo = AmgInfo(), AmgSmoothedInfo()
+        rc = L.cvr_amg_hierarchy_info(h, C.byref(info)) or L.cvr_amg_hierarchy_smoothed_info(h, C.byref(sinfo))
+        if rc:
+            raise CvrError(rc, "cvr_amg_hierarchy_info")
+        levels = [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
+        return info, sinfo, levels, [_amg_export_prolongator(L.cvr_amg_hierarchy_export_prolongator, h, info, sinfo, l, dtype) for l in range(info.levels - 1)]
     finally:
         L.cvr_amg_hierarchy_destroy(h)
 
@@ -972,13 +1035,46 @@ class Precond:
         return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options)
 
     @classmethod
-    def _amg_from_view(cls, matrix, view, options):
+    def amg_smoothed(cls, matrix, rp, ci, vals, omega=0.0, **options):
+        """cvr_precond_amg_smoothed: Precond.amg with the smoothed prolongator P = (I - omega D^-1 A) T and the Galerkin coarse operators P^T A P,
+        built on the device by the SpGEMM; omega = 0.0: the default 4/3, else 0 < omega < 2.  The same kind of object (kind 4) for the same calls."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options, omega)
+
+    @classmethod
+    def amg_smoothed_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, omega=0.0, **options):
+        """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
+        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega)
+
+    def amg_smoothed_info(self):
+        """cvr_precond_amg_smoothed_info: an AmgSmoothedInfo (smoothed, omega, products_per_apply, p_nnz of every level); all zero of a plain object"""
+        info = AmgSmoothedInfo()
+        rc = lib().cvr_precond_amg_smoothed_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_amg_smoothed_info")
+        return info
+
+    def amg_export_prolongator(self, level):
+        """cvr_precond_amg_export_prolongator: an AmgProlongator (row_ptr, col_idx, vals of P_l, n x nc) of level 0 .. levels - 2"""
+        return _amg_export_prolongator(lib().cvr_precond_amg_export_prolongator, self._p, self.amg_info(), self.amg_smoothed_info(), level, self.dtype)
+
+    @classmethod
+    def _amg_from_view(cls, matrix, view, options, omega=None):
         self = cls()
         opt = amg_options(**options)
-        rc = lib().cvr_precond_amg(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), None)
+        if omega is None:
+            rc = lib().cvr_precond_amg(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), None)
+        else:
+            rc = lib().cvr_precond_amg_smoothed(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), float(omega), None)
         if rc:
             self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_amg")
+            raise CvrError(rc, "cvr_precond_amg" if omega is None else "cvr_precond_amg_smoothed")
         lib().cvr_precond_get_info(self._p, C.byref(self.info))
         self.dtype = np.float32 if self.info.is_f32 else np.float64
         self._matrix = matrix

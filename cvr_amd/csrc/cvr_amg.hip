@@ -12,6 +12,10 @@
 //     amg_smooth_kernel] x sweeps | amg_out_kernel (z = z_0), or inside cvr_pcg_device amg_rz_kernel in its place (z = z_0 with the partial sums of
 //     r . z and, at the start, p = z; nothing behind a stop).  The level kernels take a thread per element on a grid cut to the level's size; the
 //     first and the last run on the solvers' grid.
+// The smoothed kind (cvr_precond_amg_smoothed: the same object with Hierarchy::smoothed set) builds every level on the device inside the host
+// set-up's loop (SmoothedBuild: amg_tentative_kernel, the device SpGEMM, amg_prolongator_kernel, transpose_csr, two more products), owns a handle of
+// P_l and one of R_l per level and moves between levels by products: amg_residual_kernel and R_l's product in place of amg_restrict_kernel, P_l's
+// product and amg_correct_kernel in place of amg_prolong_kernel.  Per level two more buffers: t (R_l's input, element n stays 0) and e (P_l's output).
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
@@ -30,6 +34,8 @@ struct AmgLevel {
     bool        own = false;
     void       *d_dinv = nullptr, *d_agg = nullptr, *d_mrp = nullptr, *d_mem = nullptr;
     void       *d_r = nullptr, *d_z = nullptr, *d_q = nullptr;
+    cvr_handle *hp = nullptr, *hr = nullptr;          // the smoothed kind above the coarsest level: the object's handles of P_l and R_l ...
+    void       *d_t = nullptr, *d_e = nullptr;        // ... R_l's input and P_l's output
 };
 
 struct Amg {
@@ -127,6 +133,49 @@ template <typename T>
 __global__ __launch_bounds__(kThreads) void amg_prolong_kernel(const int32_t *__restrict__ agg, const T *__restrict__ zc, T *__restrict__ z, long long n, double scale)
 {
     CVR_AMG_ELEMENTS(i, n) z[i] = (T)((double)z[i] + scale * (double)zc[agg[i]]);
+}
+
+// ---- the smoothed kind
+// behind q = A z: t_i = T(r_i - q_i), the input of R's product
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_residual_kernel(const T *__restrict__ r, const T *__restrict__ q, T *__restrict__ t, long long n)
+{
+    CVR_AMG_ELEMENTS(i, n) t[i] = (T)((double)r[i] - (double)q[i]);
+}
+
+// behind e = P zc: z_i = T(z_i + scale * e_i)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_correct_kernel(const T *__restrict__ e, T *__restrict__ z, long long n, double scale)
+{
+    CVR_AMG_ELEMENTS(i, n) z[i] = (T)((double)z[i] + scale * (double)e[i]);
+}
+
+// the tentative prolongator as a CSR: row_ptr = 0 .. n, col_idx = agg, vals = 1
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_tentative_kernel(const int32_t *__restrict__ agg, int64_t *__restrict__ rp, int32_t *__restrict__ ci, T *__restrict__ va, long long n)
+{
+    CVR_AMG_ELEMENTS(i, n + 1) {
+        rp[i] = i;
+        if (i < n) {
+            ci[i] = agg[i];
+            va[i] = T(1);
+        }
+    }
+}
+
+// P on the pattern of G = A T, a thread per row: w = omega * dinv_i; p_ij = T([j == agg_i] - w * g_ij)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void amg_prolongator_kernel(const int64_t *__restrict__ rp, const int32_t *__restrict__ ci, const T *__restrict__ g, const int32_t *__restrict__ agg,
+                                                                   const T *__restrict__ dinv, double omega, T *__restrict__ p, long long n)
+{
+    CVR_AMG_ELEMENTS(i, n) {
+        const double w = omega * (double)dinv[i];
+        const int    own = agg[i];
+        for (long long q = rp[i]; q < rp[i + 1]; q++) {
+            const double wg = w * (double)g[q];
+            p[q] = (T)((ci[q] == own ? 1.0 : 0.0) - wg);
+        }
+    }
 }
 
 // the directly solved coarsest level, n <= CVR_AMG_MAX_COARSE: z_i = T(t_0 + t_1 + ..), t_j = W_ij * r_j; W is symmetric bit for bit, so thread i
@@ -270,25 +319,202 @@ int make_handle(cvr_handle **out, const amg::Level &l, int is_f32, int device, S
     return cvr_preprocess(*out, 0, nullptr);
 }
 
-int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, hipStream_t st)
+// a handle of the object's own: cvr_create + cvr_preprocess of a view of device arrays with the default options on the object's device
+int handle_of(cvr_handle **out, const cvr_csr_view &v, int device)
 {
-    Amg *a = p->amg;
+    cvr_options opt;
+    cvr_default_options(&opt);
+    opt.device = device;
+    if (const int rc = cvr_create(out, &v, &opt)) {
+        *out = nullptr;
+        return rc;
+    }
+    return cvr_preprocess(*out, 0, nullptr);
+}
+
+// The smoothed kind's levels on the device, one coarsening step per call from inside amg::setup's loop (the aggregation before it and the next
+// level's diagonal behind it are the host's).  `cur` is the level's CSR in device memory: level 0 uploaded from the host's copy, a coarse level the
+// product that made it, kept until the next step has read it.
+struct SmoothedBuild {
+    cvr_precond *p = nullptr;
+    hipStream_t  st = nullptr;
+    double       omega = 0;
+    cvr_spgemm  *cur_owner = nullptr;
+    Scratch      cur_bufs;
+    cvr_csr_view cur{};
+    SmoothedBuild() = default;
+    SmoothedBuild(const SmoothedBuild &) = delete;
+    SmoothedBuild &operator=(const SmoothedBuild &) = delete;
+    ~SmoothedBuild()
+    {
+        if (cur_owner) (void)cvr_spgemm_destroy(cur_owner);
+    }
+
+    struct Product {          // a cvr_spgemm that lives for one step
+        cvr_spgemm *g = nullptr;
+        Product() = default;
+        Product(const Product &) = delete;
+        Product &operator=(const Product &) = delete;
+        ~Product()
+        {
+            if (g) (void)cvr_spgemm_destroy(g);
+        }
+    };
+    struct Transposed {
+        TransposedCsr t;
+        Transposed() = default;
+        Transposed(const Transposed &) = delete;
+        Transposed &operator=(const Transposed &) = delete;
+        ~Transposed() { t.release(); }
+    };
+
+    template <typename T>
+    int step(amg::Level &f, amg::Level &c, int32_t level)
+    {
+        Amg      *a = p->amg;
+        AmgLevel &dl = a->lv[(size_t)level];          // (sized for CVR_AMG_MAX_LEVELS before the set-up)
+        const int is_f32 = p->is_f32;
+        if (level == 0) {
+            void *d_rp = nullptr, *d_ci = nullptr, *d_va = nullptr;
+            if (const int rc = upload(&d_rp, f.rp.data(), sizeof(int64_t) * f.rp.size(), "level 0's row_ptr")) return rc;
+            cur_bufs.bufs.push_back(d_rp);
+            if (const int rc = upload(&d_ci, f.ci.data(), sizeof(int32_t) * f.ci.size(), "level 0's col_idx")) return rc;
+            cur_bufs.bufs.push_back(d_ci);
+            if (const int rc = upload(&d_va, f.va.data(), f.va.size(), "level 0's values")) return rc;
+            cur_bufs.bufs.push_back(d_va);
+            cur = cvr_csr_view{};
+            cur.nrows = cur.ncols = f.n;
+            cur.row_ptr = static_cast<const int64_t *>(d_rp);
+            cur.col_idx = static_cast<const int32_t *>(d_ci);
+            cur.vals = d_va;
+            cur.is_f32 = is_f32;
+            cur.arrays_on_device = 1;
+        } else {
+            dl.own = true;
+            if (const int rc = handle_of(&dl.h, cur, p->device)) return rc;
+        }
+        const long long n = f.n;
+        if (const int rc = upload(&dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
+        if (const int rc = upload(&dl.d_agg, f.agg.data(), sizeof(int32_t) * f.agg.size(), "agg")) return rc;
+        // 1. T
+        Scratch s;
+        void   *d_trp = nullptr, *d_tci = nullptr, *d_tva = nullptr, *d_pva = nullptr;
+        if (const int rc = device_alloc(&d_trp, sizeof(int64_t) * (size_t)(n + 1), "the tentative prolongator")) return rc;
+        s.bufs.push_back(d_trp);
+        if (const int rc = device_alloc(&d_tci, sizeof(int32_t) * (size_t)n, "the tentative prolongator")) return rc;
+        s.bufs.push_back(d_tci);
+        if (const int rc = device_alloc(&d_tva, sizeof(T) * (size_t)n, "the tentative prolongator")) return rc;
+        s.bufs.push_back(d_tva);
+        launch_level(amg_tentative_kernel<T>, n + 1, st, static_cast<const int32_t *>(dl.d_agg), static_cast<int64_t *>(d_trp), static_cast<int32_t *>(d_tci), static_cast<T *>(d_tva), n);
+        HIP_TRY(hipGetLastError());
+        cvr_csr_view tv{};
+        tv.nrows = f.n;
+        tv.ncols = f.nc;
+        tv.row_ptr = static_cast<const int64_t *>(d_trp);
+        tv.col_idx = static_cast<const int32_t *>(d_tci);
+        tv.vals = d_tva;
+        tv.is_f32 = is_f32;
+        tv.arrays_on_device = 1;
+        // 2. G = A T (cvr_spgemm_create orders itself behind `st` and returns with it idle)
+        Product      G, AP, AC;
+        cvr_csr_view gv{}, apv{}, acv{};
+        if (const int rc = cvr_spgemm_create(&G.g, &cur, &tv, p->device, st)) return rc;
+        if (const int rc = cvr_spgemm_csr_device(G.g, &gv)) return rc;
+        cvr_spgemm_info_t gi;
+        if (const int rc = cvr_spgemm_get_info(G.g, &gi)) return rc;
+        const size_t pnnz = (size_t)gi.nnz;
+        // 3. P on G's pattern
+        if (const int rc = device_alloc(&d_pva, sizeof(T) * pnnz, "the prolongator's values")) return rc;
+        s.bufs.push_back(d_pva);
+        launch_level(amg_prolongator_kernel<T>, n, st, gv.row_ptr, gv.col_idx, static_cast<const T *>(gv.vals), static_cast<const int32_t *>(dl.d_agg), static_cast<const T *>(dl.d_dinv), omega,
+                     static_cast<T *>(d_pva), n);
+        HIP_TRY(hipGetLastError());
+        cvr_csr_view pv = gv;
+        pv.vals = d_pva;
+        // 4. R = P^T (synchronises st)
+        Transposed R;
+        if (const int rc = transpose_csr(pv, 0, (int64_t)pnnz, false, st, &R.t)) return rc;
+        cvr_csr_view rv{};
+        rv.nrows = R.t.nrows;
+        rv.ncols = R.t.ncols;
+        rv.row_ptr = R.t.rp;
+        rv.col_idx = R.t.ci;
+        rv.vals = R.t.va;
+        rv.is_f32 = is_f32;
+        rv.arrays_on_device = 1;
+        // 5. A_c = R (A P)
+        if (const int rc = cvr_spgemm_create(&AP.g, &cur, &pv, p->device, st)) return rc;
+        if (const int rc = cvr_spgemm_csr_device(AP.g, &apv)) return rc;
+        if (const int rc = cvr_spgemm_create(&AC.g, &rv, &apv, p->device, st)) return rc;
+        if (const int rc = cvr_spgemm_csr_device(AC.g, &acv)) return rc;
+        cvr_spgemm_info_t ci;
+        if (const int rc = cvr_spgemm_get_info(AC.g, &ci)) return rc;
+        // the host's copies: P for the export, A_c for the next level's aggregation and the export
+        f.prp.assign((size_t)n + 1, 0);
+        f.pci.assign(pnnz, 0);
+        f.pva.assign(sizeof(T) * pnnz, 0);
+        HIP_TRY(hipMemcpy(f.prp.data(), gv.row_ptr, sizeof(int64_t) * f.prp.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(f.pci.data(), gv.col_idx, sizeof(int32_t) * pnnz, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(f.pva.data(), d_pva, sizeof(T) * pnnz, hipMemcpyDeviceToHost));
+        c.n = f.nc;
+        c.nnz = ci.nnz;
+        c.rp.assign((size_t)c.n + 1, 0);
+        c.ci.assign((size_t)c.nnz, 0);
+        c.va.assign(sizeof(T) * (size_t)c.nnz, 0);
+        if (const int rc = cvr_spgemm_export(AC.g, c.rp.data(), c.ci.data(), c.va.data())) return rc;
+        // the two transfer handles, from the device arrays
+        if (const int rc = handle_of(&dl.hp, pv, p->device)) return rc;
+        if (const int rc = handle_of(&dl.hr, rv, p->device)) return rc;
+        HIP_TRY(hipDeviceSynchronize());          // (the handles' copies are complete before the step's arrays go)
+        if (cur_owner) (void)cvr_spgemm_destroy(cur_owner);
+        cur_owner = AC.g;
+        AC.g = nullptr;
+        Scratch().bufs.swap(cur_bufs.bufs);          // (level 0's upload goes with the temporary)
+        cur = acv;
+        return CVR_OK;
+    }
+};
+
+size_t x_bytes_of(const cvr_handle *h) { return h->vsz * (size_t)std::max<int64_t>(h->info.x_elems, h->info.ncols + 1); }
+
+int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, bool smoothed, double omega, hipStream_t st)
+{
+    Amg          *a = p->amg;
+    const char   *entry = smoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg";
+    SmoothedBuild sb;
     {
         HostCsr hc;
         if (const int rc = stage_host(csr, hc, st)) return rc;
         int32_t bad_level = -1;
         int64_t bad_row = -1;
-        if (const int rc = amg::setup(a->H, p->n, hc.rp, hc.ci, hc.va, p->is_f32, opt, "cvr_precond_amg", &bad_level, &bad_row)) return rc;
+        if (smoothed) {
+            try {
+                a->lv.resize(CVR_AMG_MAX_LEVELS);
+            } catch (const std::bad_alloc &) {
+                return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
+            }
+            sb.p = p;
+            sb.st = st;
+            sb.omega = omega;
+            const amg::Coarsen coarsen = [&](amg::Level &f, amg::Level &c, int32_t level) {
+                return p->is_f32 ? sb.step<float>(f, c, level) : sb.step<double>(f, c, level);
+            };
+            if (const int rc = amg::setup(a->H, p->n, hc.rp, hc.ci, hc.va, p->is_f32, opt, entry, &bad_level, &bad_row, &coarsen)) return rc;
+            a->H.smoothed = 1;
+            a->H.omega = omega;
+        } else if (const int rc = amg::setup(a->H, p->n, hc.rp, hc.ci, hc.va, p->is_f32, opt, entry, &bad_level, &bad_row)) return rc;
     }
     const amg::Hierarchy &H = a->H;
     const size_t          vsz = p->is_f32 ? 4 : 8, L = H.lv.size();
-    const int             sweeps = H.opt.sweeps;
-    a->products = 2 * sweeps * ((int)L - 1) + (H.coarse_direct ? 0 : 2 * sweeps - 1);
-    if (p->n == 0) return CVR_OK;
+    a->products = amg::products_per_apply(H);
+    if (p->n == 0) {
+        a->lv.clear();
+        return CVR_OK;
+    }
     try {
         a->lv.resize(L);
     } catch (const std::bad_alloc &) {
-        return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory");
+        return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
     }
     Scratch s;
     for (size_t l = 0; l < L; l++) {
@@ -298,9 +524,30 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
         dl.n = hl.n;
         dl.nc = hl.nc;
         if (l == 0) dl.h = h;
-        else if (!(last && H.coarse_direct)) {
+        else if (smoothed) {
+            if (last && !H.coarse_direct) {          // (the levels above it got theirs in their coarsening step)
+                dl.own = true;
+                if (const int rc = handle_of(&dl.h, sb.cur, p->device)) return rc;
+            }
+        } else if (!(last && H.coarse_direct)) {
             dl.own = true;
             if (const int rc = make_handle(&dl.h, hl, p->is_f32, p->device, s)) return rc;
+        }
+        if (smoothed) {
+            if (last)
+                if (const int rc = upload(&dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
+            // r is R_(l-1)'s output, z is P_(l-1)'s input beside A_l's, t is R_l's input, e is P_l's output; zeroed: the pad slots stay 0
+            const AmgLevel *up = l > 0 ? &a->lv[l - 1] : nullptr;
+            size_t          rb = vsz * (size_t)std::max<int64_t>(hl.n, 1), zb = dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1);
+            if (up) rb = std::max(rb, y_ext_bytes(up->hr)), zb = std::max(zb, x_bytes_of(up->hp));
+            if (const int rc = zeroed(&dl.d_r, rb, "r")) return rc;
+            if (const int rc = zeroed(&dl.d_z, zb, "z")) return rc;
+            if (const int rc = zeroed(&dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+            if (!last) {
+                if (const int rc = zeroed(&dl.d_t, x_bytes_of(dl.hr), "t")) return rc;
+                if (const int rc = zeroed(&dl.d_e, y_ext_bytes(dl.hp), "e")) return rc;
+            }
+            continue;
         }
         if (const int rc = upload(&dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
         if (!last) {
@@ -344,6 +591,10 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
         launch_level(amg_first_kernel<T>, f.n, st, static_cast<const T *>(f.d_dinv), static_cast<const T *>(f.d_r), static_cast<T *>(f.d_z), (long long)f.n);
         if (const int rc = smooth_more<T>(f, sweeps - 1, st)) return rc;
         HIP_TRY(run_spmv(f.h, f.d_z, f.d_q, st));
+        if (a->H.smoothed) {
+            launch_level(amg_residual_kernel<T>, f.n, st, static_cast<const T *>(f.d_r), static_cast<const T *>(f.d_q), static_cast<T *>(f.d_t), (long long)f.n);
+            HIP_TRY(run_spmv(f.hr, f.d_t, c.d_r, st));
+        } else
         launch_level(amg_restrict_kernel<T>, f.nc, st, static_cast<const int64_t *>(f.d_mrp), static_cast<const int32_t *>(f.d_mem), static_cast<const T *>(f.d_r), static_cast<const T *>(f.d_q),
                      static_cast<T *>(c.d_r), (long long)f.nc);
     }
@@ -356,7 +607,11 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
     }
     for (size_t l = L - 1; l-- > 0;) {
         const AmgLevel &f = a->lv[l], &c = a->lv[l + 1];
-        launch_level(amg_prolong_kernel<T>, f.n, st, static_cast<const int32_t *>(f.d_agg), static_cast<const T *>(c.d_z), static_cast<T *>(f.d_z), (long long)f.n, a->H.opt.coarse_scale);
+        if (a->H.smoothed) {
+            HIP_TRY(run_spmv(f.hp, c.d_z, f.d_e, st));
+            launch_level(amg_correct_kernel<T>, f.n, st, static_cast<const T *>(f.d_e), static_cast<T *>(f.d_z), (long long)f.n, a->H.opt.coarse_scale);
+        } else
+            launch_level(amg_prolong_kernel<T>, f.n, st, static_cast<const int32_t *>(f.d_agg), static_cast<const T *>(c.d_z), static_cast<T *>(f.d_z), (long long)f.n, a->H.opt.coarse_scale);
         if (const int rc = smooth_more<T>(f, sweeps, st)) return rc;
     }
     HIP_TRY(hipGetLastError());
@@ -405,7 +660,9 @@ void amg_release(cvr_precond *p)
     if (!a) return;
     for (AmgLevel &l : a->lv) {
         if (l.own && l.h) (void)cvr_destroy(l.h);
-        for (void *buf : {l.d_dinv, l.d_agg, l.d_mrp, l.d_mem, l.d_r, l.d_z, l.d_q})
+        if (l.hp) (void)cvr_destroy(l.hp);
+        if (l.hr) (void)cvr_destroy(l.hr);
+        for (void *buf : {l.d_dinv, l.d_agg, l.d_mrp, l.d_mem, l.d_r, l.d_z, l.d_q, l.d_t, l.d_e})
             if (buf) (void)hipFree(buf);
     }
     if (a->d_winv) (void)hipFree(a->d_winv);
@@ -416,27 +673,31 @@ void amg_release(cvr_precond *p)
 }  // namespace krylov
 }  // namespace cvrh
 
-extern "C" {
+namespace {
 
-int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream)
+// cvr_precond_amg and cvr_precond_amg_smoothed: one constructor, `smoothed` with its omega as given
+int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, bool smoothed, double omega, void *stream)
 {
+    const char *entry = smoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg";
     if (!out || !h || !csr) return fail(CVR_ERR_INVALID, "null argument");
     *out = nullptr;
     cvr_amg_options o;
     cvr_amg_default_options(&o);
     if (opt) o = *opt;
-    if (const int rc = amg::check_options(&o, "cvr_precond_amg")) return rc;
+    if (const int rc = amg::check_options(&o, entry)) return rc;
+    if (smoothed)
+        if (const int rc = amg::check_omega(omega, &omega, entry)) return rc;
     if (csr->nrows != csr->ncols) return fail(CVR_ERR_INVALID, "AMG needs a square matrix (%lld x %lld)", (long long)csr->nrows, (long long)csr->ncols);
     if (csr->nrows < 0) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
-    if (csr->nrows >= (int64_t)0x7fffffff) return fail(CVR_ERR_INVALID, "cvr_precond_amg: nrows (%lld) must stay below 2^31 - 1: the rows are the members of the aggregates", (long long)csr->nrows);
-    if (const int rc = check_square_preprocessed(h, "cvr_precond_amg", "an AMG preconditioner needs")) return rc;
-    if (h->info.nrows != csr->nrows) return fail(CVR_ERR_INVALID, "cvr_precond_amg: the view has nrows = %lld, the handle nrows = %lld", (long long)csr->nrows, (long long)h->info.nrows);
-    if ((csr->is_f32 != 0) != (h->vsz == 4)) return fail(CVR_ERR_INVALID, "cvr_precond_amg: the view's type is %s, the handle's %s", csr->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
+    if (csr->nrows >= (int64_t)0x7fffffff) return fail(CVR_ERR_INVALID, "%s: nrows (%lld) must stay below 2^31 - 1: the rows are the members of the aggregates", entry, (long long)csr->nrows);
+    if (const int rc = check_square_preprocessed(h, entry, "an AMG preconditioner needs")) return rc;
+    if (h->info.nrows != csr->nrows) return fail(CVR_ERR_INVALID, "%s: the view has nrows = %lld, the handle nrows = %lld", entry, (long long)csr->nrows, (long long)h->info.nrows);
+    if ((csr->is_f32 != 0) != (h->vsz == 4)) return fail(CVR_ERR_INVALID, "%s: the view's type is %s, the handle's %s", entry, csr->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
     if (!csr->arrays_on_device) {
         if (const int rc = check_csr(csr, true)) return rc;
-        if (const int rc = amg::check_structure(csr->nrows, csr->row_ptr, csr->col_idx, "cvr_precond_amg")) return rc;
+        if (const int rc = amg::check_structure(csr->nrows, csr->row_ptr, csr->col_idx, entry)) return rc;
     }
-    Range range("cvr_precond_amg");
+    Range range(entry);
     HIP_TRY(hipSetDevice(h->device));
     cvr_precond *p = new (std::nothrow) cvr_precond;
     Amg         *a = new (std::nothrow) Amg;
@@ -451,7 +712,7 @@ int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, c
     p->bs = 0;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->amg = a;
-    if (const int rc = build(p, h, csr, &o, (hipStream_t)stream)) {
+    if (const int rc = build(p, h, csr, &o, smoothed, omega, (hipStream_t)stream)) {
         char keep[sizeof(g_err)];          // (cvr_destroy of a half-made handle must not replace the message)
         memcpy(keep, g_err, sizeof(keep));
         cvr_precond_destroy(p);
@@ -461,6 +722,35 @@ int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, c
     }
     *out = p;
     return CVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream)
+{
+    return construct(out, h, csr, opt, false, 0.0, stream);
+}
+
+int cvr_precond_amg_smoothed(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream)
+{
+    return construct(out, h, csr, opt, true, omega, stream);
+}
+
+int cvr_precond_amg_smoothed_info(const cvr_precond *p, cvr_amg_smoothed_info *info)
+{
+    if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_smoothed_info: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    amg::fill_smoothed_info(p->amg->H, info);
+    return CVR_OK;
+}
+
+int cvr_precond_amg_export_prolongator(const cvr_precond *p, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals)
+{
+    if (!p) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_export_prolongator: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    return amg::export_prolongator(p->amg->H, level, row_ptr, col_idx, vals, "cvr_precond_amg_export_prolongator");
 }
 
 int cvr_precond_amg_info(const cvr_precond *p, cvr_amg_info *info)

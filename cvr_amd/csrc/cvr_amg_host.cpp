@@ -219,7 +219,7 @@ int64_t dense_inverse(const Level &l, std::vector<uint8_t> &winv)
 }
 
 template <typename T>
-int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_row)
+int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_row, const Coarsen *coarsen)
 {
     std::vector<double> diag;
     for (;;) {
@@ -238,9 +238,13 @@ int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_ro
         if ((double)nc > 0.8 * (double)l.n) break;          // a stall: this level is the last
         l.agg.swap(agg);
         l.nc = nc;
-        members(l);
         Level c;
-        coarse_operator<T>(l, c);
+        if (coarsen) {
+            if (const int rc = (*coarsen)(l, c, level)) return rc;
+        } else {
+            members(l);
+            coarse_operator<T>(l, c);
+        }
         H.lv.push_back(std::move(c));
     }
     const Level &last = H.lv.back();
@@ -259,7 +263,7 @@ int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_ro
 }  // namespace
 
 int setup(Hierarchy &H, int64_t n, const int64_t *rp, const int32_t *ci, const void *va, int is_f32, const cvr_amg_options *opt, const char *entry, int32_t *bad_level,
-          int64_t *bad_row)
+          int64_t *bad_row, const Coarsen *coarsen)
 {
     *bad_level = -1;
     *bad_row = -1;
@@ -280,7 +284,7 @@ int setup(Hierarchy &H, int64_t n, const int64_t *rp, const int32_t *ci, const v
             l.va.resize(vsz * (size_t)l.nnz);
             memcpy(l.va.data(), static_cast<const uint8_t *>(va) + vsz * (size_t)base, l.va.size());
         }
-        return is_f32 ? setup_t<float>(H, entry, bad_level, bad_row) : setup_t<double>(H, entry, bad_level, bad_row);
+        return is_f32 ? setup_t<float>(H, entry, bad_level, bad_row, coarsen) : setup_t<double>(H, entry, bad_level, bad_row, coarsen);
     } catch (const std::bad_alloc &) {
         return fail(CVR_ERR_NOMEM, "%s: out of host memory (%lld rows)", entry, (long long)n);
     }

@@ -905,6 +905,70 @@ int cvr_amg_hierarchy_info(const cvr_amg_hierarchy *hier, cvr_amg_info *info);
 int cvr_amg_hierarchy_export_level(const cvr_amg_hierarchy *hier, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals, void *dinv, int32_t *agg, void *winv);
 int cvr_amg_hierarchy_destroy(cvr_amg_hierarchy *hier);
 
+/* ---- the fifth kind with a smoothed prolongator: smoothed-aggregation AMG, Galerkin products by the SpGEMM ----
+ * A second way to build a kind-4 object.  With the piecewise-constant prolongator above the PCG step count still grows with the mesh (5-point
+ * Laplacian to 1e-8: 27, 32, 54 steps on 24 x 24, 40 x 40, 100 x 100); one damped l1-Jacobi step on that prolongator, P_l = (I - omega D_l^-1 A_l) T_l,
+ * makes it nearly mesh-independent (14, 16, 18 steps) at an operator complexity of about 1.4 against 1.26.  T_l is the tentative prolongator of the
+ * aggregation (one 1.0 per row, in column agg[i]); D_l is the l1 diagonal the object computes anyway (1 / dinv): by Gershgorin the spectral radius of
+ * D_l^-1 A_l is at most 1, so no eigenvalue estimate is needed.  The coarse operator is A_(l+1) = P_l^T (A_l P_l), two sparse products.
+ * cvr_precond_amg, cvr_amg_setup_host and their structs are unchanged; the smoothed kind has entry points of its own.  The object is of kind 4:
+ * everything said above of the borrowed handle, the CSR input, n = 0, one stream at a time, cvr_precond_get_info, cvr_precond_destroy, the entry
+ * points that decline kind 4 (naming "kind 4 (AMG)") and the cross-kind calls holds for it, and cvr_precond_amg_info / cvr_precond_amg_export_level
+ * (and their hierarchy twins) work on it unchanged: reserved words 0, agg the tentative aggregation.
+ * omega: 0.0 means the default 4/3 (the literal 4.0 / 3.0; on the Laplacian the usual 4 / (3 rho) of the plain diagonal); any other value must be
+ *   finite with 0 < omega < 2.
+ * Set-up.  fp64 on the values converted to double, every operation rounded on its own (no fused multiply-add), every stored value rounded to T
+ *   once; products "by the SpGEMM contract" are cvr_spgemm_create's C = A B: structural pattern (an entry that cancels to 0.0 stays), rows
+ *   ascending, acc = +0, acc = T(acc + T(a * b)) in ascending position of the left row.  At level l the smoother diagonal, the stopping rule, the
+ *   strength test, the aggregation and the stall rule are those above, in that order, unchanged.  Then:
+ *   1. T_l as a CSR of n_l x n_(l+1): row_ptr = 0 .. n_l, col_idx[i] = agg[i], vals[i] = 1.
+ *   2. G = A_l T_l by the SpGEMM contract.  Row i holds column agg[i], since row i of A_l has a diagonal entry.
+ *   3. P_l on G's pattern: w_i = omega * double(dinv_i);  p_ij = T(t_ij - w_i * double(g_ij)) with t_ij = 1.0 for j == agg[i] and 0.0 otherwise:
+ *      omega times dinv first, that times g second, the subtraction third.  A g_ij that is 0.0 keeps its entry in P_l.
+ *   4. R_l = P_l^T as a CSR of n_(l+1) x n_l: row J holds P_l's entries of column J in ascending row of P_l (a stable transpose; values copied).
+ *   5. A_(l+1) = R_l (A_l P_l): two products by the SpGEMM contract, so every value is a fixed-order sum with one rounding in T per product and per
+ *      addition.  Its rows are ascending and every row has a diagonal entry (P_l's column J is not empty), so the structure rules hold for the next
+ *      level.  A_(l+1) is symmetric only to rounding: R_l (A_l P_l) and its transpose sum the same terms in another order.  That is accepted: the
+ *      dense inverse reads the lower triangle only, the strength test is per entry, and PCG meets a preconditioner that is symmetric to rounding.
+ *   The coarsest level is treated as above (the dense inverse for n <= CVR_AMG_MAX_COARSE, else 2 * sweeps sweeps).
+ * cvr_amg_smoothed_setup_host does steps 2 and 5 with cvr_spgemm_host and the rest in host loops.  cvr_precond_amg_smoothed does steps 1 - 5 on
+ *   the device: agg and dinv are uploaded, steps 1 and 3 are kernels of a thread per row, step 4 is cvr_options.transpose's device transpose, steps
+ *   2 and 5 are cvr_spgemm_create on device arrays (CVR_DEBUG=spgemm_limits applies; it never changes a bit).  A level's arrays stay on the device
+ *   for the handles and come to the host once per level, for the next level's aggregation (host code) and for the exports.  Host and device SpGEMM
+ *   give the same bits, so the object's levels and prolongators are the host twin's byte for byte.  Failures as above: CVR_ERR_STATE naming level
+ *   and row, nothing left allocated; a CVR_ERR_NOMEM of a product propagates.
+ * The object owns what a plain one owns (the members of the aggregates excepted) and, per level above the coarsest, a handle of P_l (n_l x n_(l+1))
+ *   and a handle of R_l (made from the transposed arrays, not with transpose = 1), both cvr_create + cvr_preprocess from device arrays with
+ *   cvr_default_options: their products are bit for bit those of a caller's handle of the exported arrays.  Beside r, z and q a level has t (R_l's
+ *   x: x_elems values, element n_l stays 0) and e (P_l's y: yext_elems values); r_(l+1) is R_l's y (yext_elems) and z_(l+1) is P_l's x and
+ *   A_(l+1)'s (the larger x_elems; element n_(l+1) stays 0).  No buffer is one product's y and another one's x: a y-scratch tail never meets a pad.
+ * Cycle: steps 1, 2, 4 and 6 of the cycle above, and in place of steps 3 and 5:
+ *     3'. q = A_l z;  t_i = T(r_i - q_i);  r_(l+1) = R_l t through cvr_spmv_device's launch path.
+ *     5'. e = P_l z_(l+1) through the same path;  z_i = T(z_i + coarse_scale * e_i).
+ *   An apply enqueues (2 * sweeps + 2) * (levels - 1) products, and 2 * sweeps - 1 more when the coarsest level is smoothed (products_per_apply);
+ *   spmv_count of cvr_pcg_device follows with that P.  cvr_precond_apply_device and cvr_pcg_device / cvr_pcg take the object as they take a plain
+ *   one: the apply only enqueues, reads nothing back, forms no dot product, has no kernel that waits on another workgroup and no floating-point
+ *   atomic, gives the same bits on every call for every alignment of r_dev and z_dev, and its last launch writes z and the partial sums of r.z.
+ * cvr_precond_amg_smoothed_info / cvr_amg_hierarchy_smoothed_info fill a cvr_amg_smoothed_info; of a plain kind-4 object or hierarchy: all zero.
+ * cvr_precond_amg_export_prolongator / cvr_amg_hierarchy_export_prolongator write P_l of level 0 .. levels - 2 to host arrays: row_ptr (n_l + 1),
+ *   col_idx and vals (p_nnz[level]); a caller reads the sizes from the two infos first.  The coarsest level, a level outside the hierarchy, a plain
+ *   object or hierarchy, another kind, or a null array: CVR_ERR_INVALID.
+ * Errors of cvr_precond_amg_smoothed: those of cvr_precond_amg in their order, with the check of omega (CVR_ERR_INVALID, "omega" in
+ *   cvr_last_error) right behind the options; of cvr_amg_smoothed_setup_host: those of cvr_amg_setup_host, omega likewise. */
+typedef struct {
+    int32_t smoothed;                          /* 1: built by a *_smoothed entry point; 0: plain, and everything below is 0 */
+    int32_t products_per_apply;
+    double  omega;                             /* as used: 4/3 for an argument of 0.0                                       */
+    int64_t p_nnz[CVR_AMG_MAX_LEVELS];         /* entries of P_l; 0 from the coarsest level on                              */
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_amg_smoothed_info;                       /* 176 bytes */
+int cvr_precond_amg_smoothed(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream);
+int cvr_amg_smoothed_setup_host(cvr_amg_hierarchy **out, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, int32_t *bad_level, int64_t *bad_row);
+int cvr_precond_amg_smoothed_info(const cvr_precond *p, cvr_amg_smoothed_info *info);
+int cvr_amg_hierarchy_smoothed_info(const cvr_amg_hierarchy *hier, cvr_amg_smoothed_info *info);
+int cvr_precond_amg_export_prolongator(const cvr_precond *p, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals);
+int cvr_amg_hierarchy_export_prolongator(const cvr_amg_hierarchy *hier, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals);
+
 /* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
