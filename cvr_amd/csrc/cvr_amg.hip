@@ -7,10 +7,10 @@
 //   Per level: r (n values), z (an SpMV input: element n stays 0 -- the kernels write elements 0 .. n - 1 only, and no product writes into a z),
 //     q (an SpMV output), dinv, and above the coarsest level agg, mrp and mem.  No buffer is one product's output and another one's input, so
 //     there is no pad slot to zero between products.
-//   Apply: amg_in_kernel (r_0 = r) | down: amg_first_kernel, [product, amg_smooth_kernel] x (sweeps - 1), product, amg_restrict_kernel | the
+//   Apply: precond_copy_in_kernel (r_0 = r) | down: amg_first_kernel, [product, amg_smooth_kernel] x (sweeps - 1), product, amg_restrict_kernel | the
 //     coarsest level: amg_dense_kernel (z = W r, one workgroup, a thread per row) or 2 * sweeps sweeps | up: amg_prolong_kernel, [product,
-//     amg_smooth_kernel] x sweeps | amg_out_kernel (z = z_0), or inside cvr_pcg_device amg_rz_kernel in its place (z = z_0 with the partial sums of
-//     r . z and, at the start, p = z; nothing behind a stop).  The level kernels take a thread per element on a grid cut to the level's size; the
+//     amg_smooth_kernel] x sweeps | precond_copy_out_kernel (z = z_0), or inside cvr_pcg_device precond_rz_kernel in its place (z = z_0 with the
+//     partial sums of r . z and, at the start, p = z; nothing behind a stop): cvr_precond.h's.  The level kernels take a thread per element on a grid cut to the level's size; the
 //     first and the last run on the solvers' grid.
 // The smoothed kind (cvr_precond_amg_smoothed: the same object with Hierarchy::smoothed set) builds every level on the device inside the host
 // set-up's loop (SmoothedBuild: amg_tentative_kernel, the device SpGEMM, amg_prolongator_kernel, transpose_csr, two more products), owns a handle of
@@ -51,50 +51,6 @@ struct Amg {
 namespace {
 
 // ---- the device half
-
-// r0 = r.  AL: r, the caller's array, is 16-byte aligned
-template <typename T, bool AL>
-__global__ __launch_bounds__(kThreads) void amg_in_kernel(const T *__restrict__ r, T *__restrict__ r0, long long n)
-{
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T v[kPack<T>];
-        load_pack<T, AL>(r, e, (int)cnt, v);
-        store_pack<T, true>(r0, e, (int)cnt, v);
-    }
-}
-
-// z = z0.  AL: z, the caller's array, is 16-byte aligned
-template <typename T, bool AL>
-__global__ __launch_bounds__(kThreads) void amg_out_kernel(const T *__restrict__ z0, T *__restrict__ z, long long n)
-{
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T v[kPack<T>];
-        load_pack<T, true>(z0, e, (int)cnt, v);
-        store_pack<T, AL>(z, e, (int)cnt, v);
-    }
-}
-
-// the same inside cvr_pcg_device: z = z0, the partial sums of r . z (the term double(r_i) * double(z_i) added in the thread that owns element i in
-// element order: pcg_apply_kernel's), and at the start p = z; behind a stop nothing is written
-template <typename T, bool START>
-__global__ __launch_bounds__(kThreads) void amg_rz_kernel(const T *__restrict__ r, const T *__restrict__ z0, T *__restrict__ z, T *__restrict__ p, long long n,
-                                                          double *__restrict__ out, const CgCell *__restrict__ cell)
-{
-    __shared__ double sh[1][kWaves];
-    if constexpr (!START)
-        if (cell->stop) return;          // (no workgroup of this kernel sets it)
-    double acc[1] = {0};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T rv[kPack<T>], zv[kPack<T>];
-        load_pack<T, true>(r, e, (int)cnt, rv);
-        load_pack<T, true>(z0, e, (int)cnt, zv);
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[0] += (double)rv[j] * (double)zv[j];
-        store_pack<T, true>(z, e, (int)cnt, zv);
-        if constexpr (START) store_pack<T, true>(p, e, (int)cnt, zv);
-    }
-    store_partials<1>(acc, out, sh);
-}
 
 // the elements of a thread of a level kernel: a grid-stride loop, whatever grid the level was given
 #define CVR_AMG_ELEMENTS(i, n) for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < (n); i += (long long)gridDim.x * kThreads)
@@ -199,137 +155,26 @@ void launch_level(void (*kernel)(P...), long long n, hipStream_t st, A... args)
     hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<long long>(blocks, 1)), dim3(kThreads), 0, st, args...);
 }
 
-int device_alloc(void **out, size_t bytes, const char *what)
-{
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) return CVR_OK;
-    *out = nullptr;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_amg: no device memory for %s (%zu bytes)", what, bytes);
-    return fail(CVR_ERR_HIP, "cvr_precond_amg: hipMalloc of %s: %s", what, hipGetErrorString(e));
-}
+constexpr const char *kEntry = "cvr_precond_amg";          // (as the allocation messages of both constructors begin)
 
-// a device array of the object's with the host's bytes in it
-int upload(void **out, const void *src, size_t bytes, const char *what)
-{
-    if (const int rc = device_alloc(out, bytes, what)) return rc;
-    if (bytes) HIP_TRY(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
-    return CVR_OK;
-}
-
-int zeroed(void **out, size_t bytes, const char *what)
-{
-    if (const int rc = device_alloc(out, bytes, what)) return rc;
-    HIP_TRY(hipMemset(*out, 0, bytes ? bytes : 1));
-    return CVR_OK;
-}
-
-// The view on the host: the caller's own arrays, or copies of row_ptr, col_idx and vals brought down once on `st`, checked as cvr_precond_fsai
-// checks them
-struct HostCsr {
-    const int64_t       *rp = nullptr;
-    const int32_t       *ci = nullptr;
-    const void          *va = nullptr;
-    std::vector<int64_t> rp_own;
-    std::vector<int32_t> ci_own;
-    std::vector<uint8_t> va_own;
-};
-
-int stage_host(const cvr_csr_view *c, HostCsr &h, hipStream_t st)
-{
-    const int64_t n = c->nrows;
-    if (!c->arrays_on_device) {          // (checked before any device work: cvr_precond_amg)
-        h.rp = c->row_ptr;
-        h.ci = c->col_idx;
-        h.va = c->vals;
-        return CVR_OK;
-    }
-    try {
-        h.rp_own.assign((size_t)n + 1, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory for row_ptr (%lld rows)", (long long)n);
-    }
-    if (n > 0) {
-        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
-        HIP_TRY(hipMemcpyAsync(h.rp_own.data(), c->row_ptr, sizeof(int64_t) * h.rp_own.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    cvr_csr_view hv = *c;
-    hv.row_ptr = h.rp_own.data();
-    if (const int rc = check_csr(&hv, false)) return rc;
-    h.rp = h.rp_own.data();
-    if (n > 0) {
-        if (const int rc = check_columns_device(c->col_idx, h.rp_own.front(), h.rp_own.back(), c->ncols)) return rc;
-        const int64_t j0 = h.rp_own.front(), nnz = h.rp_own.back() - j0;
-        const size_t  vsz = c->is_f32 ? 4 : 8;
-        try {
-            h.ci_own.assign((size_t)h.rp_own.back(), 0);
-            h.va_own.assign(vsz * (size_t)h.rp_own.back(), 0);
-        } catch (const std::bad_alloc &) {
-            return fail(CVR_ERR_NOMEM, "cvr_precond_amg: out of host memory for col_idx and vals (%lld entries)", (long long)nnz);
-        }
-        if (nnz > 0) {
-            if (!c->vals) return fail(CVR_ERR_INVALID, "vals is null");
-            HIP_TRY(hipMemcpy(h.ci_own.data() + j0, c->col_idx + j0, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(h.va_own.data() + vsz * (size_t)j0, static_cast<const uint8_t *>(c->vals) + vsz * (size_t)j0, vsz * (size_t)nnz, hipMemcpyDeviceToHost));
-        }
-    }
-    h.ci = h.ci_own.data();
-    h.va = h.va_own.data();
-    return amg::check_structure(n, h.rp, h.ci, "cvr_precond_amg");
-}
-
-// device memory that lives for the build only
-struct Scratch {
-    std::vector<void *> bufs;
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch()
-    {
-        for (void *p : bufs)
-            if (p) (void)hipFree(p);
-    }
-};
-
-// a coarse level's handle: cvr_create + cvr_preprocess of device arrays with the default options on the object's device
-int make_handle(cvr_handle **out, const amg::Level &l, int is_f32, int device, Scratch &s)
+// a level's CSR in device memory, uploaded from the host's copy into buffers that `s` owns
+int upload_level(const amg::Level &l, int is_f32, Scratch &s, const char *rp_what, const char *ci_what, const char *va_what, cvr_csr_view *out)
 {
     void *d_rp = nullptr, *d_ci = nullptr, *d_va = nullptr;
-    if (const int rc = upload(&d_rp, l.rp.data(), sizeof(int64_t) * l.rp.size(), "a level's row_ptr")) return rc;
+    if (const int rc = upload(kEntry, &d_rp, l.rp.data(), sizeof(int64_t) * l.rp.size(), rp_what)) return rc;
     s.bufs.push_back(d_rp);
-    if (const int rc = upload(&d_ci, l.ci.data(), sizeof(int32_t) * l.ci.size(), "a level's col_idx")) return rc;
+    if (const int rc = upload(kEntry, &d_ci, l.ci.data(), sizeof(int32_t) * l.ci.size(), ci_what)) return rc;
     s.bufs.push_back(d_ci);
-    if (const int rc = upload(&d_va, l.va.data(), l.va.size(), "a level's values")) return rc;
+    if (const int rc = upload(kEntry, &d_va, l.va.data(), l.va.size(), va_what)) return rc;
     s.bufs.push_back(d_va);
-    cvr_csr_view v{};
-    v.nrows = v.ncols = l.n;
-    v.row_ptr = static_cast<const int64_t *>(d_rp);
-    v.col_idx = static_cast<const int32_t *>(d_ci);
-    v.vals = d_va;
-    v.is_f32 = is_f32;
-    v.arrays_on_device = 1;
-    cvr_options opt;
-    cvr_default_options(&opt);
-    opt.device = device;
-    if (const int rc = cvr_create(out, &v, &opt)) {
-        *out = nullptr;
-        return rc;
-    }
-    return cvr_preprocess(*out, 0, nullptr);
-}
-
-// a handle of the object's own: cvr_create + cvr_preprocess of a view of device arrays with the default options on the object's device
-int handle_of(cvr_handle **out, const cvr_csr_view &v, int device)
-{
-    cvr_options opt;
-    cvr_default_options(&opt);
-    opt.device = device;
-    if (const int rc = cvr_create(out, &v, &opt)) {
-        *out = nullptr;
-        return rc;
-    }
-    return cvr_preprocess(*out, 0, nullptr);
+    *out = cvr_csr_view{};
+    out->nrows = out->ncols = l.n;
+    out->row_ptr = static_cast<const int64_t *>(d_rp);
+    out->col_idx = static_cast<const int32_t *>(d_ci);
+    out->vals = d_va;
+    out->is_f32 = is_f32;
+    out->arrays_on_device = 1;
+    return CVR_OK;
 }
 
 // The smoothed kind's levels on the device, one coarsening step per call from inside amg::setup's loop (the aggregation before it and the next
@@ -375,35 +220,22 @@ struct SmoothedBuild {
         AmgLevel &dl = a->lv[(size_t)level];          // (sized for CVR_AMG_MAX_LEVELS before the set-up)
         const int is_f32 = p->is_f32;
         if (level == 0) {
-            void *d_rp = nullptr, *d_ci = nullptr, *d_va = nullptr;
-            if (const int rc = upload(&d_rp, f.rp.data(), sizeof(int64_t) * f.rp.size(), "level 0's row_ptr")) return rc;
-            cur_bufs.bufs.push_back(d_rp);
-            if (const int rc = upload(&d_ci, f.ci.data(), sizeof(int32_t) * f.ci.size(), "level 0's col_idx")) return rc;
-            cur_bufs.bufs.push_back(d_ci);
-            if (const int rc = upload(&d_va, f.va.data(), f.va.size(), "level 0's values")) return rc;
-            cur_bufs.bufs.push_back(d_va);
-            cur = cvr_csr_view{};
-            cur.nrows = cur.ncols = f.n;
-            cur.row_ptr = static_cast<const int64_t *>(d_rp);
-            cur.col_idx = static_cast<const int32_t *>(d_ci);
-            cur.vals = d_va;
-            cur.is_f32 = is_f32;
-            cur.arrays_on_device = 1;
+            if (const int rc = upload_level(f, is_f32, cur_bufs, "level 0's row_ptr", "level 0's col_idx", "level 0's values", &cur)) return rc;
         } else {
             dl.own = true;
-            if (const int rc = handle_of(&dl.h, cur, p->device)) return rc;
+            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
         }
         const long long n = f.n;
-        if (const int rc = upload(&dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
-        if (const int rc = upload(&dl.d_agg, f.agg.data(), sizeof(int32_t) * f.agg.size(), "agg")) return rc;
+        if (const int rc = upload(kEntry, &dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
+        if (const int rc = upload(kEntry, &dl.d_agg, f.agg.data(), sizeof(int32_t) * f.agg.size(), "agg")) return rc;
         // 1. T
         Scratch s;
         void   *d_trp = nullptr, *d_tci = nullptr, *d_tva = nullptr, *d_pva = nullptr;
-        if (const int rc = device_alloc(&d_trp, sizeof(int64_t) * (size_t)(n + 1), "the tentative prolongator")) return rc;
+        if (const int rc = device_alloc(kEntry, &d_trp, sizeof(int64_t) * (size_t)(n + 1), "the tentative prolongator")) return rc;
         s.bufs.push_back(d_trp);
-        if (const int rc = device_alloc(&d_tci, sizeof(int32_t) * (size_t)n, "the tentative prolongator")) return rc;
+        if (const int rc = device_alloc(kEntry, &d_tci, sizeof(int32_t) * (size_t)n, "the tentative prolongator")) return rc;
         s.bufs.push_back(d_tci);
-        if (const int rc = device_alloc(&d_tva, sizeof(T) * (size_t)n, "the tentative prolongator")) return rc;
+        if (const int rc = device_alloc(kEntry, &d_tva, sizeof(T) * (size_t)n, "the tentative prolongator")) return rc;
         s.bufs.push_back(d_tva);
         launch_level(amg_tentative_kernel<T>, n + 1, st, static_cast<const int32_t *>(dl.d_agg), static_cast<int64_t *>(d_trp), static_cast<int32_t *>(d_tci), static_cast<T *>(d_tva), n);
         HIP_TRY(hipGetLastError());
@@ -424,7 +256,7 @@ struct SmoothedBuild {
         if (const int rc = cvr_spgemm_get_info(G.g, &gi)) return rc;
         const size_t pnnz = (size_t)gi.nnz;
         // 3. P on G's pattern
-        if (const int rc = device_alloc(&d_pva, sizeof(T) * pnnz, "the prolongator's values")) return rc;
+        if (const int rc = device_alloc(kEntry, &d_pva, sizeof(T) * pnnz, "the prolongator's values")) return rc;
         s.bufs.push_back(d_pva);
         launch_level(amg_prolongator_kernel<T>, n, st, gv.row_ptr, gv.col_idx, static_cast<const T *>(gv.vals), static_cast<const int32_t *>(dl.d_agg), static_cast<const T *>(dl.d_dinv), omega,
                      static_cast<T *>(d_pva), n);
@@ -463,8 +295,8 @@ struct SmoothedBuild {
         c.va.assign(sizeof(T) * (size_t)c.nnz, 0);
         if (const int rc = cvr_spgemm_export(AC.g, c.rp.data(), c.ci.data(), c.va.data())) return rc;
         // the two transfer handles, from the device arrays
-        if (const int rc = handle_of(&dl.hp, pv, p->device)) return rc;
-        if (const int rc = handle_of(&dl.hr, rv, p->device)) return rc;
+        if (const int rc = make_handle(&dl.hp, pv, p->device, 0)) return rc;
+        if (const int rc = make_handle(&dl.hr, rv, p->device, 0)) return rc;
         HIP_TRY(hipDeviceSynchronize());          // (the handles' copies are complete before the step's arrays go)
         if (cur_owner) (void)cvr_spgemm_destroy(cur_owner);
         cur_owner = AC.g;
@@ -484,7 +316,9 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
     SmoothedBuild sb;
     {
         HostCsr hc;
-        if (const int rc = stage_host(csr, hc, st)) return rc;
+        if (const int rc = stage_host(kEntry, csr, hc, true, st)) return rc;
+        if (csr->arrays_on_device)          // (host arrays: checked before any device work, in construct)
+            if (const int rc = amg::check_structure(p->n, hc.rp, hc.ci, kEntry)) return rc;
         int32_t bad_level = -1;
         int64_t bad_row = -1;
         if (smoothed) {
@@ -527,41 +361,43 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
         else if (smoothed) {
             if (last && !H.coarse_direct) {          // (the levels above it got theirs in their coarsening step)
                 dl.own = true;
-                if (const int rc = handle_of(&dl.h, sb.cur, p->device)) return rc;
+                if (const int rc = make_handle(&dl.h, sb.cur, p->device, 0)) return rc;
             }
         } else if (!(last && H.coarse_direct)) {
             dl.own = true;
-            if (const int rc = make_handle(&dl.h, hl, p->is_f32, p->device, s)) return rc;
+            cvr_csr_view lv{};
+            if (const int rc = upload_level(hl, p->is_f32, s, "a level's row_ptr", "a level's col_idx", "a level's values", &lv)) return rc;
+            if (const int rc = make_handle(&dl.h, lv, p->device, 0)) return rc;
         }
         if (smoothed) {
             if (last)
-                if (const int rc = upload(&dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
+                if (const int rc = upload(kEntry, &dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
             // r is R_(l-1)'s output, z is P_(l-1)'s input beside A_l's, t is R_l's input, e is P_l's output; zeroed: the pad slots stay 0
             const AmgLevel *up = l > 0 ? &a->lv[l - 1] : nullptr;
             size_t          rb = vsz * (size_t)std::max<int64_t>(hl.n, 1), zb = dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1);
             if (up) rb = std::max(rb, y_ext_bytes(up->hr)), zb = std::max(zb, x_bytes_of(up->hp));
-            if (const int rc = zeroed(&dl.d_r, rb, "r")) return rc;
-            if (const int rc = zeroed(&dl.d_z, zb, "z")) return rc;
-            if (const int rc = zeroed(&dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+            if (const int rc = zeroed(kEntry, &dl.d_r, rb, "r")) return rc;
+            if (const int rc = zeroed(kEntry, &dl.d_z, zb, "z")) return rc;
+            if (const int rc = zeroed(kEntry, &dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
             if (!last) {
-                if (const int rc = zeroed(&dl.d_t, x_bytes_of(dl.hr), "t")) return rc;
-                if (const int rc = zeroed(&dl.d_e, y_ext_bytes(dl.hp), "e")) return rc;
+                if (const int rc = zeroed(kEntry, &dl.d_t, x_bytes_of(dl.hr), "t")) return rc;
+                if (const int rc = zeroed(kEntry, &dl.d_e, y_ext_bytes(dl.hp), "e")) return rc;
             }
             continue;
         }
-        if (const int rc = upload(&dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
+        if (const int rc = upload(kEntry, &dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
         if (!last) {
-            if (const int rc = upload(&dl.d_agg, hl.agg.data(), sizeof(int32_t) * hl.agg.size(), "agg")) return rc;
-            if (const int rc = upload(&dl.d_mrp, hl.mrp.data(), sizeof(int64_t) * hl.mrp.size(), "the aggregates' row_ptr")) return rc;
-            if (const int rc = upload(&dl.d_mem, hl.mem.data(), sizeof(int32_t) * hl.mem.size(), "the aggregates' members")) return rc;
+            if (const int rc = upload(kEntry, &dl.d_agg, hl.agg.data(), sizeof(int32_t) * hl.agg.size(), "agg")) return rc;
+            if (const int rc = upload(kEntry, &dl.d_mrp, hl.mrp.data(), sizeof(int64_t) * hl.mrp.size(), "the aggregates' row_ptr")) return rc;
+            if (const int rc = upload(kEntry, &dl.d_mem, hl.mem.data(), sizeof(int32_t) * hl.mem.size(), "the aggregates' members")) return rc;
         }
         // r, z, q, zeroed: z[n] is the pad slot of an SpMV input and is never written again
-        if (const int rc = zeroed(&dl.d_r, vsz * (size_t)std::max<int64_t>(hl.n, 1), "r")) return rc;
-        if (const int rc = zeroed(&dl.d_z, dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1), "z")) return rc;
-        if (const int rc = zeroed(&dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+        if (const int rc = zeroed(kEntry, &dl.d_r, vsz * (size_t)std::max<int64_t>(hl.n, 1), "r")) return rc;
+        if (const int rc = zeroed(kEntry, &dl.d_z, dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1), "z")) return rc;
+        if (const int rc = zeroed(kEntry, &dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
     }
     if (H.coarse_direct)
-        if (const int rc = upload(&a->d_winv, H.winv.data(), H.winv.size(), "the coarsest level's inverse")) return rc;
+        if (const int rc = upload(kEntry, &a->d_winv, H.winv.data(), H.winv.size(), "the coarsest level's inverse")) return rc;
     HIP_TRY(hipDeviceSynchronize());          // (the handles' copies of the levels are complete before the scratch goes; the buffers are zeroed)
     return CVR_OK;
 }
@@ -584,7 +420,7 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
     const size_t    L = a->lv.size();
     const int       sweeps = a->H.opt.sweeps;
     const long long n = pc->n;
-    with_flags([&](auto AL) { launch(amg_in_kernel<T, AL>, st, r, static_cast<T *>(a->lv[0].d_r), n); }, al);
+    with_flags([&](auto AL) { launch(precond_copy_in_kernel<T, AL>, st, r, static_cast<T *>(a->lv[0].d_r), n); }, al);
     HIP_TRY(hipGetLastError());
     for (size_t l = 0; l + 1 < L; l++) {
         const AmgLevel &f = a->lv[l], &c = a->lv[l + 1];
@@ -618,11 +454,6 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
     return CVR_OK;
 }
 
-}  // namespace
-
-namespace cvrh {
-namespace krylov {
-
 int amg_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
 {
     const Amg *a = p->amg;
@@ -631,10 +462,10 @@ int amg_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
     const long long n = p->n;
     if (p->is_f32) {
         if (const int rc = enqueue_cycle<float>(p, static_cast<const float *>(r), ral, st)) return rc;
-        with_flags([&](auto AL) { launch(amg_out_kernel<float, AL>, st, static_cast<const float *>(a->lv[0].d_z), static_cast<float *>(z), n); }, zal);
+        with_flags([&](auto AL) { launch(precond_copy_out_kernel<float, AL>, st, static_cast<const float *>(a->lv[0].d_z), static_cast<float *>(z), n); }, zal);
     } else {
         if (const int rc = enqueue_cycle<double>(p, static_cast<const double *>(r), ral, st)) return rc;
-        with_flags([&](auto AL) { launch(amg_out_kernel<double, AL>, st, static_cast<const double *>(a->lv[0].d_z), static_cast<double *>(z), n); }, zal);
+        with_flags([&](auto AL) { launch(precond_copy_out_kernel<double, AL>, st, static_cast<const double *>(a->lv[0].d_z), static_cast<double *>(z), n); }, zal);
     }
     HIP_TRY(hipGetLastError());
     return CVR_OK;
@@ -647,13 +478,10 @@ int amg_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz,
     if (!a || pc->n == 0) return CVR_OK;
     if (const int rc = enqueue_cycle<T>(pc, r, true, st)) return rc;
     if (spmvs) *spmvs += a->products;
-    with_flags([&](auto START) { launch(amg_rz_kernel<T, START>, st, r, static_cast<const T *>(a->lv[0].d_z), z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
+    with_flags([&](auto START) { launch(precond_rz_kernel<T, START, true>, st, r, static_cast<const T *>(a->lv[0].d_z), z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
-template int amg_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
-template int amg_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
-
 void amg_release(cvr_precond *p)
 {
     Amg *a = p->amg;
@@ -669,6 +497,13 @@ void amg_release(cvr_precond *p)
     delete a;
     p->amg = nullptr;
 }
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+PrecondOps kAmgOps = {kPrecondAmg, "AMG", amg_apply_any, amg_release, amg_cg_apply<float>, amg_cg_apply<double>};
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -707,19 +542,13 @@ int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const c
         return fail(CVR_ERR_NOMEM, "out of host memory");
     }
     p->kind = kPrecondAmg;
+    p->ops = &kAmgOps;
     p->device = h->device;
     p->n = csr->nrows;
     p->bs = 0;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->amg = a;
-    if (const int rc = build(p, h, csr, &o, smoothed, omega, (hipStream_t)stream)) {
-        char keep[sizeof(g_err)];          // (cvr_destroy of a half-made handle must not replace the message)
-        memcpy(keep, g_err, sizeof(keep));
-        cvr_precond_destroy(p);
-        memcpy(g_err, keep, sizeof(keep));
-        (void)hipSetDevice(h->device);
-        return rc;
-    }
+    if (const int rc = build(p, h, csr, &o, smoothed, omega, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }

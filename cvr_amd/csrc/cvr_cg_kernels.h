@@ -1,24 +1,11 @@
-// cvr_cg_kernels.h -- the state cell and the vector kernels of conjugate gradients (cvr_cg.hip: cvr_cg_device, cvr_pcg_device).  cvr_precond.hip and
-// cvr_chebyshev.hip include it for the cell, which their applies inside the solver read.  What each kernel does: cvr_cg.hip's head.
+// cvr_cg_kernels.h -- the vector kernels of conjugate gradients (cvr_cg.hip: cvr_cg_device, cvr_pcg_device); the state cell they keep is
+// cvr_krylov.h's CgCell.  What each kernel does: cvr_cg.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 
 namespace cvrh {
 namespace krylov {
 namespace {
-
-// The state cell.  Written by thread 0 of workgroup 0 only; a value a kernel reads is one that a kernel BEFORE it wrote (r.z of the step before sits
-// in rz[k & 1], this step's goes to rz[(k + 1) & 1]) -- except `stop`, which the other workgroups of the kernel that sets it may or may not see yet:
-// they come to the same decision from the same sums, so either way they return without writing.
-struct CgCell {
-    double  bb, bnorm;         // b . b and its root
-    double  rr, rnorm;         // r . r of the last iterate and its root
-    double  rz[2];
-    int32_t stop;              // != 0: no kernel writes a vector any more
-    int32_t status;            // CVR_CG_*
-    int32_t iters;             // steps applied to x
-    int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
-};
 
 // The start: r holds b - A x0 (the scaled product).  z = minv .* r (PRE), p = z (or r), and the partial sums of r . r, r . z (PRE) and b . b.
 // AL: b and minv, the caller's arrays, are 16-byte aligned.

@@ -1,5 +1,5 @@
-// cvr_cg_multi_kernels.h -- the state cells, the vector kernels and the host pieces of batched conjugate gradients (cvr_cg_multi.hip:
-// cvr_cg_multi_device, cvr_pcg_multi_device).  cvr_pcg_multi.hip includes it for the cells and the column walk of its k-wide apply.
+// cvr_cg_multi_kernels.h -- the vector kernels and the host pieces of batched conjugate gradients (cvr_cg_multi.hip:
+// cvr_cg_multi_device, cvr_pcg_multi_device).  cvr_pcg_multi.hip includes it for the column walk of its k-wide apply.
 // What the kernels do and how a row's columns are walked: cvr_cg_multi.hip's head.
 #pragma once
 #include "cvr_krylov.h"
@@ -10,14 +10,6 @@ namespace {
 
 constexpr int kCols = cvr::kSpmmBlock;          // columns per call
 constexpr int kSets = 3;                        // partial-sum sets per column in `part`: column c's begin at part + c * kSets * kBlocks
-
-// a column's state cell: cvr_cg.hip's CgCell, member for member
-struct CgCell {
-    double  bb, bnorm;
-    double  rr, rnorm;
-    double  rz[2];
-    int32_t stop, status, iters, zero_x;
-};
 
 // the sub-block's values at p + off for the columns of `mask` (bits 0 .. kPack - 1): one 16-byte store when all of them are live, else one by one
 template <typename T, bool VEC>

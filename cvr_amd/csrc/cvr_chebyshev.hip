@@ -7,7 +7,7 @@
 // Both come in four modes: kInner (z goes to the object's zi: an earlier step), kLast (z goes to the caller's array: the last step of
 // cvr_precond_apply_device), kSolve and kSolveStart (the last step inside cvr_pcg_device: z goes to the solver's buffer with the partial sums of
 // r . z in set 1, what pcg_apply_kernel forms; at the start p = z too; behind a stop nothing is written).  With degree = 1 step 0 is the last.
-// The solver is cvr_cg.hip's cg_solve, which enqueues this apply through chebyshev_cg_apply (cvr_precond.h) between cg_update_kernel<T, false, AL>
+// The solver is cvr_cg.hip's cg_solve, which enqueues this apply through kChebyshevOps' cg_apply (cvr_precond.h) between cg_update_kernel<T, false, AL>
 // and cg_direction_kernel<T, true>: 3 + degree vector launches and degree SpMVs per step.  This file launches no cg_* kernel and holds no solve loop
 // (cvr_cg_kernels.h is included for the state cell the kSolve kernels read).
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
@@ -17,6 +17,19 @@
 
 using namespace cvrh;
 using namespace cvrh::krylov;
+
+namespace cvrh {
+namespace krylov {
+
+struct Chebyshev {
+    cvr_handle *h = nullptr;          // borrowed
+    int32_t     degree = 0;
+    double      lmin = 0, lmax = 0, a[CVR_CHEBYSHEV_MAX_DEGREE] = {}, b[CVR_CHEBYSHEV_MAX_DEGREE] = {};
+    void       *d_zi = nullptr, *d_q = nullptr, *d_d = nullptr;          // z between the steps (x_ext values, element ncols stays 0), q = A z (y_ext), d (n)
+};
+
+}  // namespace krylov
+}  // namespace cvrh
 
 namespace {
 
@@ -100,20 +113,21 @@ __global__ __launch_bounds__(kThreads) void cheb_start_kernel(T *__restrict__ x,
 template <typename T, Mode LASTMODE, bool AL>
 int enqueue_apply(const cvr_precond *pc, const T *r, T *out, T *p, double *part, const CgCell *cell, hipStream_t st, int *spmvs)
 {
-    const long long n = pc->n;
-    T *zi = static_cast<T *>(pc->d_zi), *q = static_cast<T *>(pc->d_q), *d = static_cast<T *>(pc->d_d);
-    if (pc->degree == 1) {
-        launch(cheb_first_kernel<T, LASTMODE, AL>, st, r, d, zi, out, p, n, pc->b[0], part, cell);
+    const Chebyshev *c = pc->cheb;
+    const long long  n = pc->n;
+    T *zi = static_cast<T *>(c->d_zi), *q = static_cast<T *>(c->d_q), *d = static_cast<T *>(c->d_d);
+    if (c->degree == 1) {
+        launch(cheb_first_kernel<T, LASTMODE, AL>, st, r, d, zi, out, p, n, c->b[0], part, cell);
         HIP_TRY(hipGetLastError());
         return CVR_OK;
     }
-    launch(cheb_first_kernel<T, kInner, AL>, st, r, d, zi, out, p, n, pc->b[0], part, cell);
+    launch(cheb_first_kernel<T, kInner, AL>, st, r, d, zi, out, p, n, c->b[0], part, cell);
     HIP_TRY(hipGetLastError());
-    for (int k = 1; k < pc->degree; k++) {
-        HIP_TRY(run_spmv(pc->h, zi, q, st));
+    for (int k = 1; k < c->degree; k++) {
+        HIP_TRY(run_spmv(c->h, zi, q, st));
         if (spmvs) ++*spmvs;
-        if (k + 1 < pc->degree) launch(cheb_step_kernel<T, kInner, AL>, st, r, (const T *)q, d, zi, out, p, n, pc->a[k], pc->b[k], part, cell);
-        else launch(cheb_step_kernel<T, LASTMODE, AL>, st, r, (const T *)q, d, zi, out, p, n, pc->a[k], pc->b[k], part, cell);
+        if (k + 1 < c->degree) launch(cheb_step_kernel<T, kInner, AL>, st, r, (const T *)q, d, zi, out, p, n, c->a[k], c->b[k], part, cell);
+        else launch(cheb_step_kernel<T, LASTMODE, AL>, st, r, (const T *)q, d, zi, out, p, n, c->a[k], c->b[k], part, cell);
         HIP_TRY(hipGetLastError());
     }
     return CVR_OK;
@@ -121,28 +135,23 @@ int enqueue_apply(const cvr_precond *pc, const T *r, T *out, T *p, double *part,
 
 // ---- the object
 
-int cheb_alloc(void **out, size_t bytes, const char *what)
-{
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) return CVR_OK;
-    *out = nullptr;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_chebyshev: no device memory for %s (%zu bytes)", what, bytes);
-    return fail(CVR_ERR_HIP, "cvr_precond_chebyshev: hipMalloc of %s: %s", what, hipGetErrorString(e));
-}
-
 // the three buffers, zeroed (zi[ncols] == 0 from here on: the kernels write values 0 .. n - 1 only)
-int cheb_buffers(cvr_precond *p)
+int cheb_buffers(Chebyshev *c)
 {
-    const size_t bytes[3] = {x_ext_bytes(p->h), y_ext_bytes(p->h), vec_bytes(p->h)};
-    void       **bufs[3] = {&p->d_zi, &p->d_q, &p->d_d};
+    const size_t bytes[3] = {x_ext_bytes(c->h), y_ext_bytes(c->h), vec_bytes(c->h)};
+    void       **bufs[3] = {&c->d_zi, &c->d_q, &c->d_d};
     const char  *names[3] = {"zi", "q", "d"};
-    for (int i = 0; i < 3; i++) {
-        if (const int rc = cheb_alloc(bufs[i], bytes[i], names[i])) return rc;
-        HIP_TRY(hipMemset(*bufs[i], 0, bytes[i]));
-    }
+    for (int i = 0; i < 3; i++)
+        if (const int rc = zeroed("cvr_precond_chebyshev", bufs[i], bytes[i], names[i])) return rc;
     HIP_TRY(hipDeviceSynchronize());          // (whatever stream the first apply comes on finds them zeroed)
     return CVR_OK;
+}
+
+template <typename T>
+int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
+{
+    if (start) return enqueue_apply<T, kSolveStart, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
+    return enqueue_apply<T, kSolve, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
 }
 
 }  // namespace
@@ -158,21 +167,17 @@ int chebyshev_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st
     return with_flags([&](auto AL) { return enqueue_apply<double, kLast, AL>(p, static_cast<const double *>(r), static_cast<double *>(z), (double *)nullptr, (double *)nullptr, (const CgCell *)nullptr, st, nullptr); }, al);
 }
 
-template <typename T>
-int chebyshev_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs)
-{
-    if (start) return enqueue_apply<T, kSolveStart, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
-    return enqueue_apply<T, kSolve, true>(pc, r, z, p, part_rz, static_cast<const CgCell *>(cell), st, spmvs);
-}
-template int chebyshev_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
-template int chebyshev_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
-
 void chebyshev_release(cvr_precond *p)
 {
-    for (void *buf : {p->d_zi, p->d_q, p->d_d})
+    Chebyshev *c = p->cheb;
+    if (!c) return;
+    for (void *buf : {c->d_zi, c->d_q, c->d_d})
         if (buf) (void)hipFree(buf);
-    p->d_zi = p->d_q = p->d_d = nullptr;
+    delete c;
+    p->cheb = nullptr;
 }
+
+PrecondOps kChebyshevOps = {kPrecondChebyshev, "Chebyshev", chebyshev_apply, chebyshev_release, chebyshev_cg_apply<float>, chebyshev_cg_apply<double>};
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -190,31 +195,35 @@ int cvr_precond_chebyshev(cvr_precond **out, cvr_handle *h, int32_t degree, doub
     Range range("cvr_precond_chebyshev");
     HIP_TRY(hipSetDevice(h->device));
     cvr_precond *p = new (std::nothrow) cvr_precond;
-    if (!p) return fail(CVR_ERR_NOMEM, "out of host memory");
+    Chebyshev   *c = new (std::nothrow) Chebyshev;
+    if (!p || !c) {
+        delete p;
+        delete c;
+        return fail(CVR_ERR_NOMEM, "out of host memory");
+    }
     p->kind = kPrecondChebyshev;
+    p->ops = &kChebyshevOps;
     p->device = h->device;
     p->n = h->info.nrows;
     p->bs = 0;
     p->is_f32 = h->vsz == 4 ? 1 : 0;
-    p->h = h;
-    p->degree = degree;
-    p->lmin = lmin;
-    p->lmax = lmax;
+    p->cheb = c;
+    c->h = h;
+    c->degree = degree;
+    c->lmin = lmin;
+    c->lmax = lmax;
     // the coefficients: every operation an fp64 one of its own (the file is compiled without contraction)
     const double theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta;
     double       rho = 1 / sigma;
-    p->a[0] = 0;
-    p->b[0] = 1 / theta;
+    c->a[0] = 0;
+    c->b[0] = 1 / theta;
     for (int k = 1; k < degree; k++) {
         const double next = 1 / (2 * sigma - rho);
-        p->a[k] = next * rho;
-        p->b[k] = 2 * next / delta;
+        c->a[k] = next * rho;
+        c->b[k] = 2 * next / delta;
         rho = next;
     }
-    if (const int rc = cheb_buffers(p)) {
-        cvr_precond_destroy(p);
-        return rc;
-    }
+    if (const int rc = cheb_buffers(c)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }
@@ -222,16 +231,16 @@ int cvr_precond_chebyshev(cvr_precond **out, cvr_handle *h, int32_t degree, doub
 int cvr_precond_chebyshev_info(const cvr_precond *p, cvr_chebyshev_info *info)
 {
     if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
-    if (p->kind != kPrecondChebyshev)
-        return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev_info: the preconditioner is of kind %d (%s), not a Chebyshev object", p->kind, p->kind == kPrecondIlu0 ? "ILU(0)" : p->kind == kPrecondFsai ? "FSAI" : p->kind == kPrecondAmg ? "AMG" : "block-Jacobi");
+    if (p->kind != kPrecondChebyshev) return fail(CVR_ERR_INVALID, "cvr_precond_chebyshev_info: the preconditioner is of kind %d (%s), not a Chebyshev object", p->kind, p->ops->name);
+    const Chebyshev *c = p->cheb;
     memset(info, 0, sizeof(*info));
-    info->degree = p->degree;
+    info->degree = c->degree;
     info->is_f32 = p->is_f32;
-    info->lmin = p->lmin;
-    info->lmax = p->lmax;
-    for (int k = 0; k < p->degree; k++) {
-        info->a[k] = p->a[k];
-        info->b[k] = p->b[k];
+    info->lmin = c->lmin;
+    info->lmax = c->lmax;
+    for (int k = 0; k < c->degree; k++) {
+        info->a[k] = c->a[k];
+        info->b[k] = c->b[k];
     }
     return CVR_OK;
 }

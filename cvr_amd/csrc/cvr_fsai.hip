@@ -13,8 +13,8 @@
 //   Object: two handles of its own, (W pattern, Wa) and (W pattern, Wb) with transpose = 1, both from device arrays with the default options, and
 //     three buffers: xin (the first product's input), t (its output and the second product's input: its pad slot is zeroed behind the first product,
 //     whose dump slot it is -- what cvr_lsqr.hip does with u^), zo (the second product's output).
-//   Apply: fsai_in_kernel (xin = r) | Wa's product | Wb^T's product | fsai_out_kernel (z = zo), or inside cvr_pcg_device fsai_rz_kernel in its place
-//     (z = zo with the partial sums of r . z and, at the start, p = z; nothing behind a stop).
+//   Apply: precond_copy_in_kernel (xin = r) | Wa's product | Wb^T's product | precond_copy_out_kernel (z = zo), or inside cvr_pcg_device
+//     precond_rz_kernel in its place (z = zo with the partial sums of r . z and, at the start, p = z; nothing behind a stop): cvr_precond.h's.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
@@ -161,126 +161,9 @@ __global__ __launch_bounds__(kFsaiThreads) void fsai_factor_kernel(const int64_t
     }
 }
 
-// xin = r.  AL: r, the caller's array, is 16-byte aligned
-template <typename T, bool AL>
-__global__ __launch_bounds__(kThreads) void fsai_in_kernel(const T *__restrict__ r, T *__restrict__ xin, long long n)
-{
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T v[kPack<T>];
-        load_pack<T, AL>(r, e, (int)cnt, v);
-        store_pack<T, true>(xin, e, (int)cnt, v);
-    }
-}
-
-// z = zo.  AL: z, the caller's array, is 16-byte aligned
-template <typename T, bool AL>
-__global__ __launch_bounds__(kThreads) void fsai_out_kernel(const T *__restrict__ zo, T *__restrict__ z, long long n)
-{
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T v[kPack<T>];
-        load_pack<T, true>(zo, e, (int)cnt, v);
-        store_pack<T, AL>(z, e, (int)cnt, v);
-    }
-}
-
-// the same inside cvr_pcg_device: z = zo, the partial sums of r . z (the term double(r_i) * double(z_i) added in the thread that owns element i in
-// element order: pcg_apply_kernel's), and at the start p = z; behind a stop nothing is written
-template <typename T, bool START>
-__global__ __launch_bounds__(kThreads) void fsai_rz_kernel(const T *__restrict__ r, const T *__restrict__ zo, T *__restrict__ z, T *__restrict__ p, long long n,
-                                                           double *__restrict__ out, const CgCell *__restrict__ cell)
-{
-    __shared__ double sh[1][kWaves];
-    if constexpr (!START)
-        if (cell->stop) return;          // (no workgroup of this kernel sets it)
-    double acc[1] = {0};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T rv[kPack<T>], zv[kPack<T>];
-        load_pack<T, true>(r, e, (int)cnt, rv);
-        load_pack<T, true>(zo, e, (int)cnt, zv);
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[0] += (double)rv[j] * (double)zv[j];
-        store_pack<T, true>(z, e, (int)cnt, zv);
-        if constexpr (START) store_pack<T, true>(p, e, (int)cnt, zv);
-    }
-    store_partials<1>(acc, out, sh);
-}
-
 // ---- the host half
 
-// device memory that lives for the build only
-struct Scratch {
-    std::vector<void *> bufs;
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch()
-    {
-        for (void *p : bufs)
-            if (p) (void)hipFree(p);
-    }
-};
-
-int device_alloc(void **out, size_t bytes, const char *what)
-{
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) return CVR_OK;
-    *out = nullptr;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_fsai: no device memory for %s (%zu bytes)", what, bytes);
-    return fail(CVR_ERR_HIP, "cvr_precond_fsai: hipMalloc of %s: %s", what, hipGetErrorString(e));
-}
-int scratch_alloc(Scratch &s, void **out, size_t bytes, const char *what)
-{
-    if (const int rc = device_alloc(out, bytes, what)) return rc;
-    s.bufs.push_back(*out);
-    return CVR_OK;
-}
-
-// The view as cvr_precond_ilu0 reads it: row_ptr and col_idx on the host for the analysis (the caller's own arrays, or copies brought down once on
-// `st`, which is synchronised before anything else reads the arrays)
-struct HostCsr {
-    const int64_t       *rp = nullptr;
-    const int32_t       *ci = nullptr;
-    std::vector<int64_t> rp_own;
-    std::vector<int32_t> ci_own;
-};
-
-int stage_host(const cvr_csr_view *c, HostCsr &h, hipStream_t st)
-{
-    const int64_t n = c->nrows;
-    if (!c->arrays_on_device) {
-        if (const int rc = check_csr(c, true)) return rc;
-        h.rp = c->row_ptr;
-        h.ci = c->col_idx;
-        return CVR_OK;
-    }
-    try {
-        h.rp_own.assign((size_t)n + 1, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(CVR_ERR_NOMEM, "cvr_precond_fsai: out of host memory for row_ptr (%lld rows)", (long long)n);
-    }
-    if (n > 0) {
-        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
-        HIP_TRY(hipMemcpyAsync(h.rp_own.data(), c->row_ptr, sizeof(int64_t) * h.rp_own.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    cvr_csr_view hv = *c;
-    hv.row_ptr = h.rp_own.data();
-    if (const int rc = check_csr(&hv, false)) return rc;
-    h.rp = h.rp_own.data();
-    if (n > 0) {
-        if (const int rc = check_columns_device(c->col_idx, h.rp_own.front(), h.rp_own.back(), c->ncols)) return rc;
-        const int64_t nnz = h.rp_own.back();
-        try {
-            h.ci_own.assign((size_t)nnz, 0);
-        } catch (const std::bad_alloc &) {
-            return fail(CVR_ERR_NOMEM, "cvr_precond_fsai: out of host memory for col_idx (%lld entries)", (long long)nnz);
-        }
-        if (nnz > 0) HIP_TRY(hipMemcpy(h.ci_own.data(), c->col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
-    }
-    h.ci = h.ci_own.data();
-    return CVR_OK;
-}
+constexpr const char *kEntry = "cvr_precond_fsai";
 
 template <typename T>
 void launch_factor(const int64_t *rp, const int32_t *ci, const void *va, const int64_t *src, const int64_t *wrp, long long n, int G, void *wa, void *wb, int32_t *bad, hipStream_t st)
@@ -290,31 +173,10 @@ void launch_factor(const int64_t *rp, const int32_t *ci, const void *va, const i
     hipLaunchKernelGGL(fsai_factor_kernel<T>, dim3((unsigned)blocks), dim3(kFsaiThreads), 0, st, rp, ci, static_cast<const T *>(va), src, wrp, n, G, static_cast<T *>(wa), static_cast<T *>(wb), bad);
 }
 
-// one of the object's two handles: cvr_create + cvr_preprocess of device arrays with the default options on the object's device
-int make_handle(cvr_handle **out, int64_t n, const int64_t *d_wrp, const int32_t *d_wci, const void *d_vals, int is_f32, int device, int transpose)
-{
-    cvr_csr_view v{};
-    v.nrows = v.ncols = n;
-    v.row_ptr = d_wrp;
-    v.col_idx = d_wci;
-    v.vals = d_vals;
-    v.is_f32 = is_f32;
-    v.arrays_on_device = 1;
-    cvr_options opt;
-    cvr_default_options(&opt);
-    opt.device = device;
-    opt.transpose = transpose;
-    if (const int rc = cvr_create(out, &v, &opt)) {
-        *out = nullptr;
-        return rc;
-    }
-    return cvr_preprocess(*out, 0, nullptr);
-}
-
 int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
 {
     HostCsr h;
-    if (const int rc = stage_host(csr, h, st)) return rc;
+    if (const int rc = stage_host(kEntry, csr, h, false, st)) return rc;
     const int64_t n = p->n;
     Fsai         *f = p->fsai;
     const size_t  vsz = p->is_f32 ? 4 : 8;
@@ -337,16 +199,16 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
     if (pat.nnz >= ((int64_t)1 << 32)) return fail(CVR_ERR_INVALID, "cvr_precond_fsai: W has %lld entries: the handle of its transpose needs fewer than 2^32", (long long)pat.nnz);
 
     const int64_t nnz_a = h.rp[n];
-    if (const int rc = device_alloc(&f->d_wa, vsz * (size_t)pat.nnz, "Wa")) return rc;
-    if (const int rc = device_alloc(&f->d_wb, vsz * (size_t)pat.nnz, "Wb")) return rc;
+    if (const int rc = device_alloc(kEntry, &f->d_wa, vsz * (size_t)pat.nnz, "Wa")) return rc;
+    if (const int rc = device_alloc(kEntry, &f->d_wb, vsz * (size_t)pat.nnz, "Wb")) return rc;
     {
         Scratch     s;
         void       *d_rp = nullptr, *d_ci = nullptr, *d_va = nullptr, *d_src = nullptr, *d_wrp = nullptr, *d_wci = nullptr, *d_bad = nullptr;
         const void *rp = csr->row_ptr, *ci = csr->col_idx, *va = csr->vals;
         if (!csr->arrays_on_device) {
-            if (const int rc = scratch_alloc(s, &d_rp, sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
-            if (const int rc = scratch_alloc(s, &d_ci, sizeof(int32_t) * (size_t)nnz_a, "col_idx")) return rc;
-            if (const int rc = scratch_alloc(s, &d_va, vsz * (size_t)nnz_a, "vals")) return rc;
+            if (const int rc = scratch_alloc(kEntry, s, &d_rp, sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
+            if (const int rc = scratch_alloc(kEntry, s, &d_ci, sizeof(int32_t) * (size_t)nnz_a, "col_idx")) return rc;
+            if (const int rc = scratch_alloc(kEntry, s, &d_va, vsz * (size_t)nnz_a, "vals")) return rc;
             HIP_TRY(hipMemcpyAsync(d_rp, csr->row_ptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_ci, csr->col_idx, sizeof(int32_t) * (size_t)nnz_a, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemcpyAsync(d_va, csr->vals, vsz * (size_t)nnz_a, hipMemcpyHostToDevice, st));
@@ -354,10 +216,10 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
             ci = d_ci;
             va = d_va;
         }
-        if (const int rc = scratch_alloc(s, &d_src, sizeof(int64_t) * (size_t)n, "the rows' first entries")) return rc;
-        if (const int rc = scratch_alloc(s, &d_wrp, sizeof(int64_t) * (size_t)(n + 1), "W's row_ptr")) return rc;
-        if (const int rc = scratch_alloc(s, &d_wci, sizeof(int32_t) * (size_t)pat.nnz, "W's col_idx")) return rc;
-        if (const int rc = scratch_alloc(s, &d_bad, sizeof(int32_t), "the pivot word")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_src, sizeof(int64_t) * (size_t)n, "the rows' first entries")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_wrp, sizeof(int64_t) * (size_t)(n + 1), "W's row_ptr")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_wci, sizeof(int32_t) * (size_t)pat.nnz, "W's col_idx")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_bad, sizeof(int32_t), "the pivot word")) return rc;
         int32_t bad = kNoRow;
         HIP_TRY(hipMemcpyAsync(d_src, src.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_wrp, f->wrp.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, st));
@@ -377,18 +239,24 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
         HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));          // (the staged copies are released behind this; the handles below read W on their own streams)
         if (bad != kNoRow) return fail(CVR_ERR_STATE, "cvr_precond_fsai: the pivot of row %d is not finite or not > 0", bad);
-        if (const int rc = make_handle(&f->ha, n, static_cast<const int64_t *>(d_wrp), static_cast<const int32_t *>(d_wci), f->d_wa, p->is_f32, p->device, 0)) return rc;
-        if (const int rc = make_handle(&f->hb, n, static_cast<const int64_t *>(d_wrp), static_cast<const int32_t *>(d_wci), f->d_wb, p->is_f32, p->device, 1)) return rc;
+        cvr_csr_view w{};          // the object's two handles: (W pattern, Wa), and (W pattern, Wb) transposed
+        w.nrows = w.ncols = n;
+        w.row_ptr = static_cast<const int64_t *>(d_wrp);
+        w.col_idx = static_cast<const int32_t *>(d_wci);
+        w.vals = f->d_wa;
+        w.is_f32 = p->is_f32;
+        w.arrays_on_device = 1;
+        if (const int rc = make_handle(&f->ha, w, p->device, 0)) return rc;
+        w.vals = f->d_wb;
+        if (const int rc = make_handle(&f->hb, w, p->device, 1)) return rc;
         HIP_TRY(hipDeviceSynchronize());          // (the handles' copies of W are complete before the scratch goes)
     }
     // the three buffers, zeroed: xin[n] and t[n] are pad slots of an SpMV input
     const size_t bytes[3] = {x_ext_bytes(f->ha), vsz * (size_t)std::max<int64_t>({f->ha->info.yext_elems, f->hb->info.x_elems, n + 1}), y_ext_bytes(f->hb)};
     void       **bufs[3] = {&f->d_xin, &f->d_t, &f->d_zo};
     const char  *names[3] = {"xin", "t", "zo"};
-    for (int i = 0; i < 3; i++) {
-        if (const int rc = device_alloc(bufs[i], bytes[i], names[i])) return rc;
-        HIP_TRY(hipMemset(*bufs[i], 0, bytes[i]));
-    }
+    for (int i = 0; i < 3; i++)
+        if (const int rc = zeroed(kEntry, bufs[i], bytes[i], names[i])) return rc;
     HIP_TRY(hipDeviceSynchronize());          // (whatever stream the first apply comes on finds them zeroed)
     return CVR_OK;
 }
@@ -399,18 +267,13 @@ int enqueue_products(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
 {
     const Fsai     *f = pc->fsai;
     const long long n = pc->n;
-    with_flags([&](auto AL) { launch(fsai_in_kernel<T, AL>, st, r, static_cast<T *>(f->d_xin), n); }, al);
+    with_flags([&](auto AL) { launch(precond_copy_in_kernel<T, AL>, st, r, static_cast<T *>(f->d_xin), n); }, al);
     HIP_TRY(hipGetLastError());
     HIP_TRY(run_spmv(f->ha, f->d_xin, f->d_t, st));
     if (const int rc = zero_pad_slot(f->d_t, sizeof(T) * (size_t)n, sizeof(T), st)) return rc;          // (the product's dump slot is the next one's pad slot)
     HIP_TRY(run_spmv(f->hb, f->d_t, f->d_zo, st));
     return CVR_OK;
 }
-
-}  // namespace
-
-namespace cvrh {
-namespace krylov {
 
 int fsai_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
 {
@@ -420,10 +283,10 @@ int fsai_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
     const long long n = p->n;
     if (p->is_f32) {
         if (const int rc = enqueue_products<float>(p, static_cast<const float *>(r), ral, st)) return rc;
-        with_flags([&](auto AL) { launch(fsai_out_kernel<float, AL>, st, static_cast<const float *>(f->d_zo), static_cast<float *>(z), n); }, zal);
+        with_flags([&](auto AL) { launch(precond_copy_out_kernel<float, AL>, st, static_cast<const float *>(f->d_zo), static_cast<float *>(z), n); }, zal);
     } else {
         if (const int rc = enqueue_products<double>(p, static_cast<const double *>(r), ral, st)) return rc;
-        with_flags([&](auto AL) { launch(fsai_out_kernel<double, AL>, st, static_cast<const double *>(f->d_zo), static_cast<double *>(z), n); }, zal);
+        with_flags([&](auto AL) { launch(precond_copy_out_kernel<double, AL>, st, static_cast<const double *>(f->d_zo), static_cast<double *>(z), n); }, zal);
     }
     HIP_TRY(hipGetLastError());
     return CVR_OK;
@@ -436,13 +299,10 @@ int fsai_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz
     if (!f || pc->n == 0) return CVR_OK;
     if (const int rc = enqueue_products<T>(pc, r, true, st)) return rc;
     if (spmvs) *spmvs += 2;
-    with_flags([&](auto START) { launch(fsai_rz_kernel<T, START>, st, r, static_cast<const T *>(f->d_zo), z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
+    with_flags([&](auto START) { launch(precond_rz_kernel<T, START, true>, st, r, static_cast<const T *>(f->d_zo), z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
-template int fsai_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
-template int fsai_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
-
 void fsai_release(cvr_precond *p)
 {
     Fsai *f = p->fsai;
@@ -454,6 +314,13 @@ void fsai_release(cvr_precond *p)
     delete f;
     p->fsai = nullptr;
 }
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+PrecondOps kFsaiOps = {kPrecondFsai, "FSAI", fsai_apply_any, fsai_release, fsai_cg_apply<float>, fsai_cg_apply<double>};
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -478,19 +345,13 @@ int cvr_precond_fsai(cvr_precond **out, const cvr_csr_view *csr, int32_t device,
         return fail(CVR_ERR_NOMEM, "out of host memory");
     }
     p->kind = kPrecondFsai;
+    p->ops = &kFsaiOps;
     p->device = device;
     p->n = csr->nrows;
     p->bs = 0;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->fsai = f;
-    if (const int rc = build(p, csr, (hipStream_t)stream)) {
-        char keep[sizeof(g_err)];          // (cvr_destroy of a half-made handle must not replace the message)
-        memcpy(keep, g_err, sizeof(keep));
-        cvr_precond_destroy(p);
-        memcpy(g_err, keep, sizeof(keep));
-        (void)hipSetDevice(device);
-        return rc;
-    }
+    if (const int rc = build(p, csr, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }

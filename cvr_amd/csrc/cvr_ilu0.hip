@@ -199,27 +199,6 @@ __global__ __launch_bounds__(kThreads) void round_kernel(const double *__restric
     for (long long q = (long long)blockIdx.x * kThreads + threadIdx.x; q < nnz; q += (long long)kBlocks * kThreads) f[q] = (T)a[q];
 }
 
-// behind the sweeps inside cvr_pcg_device: the partial sums of r . z, the term double(r_i) * double(z_i) added in the thread that owns element i in
-// element order (pcg_apply_kernel's), and at the start p = z; behind a stop nothing is written
-template <typename T, bool START>
-__global__ __launch_bounds__(kThreads) void ilu0_rz_kernel(const T *__restrict__ r, const T *__restrict__ z, T *__restrict__ p, long long n, double *__restrict__ out,
-                                                           const CgCell *__restrict__ cell)
-{
-    __shared__ double sh[1][kWaves];
-    if constexpr (!START)
-        if (cell->stop) return;          // (no workgroup of this kernel sets it)
-    double acc[1] = {0};
-    CVR_KRYLOV_PACKETS(T, e, cnt) {
-        T rv[kPack<T>], zv[kPack<T>];
-        load_pack<T, true>(r, e, (int)cnt, rv);
-        load_pack<T, true>(z, e, (int)cnt, zv);
-#pragma unroll
-        for (int j = 0; j < kPack<T>; j++) if (j < cnt) acc[0] += (double)rv[j] * (double)zv[j];
-        if constexpr (START) store_pack<T, true>(p, e, (int)cnt, zv);
-    }
-    store_partials<1>(acc, out, sh);
-}
-
 // GMRES's x from M^-1 u, behind the sweeps and under their gate: x_i = T(double(x_i) + double(zu_i)).  AL: x, the caller's array, is 16-byte aligned.
 template <typename T, bool AL>
 __global__ __launch_bounds__(kThreads) void ilu0_xadd_kernel(T *__restrict__ x, const T *__restrict__ zu, long long n, Ilu0Gate gate)
@@ -318,34 +297,7 @@ int32_t lanes_of(int64_t n, int64_t nnz)
     return G;
 }
 
-// device memory that lives for the build only
-struct Scratch {
-    std::vector<void *> bufs;
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch()
-    {
-        for (void *p : bufs)
-            if (p) (void)hipFree(p);
-    }
-};
-
-int device_alloc(void **out, size_t bytes, const char *what)
-{
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) return CVR_OK;
-    *out = nullptr;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_ilu0: no device memory for %s (%zu bytes)", what, bytes);
-    return fail(CVR_ERR_HIP, "cvr_precond_ilu0: hipMalloc of %s: %s", what, hipGetErrorString(e));
-}
-int scratch_alloc(Scratch &s, void **out, size_t bytes, const char *what)
-{
-    if (const int rc = device_alloc(out, bytes, what)) return rc;
-    s.bufs.push_back(*out);
-    return CVR_OK;
-}
+constexpr const char *kEntry = "cvr_precond_ilu0";
 
 int upload_sweep(int64_t n, const int64_t *rp, const int64_t *dpos, const std::vector<int32_t> &order, const std::vector<int32_t> &lptr, bool upper, Ilu0Sweep &sw, hipStream_t st,
                  std::vector<Ilu0Slot> &slots)
@@ -356,8 +308,8 @@ int upload_sweep(int64_t n, const int64_t *rp, const int64_t *dpos, const std::v
         if (upper) slots[(size_t)k] = {dpos[i] + 1, (int32_t)(rp[i + 1] - dpos[i] - 1), i};
         else slots[(size_t)k] = {rp[i], (int32_t)(dpos[i] - rp[i]), i};
     }
-    if (const int rc = device_alloc(reinterpret_cast<void **>(&sw.d_slots), sizeof(Ilu0Slot) * (size_t)n, "a sweep's rows")) return rc;
-    if (const int rc = device_alloc(reinterpret_cast<void **>(&sw.d_lptr), sizeof(int32_t) * lptr.size(), "a sweep's levels")) return rc;
+    if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&sw.d_slots), sizeof(Ilu0Slot) * (size_t)n, "a sweep's rows")) return rc;
+    if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&sw.d_lptr), sizeof(int32_t) * lptr.size(), "a sweep's levels")) return rc;
     HIP_TRY(hipMemcpyAsync(sw.d_slots, slots.data(), sizeof(Ilu0Slot) * (size_t)n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(sw.d_lptr, lptr.data(), sizeof(int32_t) * lptr.size(), hipMemcpyHostToDevice, st));
     return CVR_OK;
@@ -381,56 +333,10 @@ int factorise(const cvr_precond *p, const void *va_dev, const int64_t *d_rp, con
     return CVR_OK;
 }
 
-// The view as cvr_precond_block_jacobi reads it, row_ptr and col_idx on the host for the analysis (the caller's own arrays, or copies brought down
-// once on `st`, which is synchronised before anything else reads the arrays)
-struct HostCsr {
-    const int64_t       *rp = nullptr;
-    const int32_t       *ci = nullptr;
-    std::vector<int64_t> rp_own;
-    std::vector<int32_t> ci_own;
-};
-
-int stage_host(const cvr_csr_view *c, HostCsr &h, hipStream_t st)
-{
-    const int64_t n = c->nrows;
-    if (!c->arrays_on_device) {
-        if (const int rc = check_csr(c, true)) return rc;
-        h.rp = c->row_ptr;
-        h.ci = c->col_idx;
-        return CVR_OK;
-    }
-    try {
-        h.rp_own.assign((size_t)n + 1, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(CVR_ERR_NOMEM, "cvr_precond_ilu0: out of host memory for row_ptr (%lld rows)", (long long)n);
-    }
-    if (n > 0) {
-        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
-        HIP_TRY(hipMemcpyAsync(h.rp_own.data(), c->row_ptr, sizeof(int64_t) * h.rp_own.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    cvr_csr_view hv = *c;
-    hv.row_ptr = h.rp_own.data();
-    if (const int rc = check_csr(&hv, false)) return rc;
-    h.rp = h.rp_own.data();
-    if (n > 0) {
-        if (const int rc = check_columns_device(c->col_idx, h.rp_own.front(), h.rp_own.back(), c->ncols)) return rc;
-        const int64_t nnz = h.rp_own.back();
-        try {
-            h.ci_own.assign((size_t)nnz, 0);
-        } catch (const std::bad_alloc &) {
-            return fail(CVR_ERR_NOMEM, "cvr_precond_ilu0: out of host memory for col_idx (%lld entries)", (long long)nnz);
-        }
-        if (nnz > 0) HIP_TRY(hipMemcpy(h.ci_own.data(), c->col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
-    }
-    h.ci = h.ci_own.data();
-    return CVR_OK;
-}
-
 int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
 {
     HostCsr h;
-    if (const int rc = stage_host(csr, h, st)) return rc;
+    if (const int rc = stage_host(kEntry, csr, h, false, st)) return rc;
     const int64_t n = p->n;
     if (n == 0) return CVR_OK;
     Ilu0         *u = p->ilu;
@@ -465,18 +371,18 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
         return fail(CVR_ERR_NOMEM, "cvr_precond_ilu0: out of host memory for the analysis (%lld rows)", (long long)n);
     }
 
-    if (const int rc = device_alloc(reinterpret_cast<void **>(&u->d_ci), sizeof(int32_t) * (size_t)nnz, "col_idx")) return rc;
-    if (const int rc = device_alloc(&u->d_f, vsz * (size_t)nnz, "the factors")) return rc;
-    if (const int rc = device_alloc(&u->d_y, vsz * (size_t)n, "y")) return rc;
+    if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&u->d_ci), sizeof(int32_t) * (size_t)nnz, "col_idx")) return rc;
+    if (const int rc = device_alloc(kEntry, &u->d_f, vsz * (size_t)nnz, "the factors")) return rc;
+    if (const int rc = device_alloc(kEntry, &u->d_y, vsz * (size_t)n, "y")) return rc;
     Scratch s;
     void   *d_rp = nullptr, *d_dpos = nullptr, *d_a = nullptr, *d_bad = nullptr, *d_va = nullptr;
-    if (const int rc = scratch_alloc(s, &d_rp, sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
-    if (const int rc = scratch_alloc(s, &d_dpos, sizeof(int64_t) * (size_t)n, "the diagonal's positions")) return rc;
-    if (const int rc = scratch_alloc(s, &d_a, sizeof(double) * (size_t)nnz, "the fp64 copy")) return rc;
-    if (const int rc = scratch_alloc(s, &d_bad, sizeof(int32_t), "the pivot word")) return rc;
+    if (const int rc = scratch_alloc(kEntry, s, &d_rp, sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
+    if (const int rc = scratch_alloc(kEntry, s, &d_dpos, sizeof(int64_t) * (size_t)n, "the diagonal's positions")) return rc;
+    if (const int rc = scratch_alloc(kEntry, s, &d_a, sizeof(double) * (size_t)nnz, "the fp64 copy")) return rc;
+    if (const int rc = scratch_alloc(kEntry, s, &d_bad, sizeof(int32_t), "the pivot word")) return rc;
     const void *va = csr->vals;
     if (!csr->arrays_on_device) {
-        if (const int rc = scratch_alloc(s, &d_va, vsz * (size_t)nnz, "vals")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_va, vsz * (size_t)nnz, "vals")) return rc;
         HIP_TRY(hipMemcpyAsync(d_va, csr->vals, vsz * (size_t)nnz, hipMemcpyHostToDevice, st));
         va = d_va;
     }
@@ -526,14 +432,17 @@ int ilu0_add_to_x(T *x, const T *zu, long long n, const Ilu0Gate &gate, bool al,
 template int ilu0_add_to_x<float>(float *, const float *, long long, const Ilu0Gate &, bool, hipStream_t);
 template int ilu0_add_to_x<double>(double *, const double *, long long, const Ilu0Gate &, bool, hipStream_t);
 
-int ilu0_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
+namespace {
+
+int ilu0_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)          // by the object's type, no gate
 {
     if (p->is_f32) return ilu0_apply<float, float>(p, static_cast<const float *>(r), static_cast<float *>(z), Ilu0Gate{}, st);
     return ilu0_apply<double, double>(p, static_cast<const double *>(r), static_cast<double *>(z), Ilu0Gate{}, st);
 }
 
+// the sweeps into z, then one kernel on the solvers' grid with the partial sums and, at the start, p = z
 template <typename T>
-int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st)
+int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *)
 {
     const CgCell *c = static_cast<const CgCell *>(cell);
     Ilu0Gate      gate;
@@ -542,12 +451,10 @@ int ilu0_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz
         gate.nstop = 1;
     }
     if (const int rc = ilu0_apply<T, T>(pc, r, z, gate, st)) return rc;
-    with_flags([&](auto START) { launch(ilu0_rz_kernel<T, START>, st, r, (const T *)z, p, (long long)pc->n, part_rz, c); }, start);
+    with_flags([&](auto START) { launch(precond_rz_kernel<T, START, false>, st, r, (const T *)z, (T *)nullptr, p, (long long)pc->n, part_rz, c); }, start);
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
-template int ilu0_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t);
-template int ilu0_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t);
 
 void ilu0_release(cvr_precond *p)
 {
@@ -558,6 +465,10 @@ void ilu0_release(cvr_precond *p)
     delete u;
     p->ilu = nullptr;
 }
+
+}  // namespace
+
+PrecondOps kIlu0Ops = {kPrecondIlu0, "ILU(0)", ilu0_apply_any, ilu0_release, ilu0_cg_apply<float>, ilu0_cg_apply<double>};
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -582,6 +493,7 @@ int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device,
         return fail(CVR_ERR_NOMEM, "out of host memory");
     }
     p->kind = kPrecondIlu0;
+    p->ops = &kIlu0Ops;
     p->device = device;
     p->n = csr->nrows;
     p->bs = 0;
@@ -589,10 +501,7 @@ int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device,
     p->ilu = u;
     u->G = 1;
     u->wide = kDefaultWide;
-    if (const int rc = build(p, csr, (hipStream_t)stream)) {
-        cvr_precond_destroy(p);
-        return rc;
-    }
+    if (const int rc = build(p, csr, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }

@@ -104,6 +104,22 @@ __device__ __forceinline__ void store_partials(double (&acc)[K], double *__restr
     for (long long e = ((long long)blockIdx.x * kThreads + threadIdx.x) * kPack<T>, cnt = 0; e < n && ((cnt = n - e < kPack<T> ? n - e : kPack<T>), true); \
          e += (long long)kBlocks * kThreads * kPack<T>)
 
+// The state cell of conjugate gradients (cvr_cg.hip; batched CG keeps one per column), here because the preconditioners' applies inside the solver
+// read it (cvr_precond.h).  Written by thread 0 of workgroup 0 only; a value a kernel reads is one that a kernel BEFORE it wrote (r.z of the step
+// before sits in rz[k & 1], this step's goes to rz[(k + 1) & 1]) -- except `stop`, which the other workgroups of the kernel that sets it may or may
+// not see yet: they come to the same decision from the same sums, so either way they return without writing.
+namespace {
+struct CgCell {
+    double  bb, bnorm;         // b . b and its root
+    double  rr, rnorm;         // r . r of the last iterate and its root
+    double  rz[2];
+    int32_t stop;              // != 0: no kernel writes a vector any more
+    int32_t status;            // CVR_CG_*
+    int32_t iters;             // steps applied to x
+    int32_t zero_x;            // b == 0: the solution is x = 0 (the host clears it)
+};
+}  // namespace
+
 // ---- the host half
 
 // what the solvers' entry points check before any device work and before the handle is looked at

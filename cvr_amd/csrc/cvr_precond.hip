@@ -1,12 +1,13 @@
-// cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*); the entry points all kinds of object share hand the
-// Chebyshev kind on to cvr_chebyshev.hip, the ILU(0) kind on to cvr_ilu0.hip, the FSAI kind on to cvr_fsai.hip and the AMG kind on to cvr_amg.hip (apply, destroy).  The object is built once from a CSR view -- one kernel gathers the diagonal blocks into
+// cvr_precond.hip -- the block-Jacobi preconditioner (include/cvr_amd.h: cvr_precond_*), the entry points all kinds of object share (apply and
+// destroy: they call the kind's table, cvr_precond.h's PrecondOps) and the helpers every kind's constructor builds with.  The object is built once
+// from a CSR view -- one kernel gathers the diagonal blocks into
 // LDS, inverts them there in fp64 and stores the inverses W in the matrix's type -- and applied by a kernel on the solvers' grid: thread g forms z for
 // the elements CVR_KRYLOV_PACKETS gives it (cvr_precond.h: the struct and the apply of one packet, shared with cvr_bicgstab.hip and cvr_gmres.hip).
 //   precond_build_kernel   one wavefront per workgroup; L = 8, 16 or 32 lanes per block (the power of two from bs up), 64 / L blocks per wavefront
 //   precond_apply_kernel   z = W r
 //   pcg_apply_kernel       the same inside the solver, with the partial sums of r . z (set 1 of cg_direction_kernel<T, true>) and, at the start, p = z
 // W lies block after block, each block TRANSPOSED (element (i, j) at j * bs + i): for a fixed j the threads that own neighbouring rows load neighbouring
-// values.  The solver is cvr_cg.hip's cg_solve, which enqueues pcg_apply_kernel through block_jacobi_cg_apply (cvr_precond.h); this file launches no
+// values.  The solver is cvr_cg.hip's cg_solve, which enqueues pcg_apply_kernel through kBlockJacobiOps' cg_apply (cvr_precond.h); this file launches no
 // cg_* kernel and holds no solve loop (cvr_cg_kernels.h is included for the state cell the apply reads).
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
@@ -205,15 +206,7 @@ struct DeviceCsr {
     }
 };
 
-int device_alloc(void **out, size_t bytes, const char *what)
-{
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) return CVR_OK;
-    *out = nullptr;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "cvr_precond_block_jacobi: no device memory for %s (%zu bytes)", what, bytes);
-    return fail(CVR_ERR_HIP, "cvr_precond_block_jacobi: hipMalloc of %s: %s", what, hipGetErrorString(e));
-}
+constexpr const char *kEntry = "cvr_precond_block_jacobi";
 
 // checks the view as cvr_create does and leaves its arrays on the device
 int stage_csr(const cvr_csr_view *c, DeviceCsr &d, hipStream_t st)
@@ -224,9 +217,9 @@ int stage_csr(const cvr_csr_view *c, DeviceCsr &d, hipStream_t st)
         if (const int rc = check_csr(c, true)) return rc;
         if (n == 0) return CVR_OK;
         const int64_t nnz = c->row_ptr[n];
-        if (const int rc = device_alloc(&d.owned[0], sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
-        if (const int rc = device_alloc(&d.owned[1], sizeof(int32_t) * (size_t)nnz, "col_idx")) return rc;
-        if (const int rc = device_alloc(&d.owned[2], vsz * (size_t)nnz, "vals")) return rc;
+        if (const int rc = device_alloc(kEntry, &d.owned[0], sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
+        if (const int rc = device_alloc(kEntry, &d.owned[1], sizeof(int32_t) * (size_t)nnz, "col_idx")) return rc;
+        if (const int rc = device_alloc(kEntry, &d.owned[2], vsz * (size_t)nnz, "vals")) return rc;
         HIP_TRY(hipMemcpyAsync(d.owned[0], c->row_ptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, st));
         if (nnz > 0) {
             HIP_TRY(hipMemcpyAsync(d.owned[1], c->col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st));
@@ -237,24 +230,8 @@ int stage_csr(const cvr_csr_view *c, DeviceCsr &d, hipStream_t st)
         d.va = d.owned[2];
         return CVR_OK;
     }
-    // device arrays: the row pointers come to the host once for the checks (8 bytes per row), the columns are checked where they lie
-    // (copied on `st` and waited for: what the caller enqueued on that stream to produce the arrays is complete before anything reads them)
-    std::vector<int64_t> rp_host;
-    try {
-        rp_host.assign((size_t)n + 1, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(CVR_ERR_NOMEM, "cvr_precond_block_jacobi: out of host memory for row_ptr (%lld rows)", (long long)n);
-    }
-    if (n > 0) {
-        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
-        HIP_TRY(hipMemcpyAsync(rp_host.data(), c->row_ptr, sizeof(int64_t) * rp_host.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    cvr_csr_view hv = *c;
-    hv.row_ptr = rp_host.data();
-    if (const int rc = check_csr(&hv, false)) return rc;
-    if (n > 0)
-        if (const int rc = check_columns_device(c->col_idx, rp_host.front(), rp_host.back(), c->ncols)) return rc;
+    std::vector<int64_t> rp_host;          // (8 bytes per row, for the checks only)
+    if (const int rc = check_device_view(kEntry, c, rp_host, st)) return rc;
     d.rp = c->row_ptr;
     d.ci = c->col_idx;
     d.va = c->vals;
@@ -277,9 +254,9 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
     if (const int rc = stage_csr(csr, d, st)) return rc;
     if (p->nblocks == 0) return CVR_OK;
     const size_t vsz = p->is_f32 ? 4 : 8;
-    if (const int rc = device_alloc(&p->d_w, vsz * (size_t)p->nblocks * (size_t)p->bs * (size_t)p->bs, "the inverse blocks")) return rc;
+    if (const int rc = device_alloc(kEntry, &p->d_w, vsz * (size_t)p->nblocks * (size_t)p->bs * (size_t)p->bs, "the inverse blocks")) return rc;
     void *count = nullptr;
-    if (const int rc = device_alloc(&count, sizeof(unsigned long long), "the counter")) return rc;
+    if (const int rc = device_alloc(kEntry, &count, sizeof(unsigned long long), "the counter")) return rc;
     unsigned long long bad = 0;
     hipError_t         e = hipMemsetAsync(count, 0, sizeof(bad), st);
     if (e == hipSuccess) e = p->is_f32 ? launch_build<float>(d, p, static_cast<unsigned long long *>(count), st) : launch_build<double>(d, p, static_cast<unsigned long long *>(count), st);
@@ -291,20 +268,150 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
     return CVR_OK;
 }
 
-}  // namespace
+// ---- kBlockJacobiOps
 
-namespace cvrh {
-namespace krylov {
+int block_jacobi_apply(const cvr_precond *p, const void *r, void *z, hipStream_t st)
+{
+    const bool      al = ((uintptr_t)z & 15u) == 0;
+    const long long n = p->n;
+    if (p->is_f32)
+        with_flags([&](auto AL) { launch(precond_apply_kernel<float, AL>, st, static_cast<const float *>(p->d_w), (int)p->bs, static_cast<const float *>(r), static_cast<float *>(z), n); }, al);
+    else
+        with_flags([&](auto AL) { launch(precond_apply_kernel<double, AL>, st, static_cast<const double *>(p->d_w), (int)p->bs, static_cast<const double *>(r), static_cast<double *>(z), n); }, al);
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+
+void block_jacobi_release(cvr_precond *p)
+{
+    if (p->d_w) (void)hipFree(p->d_w);
+    p->d_w = nullptr;
+}
 
 template <typename T>
-int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st)
+int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *)
 {
     with_flags([&](auto START) { launch(pcg_apply_kernel<T, START>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, r, z, p, (long long)pc->n, part_rz, static_cast<const CgCell *>(cell)); }, start);
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
-template int block_jacobi_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t);
-template int block_jacobi_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t);
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
+
+PrecondOps kBlockJacobiOps = {kPrecondBlockJacobi, "block-Jacobi", block_jacobi_apply, block_jacobi_release, block_jacobi_cg_apply<float>, block_jacobi_cg_apply<double>};
+
+// ---- the constructors' helpers (cvr_precond.h)
+
+int device_alloc(const char *entry, void **out, size_t bytes, const char *what)
+{
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+    if (e == hipSuccess) return CVR_OK;
+    *out = nullptr;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return fail(CVR_ERR_NOMEM, "%s: no device memory for %s (%zu bytes)", entry, what, bytes);
+    return fail(CVR_ERR_HIP, "%s: hipMalloc of %s: %s", entry, what, hipGetErrorString(e));
+}
+
+int upload(const char *entry, void **out, const void *src, size_t bytes, const char *what)
+{
+    if (const int rc = device_alloc(entry, out, bytes, what)) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    return CVR_OK;
+}
+
+int zeroed(const char *entry, void **out, size_t bytes, const char *what)
+{
+    if (const int rc = device_alloc(entry, out, bytes, what)) return rc;
+    HIP_TRY(hipMemset(*out, 0, bytes ? bytes : 1));
+    return CVR_OK;
+}
+
+int scratch_alloc(const char *entry, Scratch &s, void **out, size_t bytes, const char *what)
+{
+    if (const int rc = device_alloc(entry, out, bytes, what)) return rc;
+    s.bufs.push_back(*out);
+    return CVR_OK;
+}
+
+int check_device_view(const char *entry, const cvr_csr_view *c, std::vector<int64_t> &rp_host, hipStream_t st)
+{
+    const int64_t n = c->nrows;
+    try {
+        rp_host.assign((size_t)n + 1, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "%s: out of host memory for row_ptr (%lld rows)", entry, (long long)n);
+    }
+    if (n > 0) {
+        if (!c->row_ptr) return fail(CVR_ERR_INVALID, "row_ptr is null");
+        HIP_TRY(hipMemcpyAsync(rp_host.data(), c->row_ptr, sizeof(int64_t) * rp_host.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    cvr_csr_view hv = *c;
+    hv.row_ptr = rp_host.data();
+    if (const int rc = check_csr(&hv, false)) return rc;
+    if (n > 0) return check_columns_device(c->col_idx, rp_host.front(), rp_host.back(), c->ncols);
+    return CVR_OK;
+}
+
+int stage_host(const char *entry, const cvr_csr_view *c, HostCsr &h, bool with_values, hipStream_t st)
+{
+    const int64_t n = c->nrows;
+    if (!c->arrays_on_device) {
+        if (const int rc = check_csr(c, true)) return rc;
+        h.rp = c->row_ptr;
+        h.ci = c->col_idx;
+        h.va = c->vals;
+        return CVR_OK;
+    }
+    if (const int rc = check_device_view(entry, c, h.rp_own, st)) return rc;
+    h.rp = h.rp_own.data();
+    if (n > 0) {
+        const int64_t j1 = h.rp_own.back(), j0 = with_values ? h.rp_own.front() : 0, nnz = j1 - j0;
+        const size_t  vsz = c->is_f32 ? 4 : 8;
+        try {
+            h.ci_own.assign((size_t)j1, 0);
+            if (with_values) h.va_own.assign(vsz * (size_t)j1, 0);
+        } catch (const std::bad_alloc &) {
+            return fail(CVR_ERR_NOMEM, "%s: out of host memory for %s (%lld entries)", entry, with_values ? "col_idx and vals" : "col_idx", (long long)nnz);
+        }
+        if (nnz > 0) {
+            if (with_values && !c->vals) return fail(CVR_ERR_INVALID, "vals is null");
+            HIP_TRY(hipMemcpy(h.ci_own.data() + j0, c->col_idx + j0, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost));
+            if (with_values)
+                HIP_TRY(hipMemcpy(h.va_own.data() + vsz * (size_t)j0, static_cast<const uint8_t *>(c->vals) + vsz * (size_t)j0, vsz * (size_t)nnz, hipMemcpyDeviceToHost));
+        }
+    }
+    h.ci = h.ci_own.data();
+    if (with_values) h.va = h.va_own.data();
+    return CVR_OK;
+}
+
+int make_handle(cvr_handle **out, const cvr_csr_view &device_view, int device, int transpose)
+{
+    cvr_options opt;
+    cvr_default_options(&opt);
+    opt.device = device;
+    opt.transpose = transpose;
+    if (const int rc = cvr_create(out, &device_view, &opt)) {
+        *out = nullptr;
+        return rc;
+    }
+    return cvr_preprocess(*out, 0, nullptr);
+}
+
+int abandon(cvr_precond *p, int rc)
+{
+    const int device = p->device;
+    char      keep[sizeof(g_err)];
+    memcpy(keep, g_err, sizeof(keep));
+    cvr_precond_destroy(p);
+    memcpy(g_err, keep, sizeof(keep));
+    (void)hipSetDevice(device);
+    return rc;
+}
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -323,15 +430,13 @@ int cvr_precond_block_jacobi(cvr_precond **out, const cvr_csr_view *csr, int32_t
     HIP_TRY(hipSetDevice(device));
     cvr_precond *p = new (std::nothrow) cvr_precond;
     if (!p) return fail(CVR_ERR_NOMEM, "out of host memory");
+    p->ops = &kBlockJacobiOps;
     p->device = device;
     p->n = csr->nrows;
     p->bs = block_size;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->nblocks = (csr->nrows + block_size - 1) / block_size;
-    if (const int rc = build(p, csr, (hipStream_t)stream)) {
-        cvr_precond_destroy(p);
-        return rc;
-    }
+    if (const int rc = build(p, csr, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }
@@ -376,44 +481,14 @@ int cvr_precond_apply_device(const cvr_precond *p, const void *r_dev, void *z_de
     if (r_dev == z_dev) return fail(CVR_ERR_INVALID, "cvr_precond_apply_device: r and z are the same array");
     if (p->n == 0) return CVR_OK;
     HIP_TRY(hipSetDevice(p->device));
-    const hipStream_t st = (hipStream_t)stream;
-    if (p->kind == kPrecondChebyshev) return chebyshev_apply(p, r_dev, z_dev, st);
-    if (p->kind == kPrecondIlu0) return ilu0_apply_any(p, r_dev, z_dev, st);
-    if (p->kind == kPrecondFsai) return fsai_apply_any(p, r_dev, z_dev, st);
-    if (p->kind == kPrecondAmg) return amg_apply_any(p, r_dev, z_dev, st);
-    const bool        al = ((uintptr_t)z_dev & 15u) == 0;
-    const long long   n = p->n;
-    if (p->is_f32)
-        with_flags([&](auto AL) { launch(precond_apply_kernel<float, AL>, st, static_cast<const float *>(p->d_w), (int)p->bs, static_cast<const float *>(r_dev), static_cast<float *>(z_dev), n); }, al);
-    else
-        with_flags([&](auto AL) { launch(precond_apply_kernel<double, AL>, st, static_cast<const double *>(p->d_w), (int)p->bs, static_cast<const double *>(r_dev), static_cast<double *>(z_dev), n); }, al);
-    HIP_TRY(hipGetLastError());
-    return CVR_OK;
+    return p->ops->apply(p, r_dev, z_dev, (hipStream_t)stream);
 }
 
 int cvr_precond_destroy(cvr_precond *p)
 {
     if (!p) return CVR_OK;
-    if (p->d_w) {
-        (void)hipSetDevice(p->device);
-        (void)hipFree(p->d_w);
-    }
-    if (p->kind == kPrecondChebyshev && (p->d_zi || p->d_q || p->d_d)) {
-        (void)hipSetDevice(p->device);
-        chebyshev_release(p);
-    }
-    if (p->ilu) {
-        (void)hipSetDevice(p->device);
-        ilu0_release(p);
-    }
-    if (p->fsai) {
-        (void)hipSetDevice(p->device);
-        fsai_release(p);
-    }
-    if (p->amg) {
-        (void)hipSetDevice(p->device);
-        amg_release(p);
-    }
+    (void)hipSetDevice(p->device);
+    p->ops->release(p);
     delete p;
     return CVR_OK;
 }
