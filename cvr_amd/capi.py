@@ -144,6 +144,11 @@ class AmgSmoothedInfo(C.Structure):
                 ("reserved", C.c_int32 * 8)]
 
 
+class AmgMis2Info(C.Structure):
+    """cvr_amg_mis2_info"""
+    _fields_ = [("mis2", C.c_int32), ("reserved0", C.c_int32), ("rounds", C.c_int32 * AMG_MAX_LEVELS), ("reserved", C.c_int32 * 8)]
+
+
 class SpGemmInfo(C.Structure):
     """cvr_spgemm_info_t"""
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("inner", C.c_int64), ("nnz", C.c_int64), ("products", C.c_int64), ("max_row_products", C.c_int64),
@@ -199,6 +204,8 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_amg_hierarchy_export_level", "cvr_amg_hierarchy_destroy",
            "cvr_precond_amg_smoothed", "cvr_amg_smoothed_setup_host", "cvr_precond_amg_smoothed_info", "cvr_amg_hierarchy_smoothed_info",
            "cvr_precond_amg_export_prolongator", "cvr_amg_hierarchy_export_prolongator",
+           "cvr_precond_amg_mis2", "cvr_amg_mis2_setup_host", "cvr_precond_amg_mis2_info", "cvr_amg_hierarchy_mis2_info", "cvr_amg_mis2_aggregate_host",
+           "cvr_amg_mis2_aggregate_device",
            "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
@@ -298,6 +305,12 @@ def lib():
         L.cvr_amg_hierarchy_smoothed_info.argtypes = [C.c_void_p, C.POINTER(AmgSmoothedInfo)]
         L.cvr_precond_amg_export_prolongator.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_amg_hierarchy_export_prolongator.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.cvr_precond_amg_mis2.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_double, C.c_void_p]
+        L.cvr_amg_mis2_setup_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.cvr_precond_amg_mis2_info.argtypes = [C.c_void_p, C.POINTER(AmgMis2Info)]
+        L.cvr_amg_hierarchy_mis2_info.argtypes = [C.c_void_p, C.POINTER(AmgMis2Info)]
+        L.cvr_amg_mis2_aggregate_host.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.cvr_amg_mis2_aggregate_device.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -513,6 +526,45 @@ def amg_smoothed_setup_host(rp, ci, vals, omega=0.0, **options):
     """cvr_amg_smoothed_setup_host: (AmgInfo, AmgSmoothedInfo, [AmgLevel, ...], [AmgProlongator, ...]) of the smoothed-aggregation hierarchy of a
     square CSR matrix with sorted rows and a diagonal in every row -- what Precond.amg_smoothed builds, in host code.  omega = 0.0: the default 4/3.
     Errors as amg_setup_host.  Host only."""
+    return _amg_smoothed_setup_host("cvr_amg_smoothed_setup_host", rp, ci, vals, omega, options)[:4]
+
+
+def amg_mis2_setup_host(rp, ci, vals, omega=0.0, **options):
+    """cvr_amg_mis2_setup_host: (AmgInfo, AmgSmoothedInfo, [AmgLevel, ...], [AmgProlongator, ...], AmgMis2Info) of the smoothed-aggregation hierarchy
+    with the MIS(2) aggregation -- what Precond.amg_mis2 builds, in host code.  Errors as amg_smoothed_setup_host.  Host only."""
+    return _amg_smoothed_setup_host("cvr_amg_mis2_setup_host", rp, ci, vals, omega, options)
+
+
+def amg_mis2_aggregate_host(rp, ci, vals, strength=0.08):
+    """cvr_amg_mis2_aggregate_host: (agg as int32, nc, rounds) of the MIS(2) aggregation of a square CSR matrix with sorted rows and a diagonal entry
+    in every row.  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    f32 = np.asarray(vals).dtype == np.float32
+    va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+    n = len(rp) - 1
+    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    agg, nc, rounds = np.full(n, -1, dtype=np.int32), C.c_int64(-1), C.c_int32(-1)
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
+    rc = lib().cvr_amg_mis2_aggregate_host(C.byref(view), float(strength), agg.ctypes.data, C.byref(nc), C.byref(rounds))
+    if rc:
+        raise CvrError(rc, "cvr_amg_mis2_aggregate_host")
+    return agg, nc.value, rounds.value
+
+
+def amg_mis2_aggregate_device(n, row_ptr_dev, col_idx_dev, vals_dev, agg_dev, is_f32=False, strength=0.08, device=0, stream=None):
+    """cvr_amg_mis2_aggregate_device: (nc, rounds); agg_dev receives n int32 values.  CSR arrays and agg_dev in the memory of `device` (raw pointers)"""
+    nc, rounds = C.c_int64(-1), C.c_int32(-1)
+    view = CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1)
+    rc = lib().cvr_amg_mis2_aggregate_device(C.byref(view), float(strength), agg_dev, C.byref(nc), C.byref(rounds), int(device), stream)
+    if rc:
+        raise CvrError(rc, "cvr_amg_mis2_aggregate_device")
+    return nc.value, rounds.value
+
+
+def _amg_smoothed_setup_host(entry, rp, ci, vals, omega, options):
+    """the set-up through `entry` (cvr_amg_smoothed_setup_host or cvr_amg_mis2_setup_host) and everything the hierarchy exports"""
     rp = np.ascontiguousarray(rp, dtype=np.int64)
     ci = np.ascontiguousarray(ci, dtype=np.int32)
     f32 = np.asarray(vals).dtype == np.float32
@@ -525,18 +577,18 @@ def amg_smoothed_setup_host(rp, ci, vals, omega=0.0, **options):
     opt = amg_options(**options)
     h, bad_level, bad_row = C.c_void_p(), C.c_int32(-1), C.c_int64(-1)
     view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
-    rc = L.cvr_amg_smoothed_setup_host(C.byref(h), C.byref(view), C.byref(opt), float(omega), C.byref(bad_level), C.byref(bad_row))
+    rc = getattr(L, entry)(C.byref(h), C.byref(view), C.byref(opt), float(omega), C.byref(bad_level), C.byref(bad_row))
     if rc:
-        e = CvrError(rc, "cvr_amg_smoothed_setup_host")
+        e = CvrError(rc, entry)
         e.bad = (bad_level.value, bad_row.value) if bad_level.value >= 0 else None
         raise e
     try:
-        info, sinfo = AmgInfo(), AmgSmoothedInfo()
-        rc = L.cvr_amg_hierarchy_info(h, C.byref(info)) or L.cvr_amg_hierarchy_smoothed_info(h, C.byref(sinfo))
+        info, sinfo, minfo = AmgInfo(), AmgSmoothedInfo(), AmgMis2Info()
+        rc = L.cvr_amg_hierarchy_info(h, C.byref(info)) or L.cvr_amg_hierarchy_smoothed_info(h, C.byref(sinfo)) or L.cvr_amg_hierarchy_mis2_info(h, C.byref(minfo))
         if rc:
             raise CvrError(rc, "cvr_amg_hierarchy_info")
         levels = [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
-        return info, sinfo, levels, [_amg_export_prolongator(L.cvr_amg_hierarchy_export_prolongator, h, info, sinfo, l, dtype) for l in range(info.levels - 1)]
+        return info, sinfo, levels, [_amg_export_prolongator(L.cvr_amg_hierarchy_export_prolongator, h, info, sinfo, l, dtype) for l in range(info.levels - 1)], minfo
     finally:
         L.cvr_amg_hierarchy_destroy(h)
 
@@ -1052,6 +1104,32 @@ class Precond:
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
         return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega)
 
+    @classmethod
+    def amg_mis2(cls, matrix, rp, ci, vals, omega=0.0, **options):
+        """cvr_precond_amg_mis2: Precond.amg_smoothed with the MIS(2) aggregation, the whole level loop on the device; the same kind of object
+        (kind 4, smoothed) for the same calls."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options, omega, mis2=True)
+
+    @classmethod
+    def amg_mis2_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, omega=0.0, **options):
+        """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
+        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega, mis2=True)
+
+    def amg_mis2_info(self):
+        """cvr_precond_amg_mis2_info: an AmgMis2Info (mis2, the MIS rounds of every level); all zero of a kind-4 object built another way"""
+        info = AmgMis2Info()
+        rc = lib().cvr_precond_amg_mis2_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_amg_mis2_info")
+        return info
+
     def amg_smoothed_info(self):
         """cvr_precond_amg_smoothed_info: an AmgSmoothedInfo (smoothed, omega, products_per_apply, p_nnz of every level); all zero of a plain object"""
         info = AmgSmoothedInfo()
@@ -1065,16 +1143,17 @@ class Precond:
         return _amg_export_prolongator(lib().cvr_precond_amg_export_prolongator, self._p, self.amg_info(), self.amg_smoothed_info(), level, self.dtype)
 
     @classmethod
-    def _amg_from_view(cls, matrix, view, options, omega=None):
+    def _amg_from_view(cls, matrix, view, options, omega=None, mis2=False):
         self = cls()
         opt = amg_options(**options)
+        entry = "cvr_precond_amg" if omega is None else "cvr_precond_amg_mis2" if mis2 else "cvr_precond_amg_smoothed"
         if omega is None:
             rc = lib().cvr_precond_amg(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), None)
         else:
-            rc = lib().cvr_precond_amg_smoothed(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), float(omega), None)
+            rc = getattr(lib(), entry)(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), float(omega), None)
         if rc:
             self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_amg" if omega is None else "cvr_precond_amg_smoothed")
+            raise CvrError(rc, entry)
         lib().cvr_precond_get_info(self._p, C.byref(self.info))
         self.dtype = np.float32 if self.info.is_f32 else np.float64
         self._matrix = matrix

@@ -16,11 +16,15 @@
 // set-up's loop (SmoothedBuild: amg_tentative_kernel, the device SpGEMM, amg_prolongator_kernel, transpose_csr, two more products), owns a handle of
 // P_l and one of R_l per level and moves between levels by products: amg_residual_kernel and R_l's product in place of amg_restrict_kernel, P_l's
 // product and amg_correct_kernel in place of amg_prolong_kernel.  Per level two more buffers: t (R_l's input, element n stays 0) and e (P_l's output).
+// The device set-up (cvr_precond_amg_mis2: setup_mis2 below) builds the same smoothed object with no level loop on the host: the MIS(2) aggregation
+// and the diagonal are kernels (cvr_amg_mis2.hip), steps 1 - 5 are SmoothedBuild::coarsen, every level's CSR, dinv, agg and P_l stay in device arrays
+// of the object's own, and the exports copy from them when first asked (fetch_level, fetch_prolongator).  DESIGN.md 5.44.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
 #include "cvr_precond.h"
 #include "cvr_amg.h"
+#include "cvr_amg_mis2.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
@@ -36,10 +40,13 @@ struct AmgLevel {
     void       *d_r = nullptr, *d_z = nullptr, *d_q = nullptr;
     cvr_handle *hp = nullptr, *hr = nullptr;          // the smoothed kind above the coarsest level: the object's handles of P_l and R_l ...
     void       *d_t = nullptr, *d_e = nullptr;        // ... R_l's input and P_l's output
+    void       *d_arp = nullptr, *d_aci = nullptr, *d_ava = nullptr;          // the device set-up (cvr_precond_amg_mis2): the level's CSR (row_ptr[0] = 0) ...
+    void       *d_prp = nullptr, *d_pci = nullptr, *d_pva = nullptr;          // ... and P_l's above the coarsest level, kept for the exports
 };
 
 struct Amg {
     amg::Hierarchy        H;          // the host's copy: what the info and the export return
+    bool                  on_demand = false;          // the device set-up: a level's arrays come to H when an export first asks (fetch_level, fetch_prolongator)
     std::vector<AmgLevel> lv;
     void                 *d_winv = nullptr;
     int                   products = 0;          // of one apply
@@ -213,24 +220,24 @@ struct SmoothedBuild {
         ~Transposed() { t.release(); }
     };
 
+    // Steps 1 - 5 of one level whose dinv and agg lie in dl: what lives on behind them, until the caller has taken its copies
+    struct Coarse {
+        Product      G, AC;
+        Scratch      s;          // T's arrays and P's values
+        cvr_csr_view pv{}, acv{};
+        void        *d_pva = nullptr;
+        size_t       pnnz = 0;
+        int64_t      cnnz = 0;
+    };
+
+    // ... and the two transfer handles; returns with the device idle
     template <typename T>
-    int step(amg::Level &f, amg::Level &c, int32_t level)
+    static int coarsen(cvr_precond *p, AmgLevel &dl, const cvr_csr_view &cur, long long n, int64_t nc, double omega, hipStream_t st, Coarse &o)
     {
-        Amg      *a = p->amg;
-        AmgLevel &dl = a->lv[(size_t)level];          // (sized for CVR_AMG_MAX_LEVELS before the set-up)
         const int is_f32 = p->is_f32;
-        if (level == 0) {
-            if (const int rc = upload_level(f, is_f32, cur_bufs, "level 0's row_ptr", "level 0's col_idx", "level 0's values", &cur)) return rc;
-        } else {
-            dl.own = true;
-            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
-        }
-        const long long n = f.n;
-        if (const int rc = upload(kEntry, &dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
-        if (const int rc = upload(kEntry, &dl.d_agg, f.agg.data(), sizeof(int32_t) * f.agg.size(), "agg")) return rc;
         // 1. T
-        Scratch s;
-        void   *d_trp = nullptr, *d_tci = nullptr, *d_tva = nullptr, *d_pva = nullptr;
+        Scratch &s = o.s;
+        void    *d_trp = nullptr, *d_tci = nullptr, *d_tva = nullptr, *d_pva = nullptr;
         if (const int rc = device_alloc(kEntry, &d_trp, sizeof(int64_t) * (size_t)(n + 1), "the tentative prolongator")) return rc;
         s.bufs.push_back(d_trp);
         if (const int rc = device_alloc(kEntry, &d_tci, sizeof(int32_t) * (size_t)n, "the tentative prolongator")) return rc;
@@ -240,20 +247,20 @@ struct SmoothedBuild {
         launch_level(amg_tentative_kernel<T>, n + 1, st, static_cast<const int32_t *>(dl.d_agg), static_cast<int64_t *>(d_trp), static_cast<int32_t *>(d_tci), static_cast<T *>(d_tva), n);
         HIP_TRY(hipGetLastError());
         cvr_csr_view tv{};
-        tv.nrows = f.n;
-        tv.ncols = f.nc;
+        tv.nrows = n;
+        tv.ncols = nc;
         tv.row_ptr = static_cast<const int64_t *>(d_trp);
         tv.col_idx = static_cast<const int32_t *>(d_tci);
         tv.vals = d_tva;
         tv.is_f32 = is_f32;
         tv.arrays_on_device = 1;
         // 2. G = A T (cvr_spgemm_create orders itself behind `st` and returns with it idle)
-        Product      G, AP, AC;
-        cvr_csr_view gv{}, apv{}, acv{};
-        if (const int rc = cvr_spgemm_create(&G.g, &cur, &tv, p->device, st)) return rc;
-        if (const int rc = cvr_spgemm_csr_device(G.g, &gv)) return rc;
+        Product      AP;
+        cvr_csr_view gv{}, apv{};
+        if (const int rc = cvr_spgemm_create(&o.G.g, &cur, &tv, p->device, st)) return rc;
+        if (const int rc = cvr_spgemm_csr_device(o.G.g, &gv)) return rc;
         cvr_spgemm_info_t gi;
-        if (const int rc = cvr_spgemm_get_info(G.g, &gi)) return rc;
+        if (const int rc = cvr_spgemm_get_info(o.G.g, &gi)) return rc;
         const size_t pnnz = (size_t)gi.nnz;
         // 3. P on G's pattern
         if (const int rc = device_alloc(kEntry, &d_pva, sizeof(T) * pnnz, "the prolongator's values")) return rc;
@@ -277,44 +284,288 @@ struct SmoothedBuild {
         // 5. A_c = R (A P)
         if (const int rc = cvr_spgemm_create(&AP.g, &cur, &pv, p->device, st)) return rc;
         if (const int rc = cvr_spgemm_csr_device(AP.g, &apv)) return rc;
-        if (const int rc = cvr_spgemm_create(&AC.g, &rv, &apv, p->device, st)) return rc;
-        if (const int rc = cvr_spgemm_csr_device(AC.g, &acv)) return rc;
+        if (const int rc = cvr_spgemm_create(&o.AC.g, &rv, &apv, p->device, st)) return rc;
+        if (const int rc = cvr_spgemm_csr_device(o.AC.g, &o.acv)) return rc;
         cvr_spgemm_info_t ci;
-        if (const int rc = cvr_spgemm_get_info(AC.g, &ci)) return rc;
-        // the host's copies: P for the export, A_c for the next level's aggregation and the export
-        f.prp.assign((size_t)n + 1, 0);
-        f.pci.assign(pnnz, 0);
-        f.pva.assign(sizeof(T) * pnnz, 0);
-        HIP_TRY(hipMemcpy(f.prp.data(), gv.row_ptr, sizeof(int64_t) * f.prp.size(), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(f.pci.data(), gv.col_idx, sizeof(int32_t) * pnnz, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(f.pva.data(), d_pva, sizeof(T) * pnnz, hipMemcpyDeviceToHost));
-        c.n = f.nc;
-        c.nnz = ci.nnz;
-        c.rp.assign((size_t)c.n + 1, 0);
-        c.ci.assign((size_t)c.nnz, 0);
-        c.va.assign(sizeof(T) * (size_t)c.nnz, 0);
-        if (const int rc = cvr_spgemm_export(AC.g, c.rp.data(), c.ci.data(), c.va.data())) return rc;
+        if (const int rc = cvr_spgemm_get_info(o.AC.g, &ci)) return rc;
         // the two transfer handles, from the device arrays
         if (const int rc = make_handle(&dl.hp, pv, p->device, 0)) return rc;
         if (const int rc = make_handle(&dl.hr, rv, p->device, 0)) return rc;
         HIP_TRY(hipDeviceSynchronize());          // (the handles' copies are complete before the step's arrays go)
+        o.pv = pv;
+        o.d_pva = d_pva;
+        o.pnnz = pnnz;
+        o.cnnz = ci.nnz;
+        return CVR_OK;
+    }
+
+    template <typename T>
+    int step(amg::Level &f, amg::Level &c, int32_t level)
+    {
+        Amg      *a = p->amg;
+        AmgLevel &dl = a->lv[(size_t)level];          // (sized for CVR_AMG_MAX_LEVELS before the set-up)
+        const int is_f32 = p->is_f32;
+        if (level == 0) {
+            if (const int rc = upload_level(f, is_f32, cur_bufs, "level 0's row_ptr", "level 0's col_idx", "level 0's values", &cur)) return rc;
+        } else {
+            dl.own = true;
+            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
+        }
+        const long long n = f.n;
+        if (const int rc = upload(kEntry, &dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
+        if (const int rc = upload(kEntry, &dl.d_agg, f.agg.data(), sizeof(int32_t) * f.agg.size(), "agg")) return rc;
+        Coarse o;
+        if (const int rc = coarsen<T>(p, dl, cur, n, f.nc, omega, st, o)) return rc;
+        const size_t pnnz = o.pnnz;
+        // the host's copies: P for the export, A_c for the next level's aggregation and the export
+        f.pnnz = (int64_t)pnnz;
+        f.prp.assign((size_t)n + 1, 0);
+        f.pci.assign(pnnz, 0);
+        f.pva.assign(sizeof(T) * pnnz, 0);
+        HIP_TRY(hipMemcpy(f.prp.data(), o.pv.row_ptr, sizeof(int64_t) * f.prp.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(f.pci.data(), o.pv.col_idx, sizeof(int32_t) * pnnz, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(f.pva.data(), o.d_pva, sizeof(T) * pnnz, hipMemcpyDeviceToHost));
+        c.n = f.nc;
+        c.nnz = o.cnnz;
+        c.rp.assign((size_t)c.n + 1, 0);
+        c.ci.assign((size_t)c.nnz, 0);
+        c.va.assign(sizeof(T) * (size_t)c.nnz, 0);
+        if (const int rc = cvr_spgemm_export(o.AC.g, c.rp.data(), c.ci.data(), c.va.data())) return rc;
         if (cur_owner) (void)cvr_spgemm_destroy(cur_owner);
-        cur_owner = AC.g;
-        AC.g = nullptr;
+        cur_owner = o.AC.g;
+        o.AC.g = nullptr;
         Scratch().bufs.swap(cur_bufs.bufs);          // (level 0's upload goes with the temporary)
-        cur = acv;
+        cur = o.acv;
         return CVR_OK;
     }
 };
 
 size_t x_bytes_of(const cvr_handle *h) { return h->vsz * (size_t)std::max<int64_t>(h->info.x_elems, h->info.ncols + 1); }
 
-int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, bool smoothed, double omega, hipStream_t st)
+enum class Mode { kPlain, kSmoothed, kMis2 };
+const char *entry_of(Mode m) { return m == Mode::kMis2 ? "cvr_precond_amg_mis2" : m == Mode::kSmoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg"; }
+
+// row_ptr[i] -= base
+__global__ __launch_bounds__(kThreads) void amg_rebase_kernel(int64_t *__restrict__ rp, long long n1, long long base)
+{
+    CVR_AMG_ELEMENTS(i, n1) rp[i] -= base;
+}
+
+cvr_csr_view level_view(const AmgLevel &dl, int64_t n, int is_f32)
+{
+    cvr_csr_view v{};
+    v.nrows = v.ncols = n;
+    v.row_ptr = static_cast<const int64_t *>(dl.d_arp);
+    v.col_idx = static_cast<const int32_t *>(dl.d_aci);
+    v.vals = dl.d_ava;
+    v.is_f32 = is_f32;
+    v.arrays_on_device = 1;
+    return v;
+}
+
+// The device set-up's copy of a level or a prolongator in H, made when an export first asks for it
+int fetch_level(const cvr_precond *p, int32_t level)
+{
+    Amg *a = p->amg;
+    if (!a->on_demand || level < 0 || level >= (int32_t)a->H.lv.size()) return CVR_OK;          // (a level outside: the export's own error)
+    amg::Level     &l = a->H.lv[(size_t)level];
+    const AmgLevel &dl = a->lv[(size_t)level];
+    const size_t    vsz = p->is_f32 ? 4 : 8;
+    HIP_TRY(hipSetDevice(p->device));
+    try {
+        if (l.rp.empty()) {
+            std::vector<int64_t> rp((size_t)l.n + 1, 0);
+            std::vector<int32_t> ci((size_t)l.nnz, 0);
+            std::vector<uint8_t> va(vsz * (size_t)l.nnz, 0);
+            HIP_TRY(hipMemcpy(rp.data(), dl.d_arp, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
+            if (l.nnz > 0) {
+                HIP_TRY(hipMemcpy(ci.data(), dl.d_aci, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(va.data(), dl.d_ava, va.size(), hipMemcpyDeviceToHost));
+            }
+            l.ci.swap(ci);
+            l.va.swap(va);
+            l.rp.swap(rp);
+        }
+        if (l.dinv.empty() && l.n > 0) {
+            std::vector<uint8_t> dinv(vsz * (size_t)l.n, 0);
+            HIP_TRY(hipMemcpy(dinv.data(), dl.d_dinv, dinv.size(), hipMemcpyDeviceToHost));
+            l.dinv.swap(dinv);
+        }
+        if (l.agg.empty() && level + 1 < (int32_t)a->H.lv.size()) {
+            std::vector<int32_t> agg((size_t)l.n, 0);
+            HIP_TRY(hipMemcpy(agg.data(), dl.d_agg, sizeof(int32_t) * agg.size(), hipMemcpyDeviceToHost));
+            l.agg.swap(agg);
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "%s: out of host memory for level %d", kEntry, level);
+    }
+    return CVR_OK;
+}
+
+int fetch_prolongator(const cvr_precond *p, int32_t level)
+{
+    Amg *a = p->amg;
+    if (!a->on_demand || level < 0 || level + 1 >= (int32_t)a->H.lv.size()) return CVR_OK;
+    amg::Level     &l = a->H.lv[(size_t)level];
+    const AmgLevel &dl = a->lv[(size_t)level];
+    if (!l.prp.empty()) return CVR_OK;
+    HIP_TRY(hipSetDevice(p->device));
+    try {
+        std::vector<int64_t> rp((size_t)l.n + 1, 0);
+        std::vector<int32_t> ci((size_t)l.pnnz, 0);
+        std::vector<uint8_t> va((p->is_f32 ? 4 : 8) * (size_t)l.pnnz, 0);
+        HIP_TRY(hipMemcpy(rp.data(), dl.d_prp, sizeof(int64_t) * rp.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ci.data(), dl.d_pci, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(va.data(), dl.d_pva, va.size(), hipMemcpyDeviceToHost));
+        l.pci.swap(ci);
+        l.pva.swap(va);
+        l.prp.swap(rp);
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "%s: out of host memory for the prolongator of level %d", kEntry, level);
+    }
+    return CVR_OK;
+}
+
+// bytes of device memory into a buffer of the object's own, enqueued on st
+int device_copy(void **out, const void *src, size_t bytes, const char *what, hipStream_t st)
+{
+    if (const int rc = device_alloc(kEntry, out, bytes, what)) return rc;
+    if (bytes) HIP_TRY(hipMemcpyAsync(*out, src, bytes, hipMemcpyDeviceToDevice, st));
+    return CVR_OK;
+}
+
+// cvr_precond_amg_mis2's set-up: the smoothed kind's level loop with nothing of it on the host.  Level 0 becomes arrays of the object's own (from
+// host arrays, or from device arrays behind their checks); per level the diagonal kernel, the MIS(2) aggregation (cvr_amg_mis2.hip), steps 1 - 5
+// (SmoothedBuild::coarsen) and device-to-device copies of P_l and A_(l+1) into arrays the object keeps for the next level and for the exports.
+// The host waits on scalars and reads the coarsest level for the dense inverse.  *cur: the last level's CSR, for its handle.
+template <typename T>
+int setup_mis2(cvr_precond *p, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, hipStream_t st, cvr_csr_view *cur_out)
+{
+    const char     *entry = entry_of(Mode::kMis2);
+    Amg            *a = p->amg;
+    amg::Hierarchy &H = a->H;
+    const int       is_f32 = p->is_f32;
+    const int64_t   n0 = p->n;
+    int64_t         j0 = 0, j1 = 0;
+    cvr::debug_refresh();
+    if (csr->arrays_on_device) {          // (host arrays: checked before any device work, in construct)
+        std::vector<int64_t> rp_host;
+        if (const int rc = check_device_view(kEntry, csr, rp_host, st)) return rc;
+        if (n0 > 0) j0 = rp_host.front(), j1 = rp_host.back();
+        if (j1 > j0 && !csr->vals) return fail(CVR_ERR_INVALID, "vals is null");
+        if (const int rc = mis2_check_structure_device(entry, *csr, rp_host, st)) return rc;
+    } else if (n0 > 0) j0 = csr->row_ptr[0], j1 = csr->row_ptr[n0];
+    if (n0 == 0) {          // one empty level, inverted directly: the host's set-up makes it
+        int32_t bad_level = -1;
+        int64_t bad_row = -1;
+        const int64_t rp0 = 0;
+        if (const int rc = amg::setup(H, 0, &rp0, nullptr, nullptr, is_f32, opt, entry, &bad_level, &bad_row, nullptr, amg::Aggregation::kMis2)) return rc;
+        H.smoothed = 1;
+        H.omega = omega;
+        return CVR_OK;
+    }
+    try {
+        H = amg::Hierarchy();
+        H.lv.reserve(CVR_AMG_MAX_LEVELS);
+        H.lv.emplace_back();
+        a->lv.resize(CVR_AMG_MAX_LEVELS);
+    } catch (const std::bad_alloc &) {
+        return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
+    }
+    H.opt = *opt;
+    H.is_f32 = is_f32;
+    H.smoothed = 1;
+    H.omega = omega;
+    H.mis2 = 1;
+    a->on_demand = true;
+    // level 0 in the object's own arrays, row_ptr[0] = 0
+    {
+        AmgLevel           &d0 = a->lv[0];
+        const size_t        nnz = (size_t)(j1 - j0);
+        const hipMemcpyKind kind = csr->arrays_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        if (const int rc = device_alloc(kEntry, &d0.d_arp, sizeof(int64_t) * (size_t)(n0 + 1), "level 0's row_ptr")) return rc;
+        if (const int rc = device_alloc(kEntry, &d0.d_aci, sizeof(int32_t) * nnz, "level 0's col_idx")) return rc;
+        if (const int rc = device_alloc(kEntry, &d0.d_ava, sizeof(T) * nnz, "level 0's values")) return rc;
+        HIP_TRY(hipMemcpyAsync(d0.d_arp, csr->row_ptr, sizeof(int64_t) * (size_t)(n0 + 1), kind, st));
+        if (nnz > 0) {
+            HIP_TRY(hipMemcpyAsync(d0.d_aci, csr->col_idx + j0, sizeof(int32_t) * nnz, kind, st));
+            HIP_TRY(hipMemcpyAsync(d0.d_ava, static_cast<const T *>(csr->vals) + j0, sizeof(T) * nnz, kind, st));
+        }
+        if (j0 != 0) launch_level(amg_rebase_kernel, n0 + 1, st, static_cast<int64_t *>(d0.d_arp), (long long)(n0 + 1), (long long)j0);
+        HIP_TRY(hipGetLastError());
+        H.lv[0].n = n0;
+        H.lv[0].nnz = (int64_t)nnz;
+    }
+    cvr_csr_view cur = level_view(a->lv[0], n0, is_f32);
+    for (;;) {
+        const int32_t level = (int32_t)H.lv.size() - 1;
+        amg::Level   &l = H.lv.back();
+        AmgLevel     &dl = a->lv[(size_t)level];
+        const int64_t n = l.n;
+        Scratch       s;
+        void         *d_diag = nullptr;
+        int64_t       bad = -1;
+        if (const int rc = device_alloc(kEntry, &dl.d_dinv, sizeof(T) * (size_t)n, "dinv")) return rc;
+        if (const int rc = scratch_alloc(kEntry, s, &d_diag, sizeof(double) * (size_t)n, "the diagonal")) return rc;
+        if (const int rc = mis2_diagonal_device(kEntry, cur, dl.d_dinv, static_cast<double *>(d_diag), &bad, st)) return rc;
+        if (bad >= 0) return fail(CVR_ERR_STATE, "%s: level %d: the diagonal entry of row %lld is not finite or not > 0", entry, level, (long long)bad);
+        if (n <= H.opt.coarse_size || (int32_t)H.lv.size() == H.opt.max_levels) break;
+        int64_t nc = 0;
+        int32_t rounds = 0;
+        if (const int rc = device_alloc(kEntry, &dl.d_agg, sizeof(int32_t) * (size_t)n, "agg")) return rc;
+        if (const int rc = mis2_aggregate_device(kEntry, cur, 0, l.nnz, static_cast<const double *>(d_diag), H.opt.strength, static_cast<int32_t *>(dl.d_agg), &nc, &rounds, st)) return rc;
+        if ((double)nc > 0.8 * (double)n) {          // a stall: this level is the last
+            (void)hipFree(dl.d_agg);
+            dl.d_agg = nullptr;
+            break;
+        }
+        l.nc = nc;
+        H.rounds[level] = rounds;
+        if (level > 0) {
+            dl.own = true;
+            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
+        }
+        SmoothedBuild::Coarse o;
+        if (const int rc = SmoothedBuild::coarsen<T>(p, dl, cur, n, nc, omega, st, o)) return rc;
+        AmgLevel &dn = a->lv[(size_t)level + 1];
+        if (const int rc = device_copy(&dl.d_prp, o.pv.row_ptr, sizeof(int64_t) * (size_t)(n + 1), "a prolongator's row_ptr", st)) return rc;
+        if (const int rc = device_copy(&dl.d_pci, o.pv.col_idx, sizeof(int32_t) * o.pnnz, "a prolongator's col_idx", st)) return rc;
+        if (const int rc = device_copy(&dl.d_pva, o.d_pva, sizeof(T) * o.pnnz, "a prolongator's values", st)) return rc;
+        if (const int rc = device_copy(&dn.d_arp, o.acv.row_ptr, sizeof(int64_t) * (size_t)(nc + 1), "a level's row_ptr", st)) return rc;
+        if (const int rc = device_copy(&dn.d_aci, o.acv.col_idx, sizeof(int32_t) * (size_t)o.cnnz, "a level's col_idx", st)) return rc;
+        if (const int rc = device_copy(&dn.d_ava, o.acv.vals, sizeof(T) * (size_t)o.cnnz, "a level's values", st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));          // (the copies are complete before the step's arrays go)
+        l.pnnz = (int64_t)o.pnnz;
+        H.lv.emplace_back();          // (reserved: l stays where it is)
+        H.lv.back().n = nc;
+        H.lv.back().nnz = o.cnnz;
+        cur = level_view(dn, nc, is_f32);
+    }
+    const int32_t last = (int32_t)H.lv.size() - 1;
+    if (H.lv.back().n <= CVR_AMG_MAX_COARSE) {          // the coarsest level comes to the host for its inverse
+        H.coarse_direct = 1;
+        if (const int rc = fetch_level(p, last)) return rc;
+        int64_t bad = -1;
+        try {
+            bad = amg::coarsest_inverse(H.lv.back(), is_f32, H.winv);
+        } catch (const std::bad_alloc &) {
+            return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
+        }
+        if (bad >= 0) return fail(CVR_ERR_STATE, "%s: level %d: the pivot of row %lld of the coarsest matrix is not finite or not > 0", entry, last, (long long)bad);
+    }
+    *cur_out = cur;
+    return CVR_OK;
+}
+
+int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, Mode mode, double omega, hipStream_t st)
 {
     Amg          *a = p->amg;
-    const char   *entry = smoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg";
+    const bool    smoothed = mode != Mode::kPlain;
+    const char   *entry = entry_of(mode);
     SmoothedBuild sb;
-    {
+    if (mode == Mode::kMis2) {
+        if (const int rc = p->is_f32 ? setup_mis2<float>(p, csr, opt, omega, st, &sb.cur) : setup_mis2<double>(p, csr, opt, omega, st, &sb.cur)) return rc;
+    } else {
         HostCsr hc;
         if (const int rc = stage_host(kEntry, csr, hc, true, st)) return rc;
         if (csr->arrays_on_device)          // (host arrays: checked before any device work, in construct)
@@ -370,7 +621,7 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
             if (const int rc = make_handle(&dl.h, lv, p->device, 0)) return rc;
         }
         if (smoothed) {
-            if (last)
+            if (last && !dl.d_dinv)          // (the device set-up has left every level's there)
                 if (const int rc = upload(kEntry, &dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
             // r is R_(l-1)'s output, z is P_(l-1)'s input beside A_l's, t is R_l's input, e is P_l's output; zeroed: the pad slots stay 0
             const AmgLevel *up = l > 0 ? &a->lv[l - 1] : nullptr;
@@ -490,7 +741,7 @@ void amg_release(cvr_precond *p)
         if (l.own && l.h) (void)cvr_destroy(l.h);
         if (l.hp) (void)cvr_destroy(l.hp);
         if (l.hr) (void)cvr_destroy(l.hr);
-        for (void *buf : {l.d_dinv, l.d_agg, l.d_mrp, l.d_mem, l.d_r, l.d_z, l.d_q, l.d_t, l.d_e})
+        for (void *buf : {l.d_dinv, l.d_agg, l.d_mrp, l.d_mem, l.d_r, l.d_z, l.d_q, l.d_t, l.d_e, l.d_arp, l.d_aci, l.d_ava, l.d_prp, l.d_pci, l.d_pva})
             if (buf) (void)hipFree(buf);
     }
     if (a->d_winv) (void)hipFree(a->d_winv);
@@ -510,10 +761,11 @@ PrecondOps kAmgOps = {kPrecondAmg, "AMG", amg_apply_any, amg_release, amg_cg_app
 
 namespace {
 
-// cvr_precond_amg and cvr_precond_amg_smoothed: one constructor, `smoothed` with its omega as given
-int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, bool smoothed, double omega, void *stream)
+// cvr_precond_amg, cvr_precond_amg_smoothed and cvr_precond_amg_mis2: one constructor, the smoothed kinds with their omega as given
+int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, Mode mode, double omega, void *stream)
 {
-    const char *entry = smoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg";
+    const bool  smoothed = mode != Mode::kPlain;
+    const char *entry = entry_of(mode);
     if (!out || !h || !csr) return fail(CVR_ERR_INVALID, "null argument");
     *out = nullptr;
     cvr_amg_options o;
@@ -548,7 +800,7 @@ int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const c
     p->bs = 0;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->amg = a;
-    if (const int rc = build(p, h, csr, &o, smoothed, omega, (hipStream_t)stream)) return abandon(p, rc);
+    if (const int rc = build(p, h, csr, &o, mode, omega, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }
@@ -559,12 +811,25 @@ extern "C" {
 
 int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream)
 {
-    return construct(out, h, csr, opt, false, 0.0, stream);
+    return construct(out, h, csr, opt, Mode::kPlain, 0.0, stream);
 }
 
 int cvr_precond_amg_smoothed(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream)
 {
-    return construct(out, h, csr, opt, true, omega, stream);
+    return construct(out, h, csr, opt, Mode::kSmoothed, omega, stream);
+}
+
+int cvr_precond_amg_mis2(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream)
+{
+    return construct(out, h, csr, opt, Mode::kMis2, omega, stream);
+}
+
+int cvr_precond_amg_mis2_info(const cvr_precond *p, cvr_amg_mis2_info *info)
+{
+    if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_mis2_info: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    amg::fill_mis2_info(p->amg->H, info);
+    return CVR_OK;
 }
 
 int cvr_precond_amg_smoothed_info(const cvr_precond *p, cvr_amg_smoothed_info *info)
@@ -579,6 +844,7 @@ int cvr_precond_amg_export_prolongator(const cvr_precond *p, int32_t level, int6
 {
     if (!p) return fail(CVR_ERR_INVALID, "null argument");
     if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_export_prolongator: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    if (const int rc = fetch_prolongator(p, level)) return rc;
     return amg::export_prolongator(p->amg->H, level, row_ptr, col_idx, vals, "cvr_precond_amg_export_prolongator");
 }
 
@@ -594,6 +860,7 @@ int cvr_precond_amg_export_level(const cvr_precond *p, int32_t level, int64_t *r
 {
     if (!p) return fail(CVR_ERR_INVALID, "null argument");
     if (p->kind != kPrecondAmg || !p->amg) return fail(CVR_ERR_INVALID, "cvr_precond_amg_export_level: the preconditioner is of kind %d, not an AMG object (kind %d)", p->kind, kPrecondAmg);
+    if (const int rc = fetch_level(p, level)) return rc;
     return amg::export_level(p->amg->H, level, row_ptr, col_idx, vals, dinv, agg, winv, "cvr_precond_amg_export_level");
 }
 

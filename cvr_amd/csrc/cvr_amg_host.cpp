@@ -26,17 +26,17 @@ int check_options(const cvr_amg_options *o, const char *entry)
     return CVR_OK;
 }
 
-int check_structure(int64_t n, const int64_t *rp, const int32_t *ci, const char *entry)
+int check_structure(int64_t n, const int64_t *rp, const int32_t *ci, const char *entry, int64_t row0)
 {
     for (int64_t i = 0; i < n; i++) {
         int64_t d = -1, prev = -1;
         for (int64_t q = rp[i]; q < rp[i + 1]; q++) {
             const int64_t c = ci[q];
-            if (c <= prev) return fail(CVR_ERR_INVALID, "%s: row %lld: the columns are not strictly increasing (%lld behind %lld)", entry, (long long)i, (long long)c, (long long)prev);
+            if (c <= prev) return fail(CVR_ERR_INVALID, "%s: row %lld: the columns are not strictly increasing (%lld behind %lld)", entry, (long long)(row0 + i), (long long)c, (long long)prev);
             prev = c;
-            if (c == i) d = q;
+            if (c == row0 + i) d = q;
         }
-        if (d < 0) return fail(CVR_ERR_INVALID, "%s: row %lld has no diagonal entry", entry, (long long)i);
+        if (d < 0) return fail(CVR_ERR_INVALID, "%s: row %lld has no diagonal entry", entry, (long long)(row0 + i));
     }
     return CVR_OK;
 }
@@ -219,8 +219,9 @@ int64_t dense_inverse(const Level &l, std::vector<uint8_t> &winv)
 }
 
 template <typename T>
-int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_row, const Coarsen *coarsen)
+int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_row, const Coarsen *coarsen, Aggregation aggregation)
 {
+    H.mis2 = aggregation == Aggregation::kMis2;
     std::vector<double> diag;
     for (;;) {
         Level        &l = H.lv.back();
@@ -234,8 +235,14 @@ int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_ro
         smoother_diagonal<T>(l);
         if (l.n <= H.opt.coarse_size || (int32_t)H.lv.size() == H.opt.max_levels) break;
         std::vector<int32_t> agg;
-        const int64_t        nc = aggregate<T>(l, diag, H.opt.strength, agg);
+        int32_t              rounds = 0;
+        int64_t              nc;
+        if (aggregation == Aggregation::kMis2) {
+            agg.assign((size_t)l.n, -1);
+            nc = mis2_aggregate(l.n, l.rp.data(), l.ci.data(), l.va.data(), sizeof(T) == 4, H.opt.strength, agg.data(), &rounds);
+        } else nc = aggregate<T>(l, diag, H.opt.strength, agg);
         if ((double)nc > 0.8 * (double)l.n) break;          // a stall: this level is the last
+        H.rounds[level] = rounds;
         l.agg.swap(agg);
         l.nc = nc;
         Level c;
@@ -263,7 +270,7 @@ int setup_t(Hierarchy &H, const char *entry, int32_t *bad_level, int64_t *bad_ro
 }  // namespace
 
 int setup(Hierarchy &H, int64_t n, const int64_t *rp, const int32_t *ci, const void *va, int is_f32, const cvr_amg_options *opt, const char *entry, int32_t *bad_level,
-          int64_t *bad_row, const Coarsen *coarsen)
+          int64_t *bad_row, const Coarsen *coarsen, Aggregation aggregation)
 {
     *bad_level = -1;
     *bad_row = -1;
@@ -284,11 +291,13 @@ int setup(Hierarchy &H, int64_t n, const int64_t *rp, const int32_t *ci, const v
             l.va.resize(vsz * (size_t)l.nnz);
             memcpy(l.va.data(), static_cast<const uint8_t *>(va) + vsz * (size_t)base, l.va.size());
         }
-        return is_f32 ? setup_t<float>(H, entry, bad_level, bad_row, coarsen) : setup_t<double>(H, entry, bad_level, bad_row, coarsen);
+        return is_f32 ? setup_t<float>(H, entry, bad_level, bad_row, coarsen, aggregation) : setup_t<double>(H, entry, bad_level, bad_row, coarsen, aggregation);
     } catch (const std::bad_alloc &) {
         return fail(CVR_ERR_NOMEM, "%s: out of host memory (%lld rows)", entry, (long long)n);
     }
 }
+
+int64_t coarsest_inverse(const Level &l, int is_f32, std::vector<uint8_t> &winv) { return is_f32 ? dense_inverse<float>(l, winv) : dense_inverse<double>(l, winv); }
 
 void fill_info(const Hierarchy &H, cvr_amg_info *info)
 {

@@ -126,6 +126,7 @@ int coarsen_t(Level &f, Level &c, double omega)
     f.prp.swap(p.rp);
     f.pci.swap(p.ci);
     f.pva.swap(p.va);
+    f.pnnz = (int64_t)pnnz;
     return CVR_OK;
 }
 
@@ -149,7 +150,7 @@ void fill_smoothed_info(const Hierarchy &H, cvr_amg_smoothed_info *info)
     info->smoothed = 1;
     info->products_per_apply = products_per_apply(H);
     info->omega = H.omega;
-    for (size_t l = 0; l + 1 < H.lv.size(); l++) info->p_nnz[l] = (int64_t)H.lv[l].pci.size();
+    for (size_t l = 0; l + 1 < H.lv.size(); l++) info->p_nnz[l] = H.lv[l].pnnz;
 }
 
 int export_prolongator(const Hierarchy &H, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals, const char *entry)

@@ -969,6 +969,58 @@ int cvr_amg_hierarchy_smoothed_info(const cvr_amg_hierarchy *hier, cvr_amg_smoot
 int cvr_precond_amg_export_prolongator(const cvr_precond *p, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals);
 int cvr_amg_hierarchy_export_prolongator(const cvr_amg_hierarchy *hier, int32_t level, int64_t *row_ptr, int32_t *col_idx, void *vals);
 
+/* Smoothed-aggregation AMG whose set-up runs on the device: cvr_precond_amg_smoothed with a distance-2 maximal independent set, MIS(2), in place of
+ * the three serial passes -- an aggregation defined by parallel rounds (Bell, Dalton, Olson), since a pass that walks the rows in ascending order
+ * cannot be a kernel.  The object is kind 4 with smoothed = 1: its cycle, products_per_apply, buffers, exports, infos and the entry points that
+ * take or decline it are the smoothed kind's, unchanged.  Everything of the set-up but the aggregation keeps the text above bit for bit: the
+ * smoother diagonal, the bad-diagonal rule (the lowest row), the stopping rule, the stall rule, steps 1 - 5, the dense inverse, omega.
+ * The aggregation of a level (a CSR that passed the structure rules) with `strength`:
+ *   N(i), the strong neighbours: the columns j != i of row i whose entry passes the strength test above (a_ij != 0 and
+ *     a_ij * a_ij >= ((strength * strength) * a_ii) * a_jj in fp64).  N is taken row by row and never symmetrised: everything below is defined for
+ *     a directed N (a coarse operator is symmetric only to rounding, and the structure rules do not ask for a symmetric pattern).
+ *   Keys: h(i) = murmur3's 32-bit finaliser of uint32(i) (x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16, modulo 2^32);
+ *     key(i) = (uint64(state_i) << 62) | (uint64(h(i) >> 1) << 31) | uint64(i) with the states 1 undecided, 2 root, 0 out.  n < 2^31 - 1, so keys
+ *     are unique.  The hash is of the row index alone: no level, no seed -- the aggregation of a matrix is a function of that matrix.
+ *   Rounds: all rows start undecided.  A round is a pure function of the states at its start: m1(i) = max(key(i), key(j) for j in N(i));
+ *     m2(i) = max(m1(i), m1(j) for j in N(i)); an undecided i with m2(i) == key(i) becomes a root, an undecided i whose m2(i) carries state 2 goes
+ *     out.  Rounds repeat until no row is undecided; `rounds` counts those that began with an undecided row (0 for n = 0).  The undecided row with
+ *     the largest key sees a root or itself, so every round decides a row; a row with empty N(i) is a root after round 1 and ends as a singleton.
+ *   Numbering: the aggregates are numbered by their roots in ascending row order (an exclusive scan of the root flags); nc = the roots.
+ *   Join, two passes, each a pure function of the state before it: 1. a non-root i with a root in N(i) takes the aggregate of the root j with the
+ *     largest |a_ij| (fp64; ties: the lowest j); 2. a still-free i takes the aggregate of the j in N(i) that is a root or was assigned by pass 1,
+ *     by the same rule (rows assigned by pass 2 do not count).  An out row has a root within two directed steps, so no row stays free.  Nothing is
+ *     merged, split or renumbered afterwards.
+ * cvr_precond_amg_mis2 runs none of the level loop on the host.  Level 0 is copied once into arrays of the object's own on the device (from host
+ *   arrays, checked on the host before any device work, or from device arrays, checked where they lie: the structure rules by a kernel that finds
+ *   the lowest offending row).  Per level: a kernel for the diagonal, dinv and the lowest bad row (an integer atomicMin), one for the flags of the
+ *   strong entries, two per round (m1; m2 with the state update and the count of undecided rows, an integer atomic add), a scan of the root flags,
+ *   the two join passes, then steps 1 - 5 as cvr_precond_amg_smoothed does them.  A thread per row; no kernel waits on another workgroup; no
+ *   floating-point atomic.  The host waits on scalars only (the bad-row word, the undecided counts, nc, the products' nnz) and reads the coarsest
+ *   level (at most CVR_AMG_MAX_COARSE rows) for the dense inverse.  CVR_DEBUG=mis2_check=<k> reads the undecided counts back every k rounds
+ *   (default 4); the surplus rounds change nothing and are not counted, so no bit and no count depends on k.
+ *   The object keeps every level's CSR, dinv, agg and P_l in device arrays of its own beside the handles; the exports and infos copy from them when
+ *   asked (and keep the host copy).  Levels, prolongators, infos and `rounds` are cvr_amg_mis2_setup_host's byte for byte.
+ * cvr_amg_mis2_setup_host: cvr_amg_smoothed_setup_host with this aggregation in host loops.
+ * cvr_precond_amg_mis2_info / cvr_amg_hierarchy_mis2_info fill a cvr_amg_mis2_info; of a kind-4 object or hierarchy built another way: all zero;
+ *   another kind: CVR_ERR_INVALID.  cvr_precond_amg_smoothed_info reports smoothed = 1 on the new object.
+ * cvr_amg_mis2_aggregate_host / _device: the aggregation alone, of any square matrix that passes the structure rules (nothing is asked of the
+ *   diagonal's sign: the strength test reads it as it is): agg (nrows entries; host memory / memory of `device`), *nc and *rounds.  The device call
+ *   checks the view as cvr_precond_amg_mis2 checks device arrays, orders itself behind `stream` and returns with it idle; both give the same agg.
+ * Errors: those of cvr_precond_amg_smoothed / cvr_amg_smoothed_setup_host in their order, with the entry point's own name in cvr_last_error; on a
+ *   failure nothing is left allocated. */
+typedef struct {
+    int32_t mis2;                              /* 1: built by a *_mis2 entry point; 0: otherwise, and everything below is 0 */
+    int32_t reserved0;                         /* 0                                                                         */
+    int32_t rounds[CVR_AMG_MAX_LEVELS];        /* MIS rounds of level l's aggregation; 0 from the coarsest level on         */
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_amg_mis2_info;                           /* 104 bytes */
+int cvr_precond_amg_mis2(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream);
+int cvr_amg_mis2_setup_host(cvr_amg_hierarchy **out, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, int32_t *bad_level, int64_t *bad_row);
+int cvr_precond_amg_mis2_info(const cvr_precond *p, cvr_amg_mis2_info *info);
+int cvr_amg_hierarchy_mis2_info(const cvr_amg_hierarchy *hier, cvr_amg_mis2_info *info);
+int cvr_amg_mis2_aggregate_host(const cvr_csr_view *csr, double strength, int32_t *agg, int64_t *nc, int32_t *rounds);
+int cvr_amg_mis2_aggregate_device(const cvr_csr_view *csr_on_device, double strength, int32_t *agg_dev, int64_t *nc, int32_t *rounds, int device, void *stream);
+
 /* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
