@@ -12,6 +12,8 @@ What the header fixes and this file does, in the header's order:
   * the solvers: cvr_cg_device's, cvr_bicgstab_device's and cvr_gmres_device's recurrences with this apply where they have T(minv * r); GMRES forms x
     from the fp64 combination u by the same two sweeps with u where L's sweep has double(r): x = T(double(x) + double(zu)).
 The arithmetic is Python's float (IEEE fp64, one rounding per operation, never fused) in the apply and numpy's fp64 scalars in the factorisation."""
+import functools
+
 import numpy as np
 
 import krylov_model as KM
@@ -234,6 +236,88 @@ def transpose(n, rp, ci, va):
     rpt = np.zeros(n + 1, dtype=np.int64)
     rpt[1:] = np.cumsum(np.bincount(cols, minlength=n))
     return n, n, rpt, rows[order].astype(np.int32), np.asarray(va[: rp[-1]])[order]
+
+
+def _irregular_triangle(n, rng, kmax, near, shallow):
+    """per row i the ascending columns left of the diagonal: about one row in six has none, the others draw k in [1, min(i, kmax)] columns, each one of
+    the `near` columns just left of i or uniform in [0, i) (a coin decides; a column drawn twice counts once).  shallow > 0: that share of the rows
+    with columns draws them uniformly among the earlier rows that have none instead -- rows of level 1"""
+    rows, roots = [np.zeros(0, dtype=np.int64)], [0]
+    for i in range(1, n):
+        if rng.random() < 1.0 / 6.0:
+            rows.append(np.zeros(0, dtype=np.int64))
+            roots.append(i)
+            continue
+        k = int(rng.integers(1, min(i, kmax) + 1))
+        if shallow > 0 and rng.random() < shallow:
+            rows.append(np.unique(rng.choice(roots, size=k)).astype(np.int64))
+            continue
+        close = i - 1 - rng.integers(0, min(near, i), size=k)
+        far = rng.integers(0, i, size=k)
+        rows.append(np.unique(np.where(rng.random(k) < 0.5, close, far)).astype(np.int64))
+    return rows
+
+
+def irregular(n, seed, sym, kmax, dtype, near=8, shallow=0.0):
+    """(n, n, row_ptr, col_idx, vals) of an irregular matrix that ILU(0) factors without a bad pivot: rows of unrelated lengths (0 .. kmax entries in a
+    triangle), level-0 rows scattered through the matrix, neighbouring and far columns mixed.  sym: the upper triangle mirrors the lower one, pattern and
+    values; else it is drawn on its own in the same way from the last row back (row i's columns right of the diagonal among i + 1 .. i + near or uniform
+    in (i, n)).  Off-diagonal values uniform in (-1, 1), the diagonal 1 + the sum of the row's |off-diagonals| + U(0, 1): strictly row dominant.
+    shallow: the share of rows of level 1 (_irregular_triangle); 0 but for irr-nonsym-2500, where a level of 512 rows behind a narrower level 0 is
+    wanted: with columns uniform in [0, i) a level behind level 0 holds less than level 0's share times the rest, never a fifth of the rows.
+    Everything comes from np.random.default_rng(seed)."""
+    rng = np.random.default_rng(seed)
+    lower = _irregular_triangle(n, rng, kmax, near, shallow)
+    lower_vals = [rng.uniform(-1.0, 1.0, size=len(c)) for c in lower]
+    upper, upper_vals = [[] for _ in range(n)], [[] for _ in range(n)]
+    if sym:
+        for i in range(n):
+            for c, v in zip(lower[i].tolist(), lower_vals[i].tolist()):          # (rows ascending: every upper row comes out ascending)
+                upper[c].append(i)
+                upper_vals[c].append(v)
+    else:
+        mirrored = _irregular_triangle(n, rng, kmax, near, shallow)
+        for i in range(n):
+            upper[i] = (n - 1 - mirrored[n - 1 - i])[::-1].tolist()
+            upper_vals[i] = rng.uniform(-1.0, 1.0, size=len(upper[i])).tolist()
+    rp, ci, va = [0], [], []
+    for i in range(n):
+        off = lower_vals[i].tolist() + list(upper_vals[i])
+        ci += lower[i].tolist() + [i] + list(upper[i])
+        va += lower_vals[i].tolist() + [1.0 + float(np.abs(off).sum()) + rng.random()] + list(upper_vals[i])
+        rp.append(len(ci))
+    return n, n, np.array(rp, dtype=np.int64), np.array(ci, dtype=np.int32), np.array(va).astype(dtype)
+
+
+# name -> (n, seed, sym, kmax, near, shallow): the irregular cases of tests/test_ilu_model_host.py (which holds each to its conditions) and of
+# tests/test_gpu_ilu0_irregular.py
+IRREGULAR = {
+    "irr-spd-700": (700, 700, True, 6, 8, 0.0),
+    "irr-nonsym-700": (700, 701, False, 6, 8, 0.0),
+    "irr-dense-spd-320": (320, 320, True, 190, 8, 0.0),
+    "irr-dense-nonsym-320": (320, 321, False, 320, 8, 0.0),
+    "irr-nonsym-2500": (2500, 2500, False, 3, 8, 0.3),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def irregular_case(name, prec):
+    """(n, rp, ci, va, f, lo, up, nlo, nup, threshold) of a named case in "fp64" or "fp32": the matrix, the model's factors (no bad pivot), its levels and
+    width_threshold -- computed once and shared, nobody writes to them"""
+    dtype = np.float64 if prec == "fp64" else np.float32
+    n, seed, sym, kmax, near, shallow = IRREGULAR[name]
+    n, _, rp, ci, va = irregular(n, seed, sym, kmax, dtype, near, shallow)
+    f, bad = factor(rp, ci, va, dtype)
+    assert bad is None, (name, prec, bad)
+    for a in (rp, ci, va, f):
+        a.setflags(write=False)
+    return (n, rp, ci, va, f) + levels(rp, ci) + (width_threshold(rp, ci),)
+
+
+def width_threshold(rp, ci):
+    """a wide_threshold from the matrix's own level widths, max(2, the median width over both sweeps): about half of the levels are wide, half merged"""
+    lo, up, nlo, nup = levels(rp, ci)
+    return max(2, int(np.median(np.concatenate([widths(lo, nlo), widths(up, nup)]))))
 
 
 def dense_lu(n, rp, ci, f):

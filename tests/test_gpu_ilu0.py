@@ -2,8 +2,11 @@
 cvr_pcg / cvr_pbicgstab / cvr_pgmres with an object of this kind, all through the ABI, against tests/ilu_model.py.
 
   * the factors (export) and the apply byte for byte against the model, fp64 and fp32: banded "spd" and "nonsym" at n = 1, 2, 63, 64, 65, 1025 (n levels
-    of one row: the merged path), the Laplacian at m = 3, 24, 40, the two-level wide matrix (n = 4097) and its transpose (wide levels in L and in U);
-    r and z off the 16-byte grid one at a time; every apply repeated
+    of one row: the merged path), the Laplacian at m = 3, 24, 40, the two-level wide matrix (n = 4097) and its transpose (wide levels in L and in U),
+    the five irregular cases of ilu_model.IRREGULAR (default G = 4, 64, 32, 2; tests/test_ilu_model_host.py holds them to their conditions), those
+    also under the threshold taken from their own level widths (merged runs and wide levels in turn; irr-nonsym-2500 alternates by default);
+    r and z off the 16-byte grid one at a time; every apply repeated.  tests/test_gpu_ilu0_irregular.py: every lane count, the solvers on the
+    irregular patterns, the lowest bad pivot
   * every object built under CVR_DEBUG=ilu_wide=1, the default and ilu_wide=1000000: the same export and apply, launches_* by the model's plan
   * PCG, PBiCGSTAB and PGMRES (restart 5 and 30) step by step against the model: max_iters 0 .. 4 at rtol 0, a solve to 1e-8 on the 24 x 24 Laplacian;
     check_every 1, 3 and the default give the same bits; spmv_count by the block-Jacobi formulas; the host twins
@@ -35,22 +38,31 @@ def _matrix(name, dtype):
         return synth.laplacian_2d(int(size), dtype)
     if kind == "wide":
         return IM.wide_matrix(dtype)
+    if kind == "irr":
+        n, rp, ci, va = IM.irregular_case(name, "fp64" if dtype == np.float64 else "fp32")[:4]
+        return n, n, rp, ci, va
     assert kind == "wideT", name
     n, _, rp, ci, va = IM.wide_matrix(dtype)
     return IM.transpose(n, rp, ci, va)
 
 
-MATRICES = [f"{k}-{n}" for k in ("spd", "nonsym") for n in (1, 2, 63, 64, 65, 1025)] + ["laplacian-3", "laplacian-24", "laplacian-40", "wide", "wideT"]
+MATRICES = [f"{k}-{n}" for k in ("spd", "nonsym") for n in (1, 2, 63, 64, 65, 1025)] + ["laplacian-3", "laplacian-24", "laplacian-40", "wide", "wideT"] + list(IM.IRREGULAR)
 
 
-def _build(rp, ci, va, wide=None):
-    """Precond.ilu0 with CVR_DEBUG=ilu_wide=<wide> in the environment while the object is built (the switch is read there)"""
+def _thresholds(name, rp, ci):
+    """WIDES, and for the irregular cases with narrow levels the threshold from their own widths: merged runs and wide levels in turn"""
+    return WIDES + ([IM.width_threshold(rp, ci)] if name.startswith("irr-") and name != "irr-nonsym-2500" else [])
+
+
+def _build(rp, ci, va, wide=None, lanes=None):
+    """Precond.ilu0 with CVR_DEBUG=ilu_wide=<wide>,ilu_lanes=<lanes> in the environment while the object is built (the switches are read there)"""
+    knobs = ([f"ilu_wide={wide}"] if wide is not None else []) + ([f"ilu_lanes={lanes}"] if lanes is not None else [])
     old = os.environ.get("CVR_DEBUG")
     try:
-        if wide is None:
-            os.environ.pop("CVR_DEBUG", None)
+        if knobs:
+            os.environ["CVR_DEBUG"] = ",".join(knobs)
         else:
-            os.environ["CVR_DEBUG"] = f"ilu_wide={wide}"
+            os.environ.pop("CVR_DEBUG", None)
         return capi.Precond.ilu0(rp, ci, va)
     finally:
         if old is None:
@@ -81,14 +93,17 @@ def test_factors_and_apply_against_the_model_for_every_plan(name, prec):
     dtype = G.dtype_of(prec)
     n, _, rp, ci, va = _matrix(name, dtype)
     nnz = int(rp[-1])
-    f, bad = IM.factor(rp, ci, va, dtype)
-    assert bad is None
-    lo, up, nlo, nup = IM.levels(rp, ci)
+    if name.startswith("irr-"):          # (factored once for all the tests that use the case)
+        f, lo, up, nlo, nup = IM.irregular_case(name, prec)[4:9]
+    else:
+        f, bad = IM.factor(rp, ci, va, dtype)
+        assert bad is None
+        lo, up, nlo, nup = IM.levels(rp, ci)
     Gl = IM.default_lanes(n, nnz)
     r = KM.inputs(n, dtype)[0]
     want = IM.apply(rp, ci, f, r, Gl, dtype)
     assert np.isfinite(want).all()
-    for wide in WIDES:
+    for wide in _thresholds(name, rp, ci):
         P = _build(rp, ci, va, wide)
         try:
             w = IM.DEFAULT_WIDE if wide is None else wide

@@ -58,6 +58,12 @@ def test_empty_strict_triangles_and_n_zero():
     assert _check(rp, ci) == (2, 1)
 
 
+@pytest.mark.parametrize("name", list(IM.IRREGULAR))
+def test_irregular(name):
+    n, rp, ci, _, _, _, _, nlo, nup, _ = IM.irregular_case(name, "fp64")
+    assert _check(rp, ci) == (nlo, nup) and min(nlo, nup) > 20          # rows of unrelated lengths, level-0 rows scattered through the matrix
+
+
 def _call(n, ncols, rp, ci):
     L = capi.lib()
     rp, ci = np.ascontiguousarray(rp, dtype=np.int64), np.ascontiguousarray(ci, dtype=np.int32)
