@@ -189,10 +189,27 @@ def cases(dtype):
 CASE_NAMES = list(cases(np.float32))
 COLLISIONS = [20, 40, 80, 170, 340, 680, 1360, 2700]          # 1.5 times as many products: a table of 64, 128, .., 8192 slots
 COLLISION_NAMES = [f"collisions-{d}{e}" for d in COLLISIONS for e in ("", "-end")]
-PLAN_CASES = ["laplacian-24", "duplicates", "collisions-340", "collisions-340-end"]          # rerun under lowered limits
+PLAN_CASES = ["laplacian-24", "duplicates", "collisions-340", "collisions-340-end", "mixed-3000"]          # rerun under lowered limits
+MIXED_PRODUCTS = [0, 5, 40, 100, 0, 12, 70]
+
+
+def mixed(dtype, m=3000, seed=31):
+    """A of m rows whose products cycle through MIXED_PRODUCTS: a period of 7 divides no thread's range of ceil(m / 1024) = 3 consecutive rows in
+    the bin and scan kernels, so every boundary between two classes falls inside some thread's range.  B: 150 rows of 5 entries and 50 rows of one,
+    on 300 columns, so that a row of A meets columns more than once.  Under the default limits the classes are empty, group (5, 12) and block (40,
+    70, 100); under 8:64 all four: group (5), block (12, 40), spill (70, 100)"""
+    r = np.random.default_rng(seed)
+    rows_b = [sorted(r.choice(300, size=5 if k < 150 else 1, replace=False).tolist()) for k in range(200)]
+    rows_a = []
+    for i in range(m):
+        p = MIXED_PRODUCTS[i % 7]
+        rows_a.append(sorted(r.choice(150, size=p // 5, replace=False).tolist()) + sorted((150 + r.choice(50, size=p % 5, replace=False)).tolist()))
+    return from_rows(m, 200, rows_a, dtype, seed + 1), from_rows(200, 300, rows_b, dtype, seed + 2)
 
 
 def named(name, dtype):
+    if name == "mixed-3000":
+        return mixed(dtype)
     if name.startswith("collisions-"):
         return collision_pair(int(name.split("-")[1]), dtype, end=name.endswith("-end"))
     return cases(dtype)[name]

@@ -94,6 +94,45 @@ def test_export_and_info(name, prec):
         assert i.rows_spill == 1 and i.rows_block == 2
 
 
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+def test_rows_of_every_class_side_by_side(prec):
+    """mixed-3000: 3000 rows whose products cycle with a period of 7, three consecutive rows to a thread of the bin and the scan kernels: a thread
+    bins rows of different classes (the older mixed cases have at most 90 rows, one row a thread)"""
+    a, b, want, prod = _case("mixed-3000", prec)
+    assert a.nrows == 3000 and prod.tolist() == [SM.MIXED_PRODUCTS[i % 7] for i in range(3000)] and prod.sum() < 150000
+    assert SM.row_classes(prod) == (857, 857, 1286, 0)          # 0, 0 | 5, 12 | 40, 100, 70 of every seven rows; 3000 = 428 * 7 + 4, the last four rows 0, 5, 40, 100
+    assert all(c > 0 for c in SM.row_classes(prod, 8, 64))          # ... and under 8:64 (test_a_lowered_plan_gives_the_same_bytes) all four classes
+    assert (want.terms > 1).any()
+    _both_ways(a, b, want, prod, ("mixed-3000", prec))
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_squared(prec):
+    """(A, the host twin's A A) for the 513 x 513 grid matrix of mis2_amg_model -- computed once, shared, never changed"""
+    import mis2_amg_model as M
+    n, _, rp, ci, va = M.matrix("ties-grid-513", G.dtype_of(prec))
+    a = SM.Csr(n, n, rp, ci, va)
+    return a, capi.spgemm_host(_tuple(a), _tuple(a))
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+def test_more_group_rows_than_one_trip_of_the_group_kernel(prec):
+    """A A for a 5-point grid of 513^2 = 263 169 rows, every one a group row (at most 25 products): the group kernel takes 4096 workgroups x 32 teams
+    = 131 072 rows a trip, so its second and third trips run, and the bin and scan kernels give a thread 258 rows.  Against the host twin
+    cvr_spgemm_host, byte for byte: spgemm_model.spgemm is a Python loop over 6.6 million products and would take minutes; the twin is pinned to it
+    by tests/test_spgemm_host.py on every smaller case."""
+    a, (rp, ci, va) = _grid_squared(prec)
+    g = _from_device(a, a)
+    try:
+        got = g.export()
+        i = g.info()
+    finally:
+        g.close()
+    assert np.array_equal(got[0], rp) and np.array_equal(got[1], ci) and got[2].dtype == va.dtype and got[2].tobytes() == va.tobytes()
+    assert (i.rows_group, i.rows_block, i.rows_spill, i.rows_empty) == (263169, 0, 0, 0) and i.nnz == len(ci) and i.products > 6500000 and i.max_row_products == 25
+    assert (i.group_limit, i.block_limit) == (SM.GROUP_LIMIT, SM.BLOCK_LIMIT)
+
+
 def _limits():
     one = SM.from_rows(1, 1, [[0]], np.float64)
     g = capi.SpGemm.create(_tuple(one), _tuple(one))

@@ -217,3 +217,28 @@ def test_a_bad_diagonal_or_pivot_reports_level_and_row():
             with pytest.raises(capi.CvrError) as e:
                 capi.amg_mis2_setup_host(rp, ci, va)
             assert e.value.code == capi.ERR_STATE and e.value.bad == H.bad[:2] and f"level {H.bad[0]}" in str(e.value) and f"row {H.bad[1]} " in str(e.value)
+
+
+# ---- the irregular and the large cases (M.IRREGULAR) ----
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("name", M.IRREGULAR_CASES)
+def test_the_host_aggregation_of_the_irregular_cases_is_the_models(name, prec):
+    dtype = np.float64 if prec == "fp64" else np.float32
+    n, _, rp, ci, va = M.matrix(name, dtype)
+    want, nc, rounds = M.cached_aggregate(name, dtype)
+    agg, gnc, grounds = capi.amg_mis2_aggregate_host(rp, ci, va)
+    assert (gnc, grounds) == (nc, rounds) and agg.dtype == np.int32 and agg.tobytes() == want.tobytes(), (name, prec, np.flatnonzero(agg != want)[:5])
+
+
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+@pytest.mark.parametrize("name", M.IRREGULAR_SETUP_CASES)
+def test_the_host_setup_of_the_irregular_cases_is_the_model_byte_for_byte(name, prec):
+    dtype = np.float64 if prec == "fp64" else np.float32
+    n, _, rp, ci, va = M.matrix(name, dtype)
+    H = M.cached_setup(name, dtype)          # (once per process: 5 to 15 s of Python SpGEMM a case and precision)
+    assert H.bad is None
+    info, sinfo, levels, pro, minfo = capi.amg_mis2_setup_host(rp, ci, va)
+    assert SA.same_hierarchy(H, info, sinfo, levels, pro) == "", (name, prec)
+    assert M.same_rounds(H, minfo) == "", (name, prec)
+    if name == "irr-spd-3000":          # a coarsest level of more than 256 rows: smoothed, not inverted
+        assert info.levels == 4 and info.coarse_direct == 0

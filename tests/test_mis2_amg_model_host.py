@@ -150,3 +150,277 @@ def test_levels_rounds_and_pcg_steps_on_the_laplacian_are_pinned(m):
     assert [l.n for l in H.levels] == LEVELS[m] and H.rounds == ROUNDS[m] and H.coarse_direct
     assert steps == STEPS[m]
     assert 1.3 < H.operator_complexity() < 1.4
+
+
+# ---- the irregular and the large cases (M.IRREGULAR): the conditions tests/test_gpu_mis2_amg_irregular.py relies on, and the mutants they tell apart ----
+NEW = M.IRREGULAR_CASES
+SMALL_NEW = ["irr-spd-3000", "irr-directed-3000", "star-2000"]
+MUTANT_CASES = SMALL_NEW + M.TIES_CASES          # (the three edge cases are ties-62290's band without the pairs: nothing it does not show)
+SYMMETRIC = [name for name in NEW if name != "irr-directed-3000"]
+
+
+def _pattern_code(n, rp, ci):
+    return np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) * n + ci
+
+
+@pytest.mark.parametrize("name", NEW)
+def test_the_generators_keep_their_rules(name):
+    n, ncols, rp, ci, va = M.matrix(name, np.float64)
+    assert n == ncols == len(rp) - 1 and rp[0] == 0 and rp[-1] == len(ci) == len(va) and ci.dtype == np.int32 and rp.dtype == np.int64
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    inner = rows[1:] == rows[:-1]
+    assert (np.diff(ci.astype(np.int64))[inner] > 0).all(), "strictly increasing columns"
+    assert np.array_equal(np.flatnonzero(ci == rows) >= 0, np.ones(n, dtype=bool)) and (ci == rows).sum() == n, "a diagonal entry in every row"
+    again = M.IRREGULAR[name][0](np.float64)          # the seed: made twice, the same bytes; fp32 is the rounded fp64
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again[2:], (rp, ci, va)))
+    assert M.matrix(name, np.float32)[4].tobytes() == va.astype(np.float32).tobytes()
+    code = _pattern_code(n, rp, ci)
+    back = ci.astype(np.int64) * n + rows
+    order = np.argsort(back, kind="stable")
+    if name in SYMMETRIC:
+        assert np.array_equal(back[order], code) and np.array_equal(va[order], va), "symmetric"
+        off = ci != rows
+        d = va[~off]
+        assert (va[off] <= 0).all() and (d > np.bincount(rows[off], weights=-va[off], minlength=n)).all(), "an M-matrix, strictly dominant"
+        assert np.array_equal(va.astype(np.float32).astype(np.float64)[off], va[off]) or name == "irr-spd-3000"          # the distinct weights are fp32 numbers
+    else:
+        assert not np.isin(code, back).all(), "some (i, j) without (j, i)"
+
+
+def test_the_irregular_matrices_are_what_the_issue_asks_for():
+    n, _, rp, ci, va = M.matrix("irr-spd-3000", np.float64)
+    lv = AM.Level(n, rp, ci, va)
+    length = np.diff(rp) - 1
+    hist = np.bincount(length)
+    print(f"irr-spd-3000: off-diagonal row lengths 0 .. {length.max()}, {hist[:8].tolist()} rows of 0 .. 7, {(length > 20).sum()} of more than 20")
+    assert n == 3000 and 40 <= length.max() <= 70 and (length == 0).mean() >= 0.05
+    assert np.median(length) <= 4 and (length > 20).sum() >= 30          # a power law: most rows short, a tail of long ones
+    off = ci != lv.rows()
+    weak = 1.0 - AM.strong_entries(lv, 0.08).sum() / off.sum()
+    print(f"irr-spd-3000: {100 * weak:.1f} % of the off-diagonal entries fail the strength test at 0.08")
+    assert 0.05 <= weak <= 0.25
+    mag = np.abs(va[off])
+    assert (mag == 0).sum() == 24 and 0.05 <= mag[mag > 0].min() and mag.max() <= 1.0          # 12 edges stored as explicit zeros
+    grid = (mag * 8 == np.round(mag * 8)) & (mag > 0)
+    assert 0.15 <= grid.mean() <= 0.25
+    # equal magnitudes inside a row beside distinct ones
+    r = lv.rows()[off]
+    order = np.lexsort((mag, r))
+    same = (r[order][1:] == r[order][:-1]) & (mag[order][1:] == mag[order][:-1]) & (mag[order][1:] > 0)
+    assert same.sum() >= 100 and len(np.unique(mag)) > 1000
+    # the directed case: irr-spd's pattern less one direction of about 30 % of the edges, a third of the survivors weak
+    m, _, rp2, ci2, va2 = M.matrix("irr-directed-3000", np.float64)
+    code, code2 = _pattern_code(n, rp, ci), _pattern_code(m, rp2, ci2)
+    assert m == n and np.isin(code2, code).all()
+    gone = (len(code) - len(code2)) / (off.sum() / 2)
+    lv2 = AM.Level(m, rp2, ci2, va2)
+    rows2, cols2, _ = M.strong_graph(lv2, 0.08)
+    one_way = ~np.isin(cols2 * n + rows2, rows2 * n + cols2)
+    scaled = (np.abs(va2) < 0.02) & (va2 != 0) & (ci2 != lv2.rows())          # (w * 2^-7 <= 2^-7, and no unscaled weight is below 0.05)
+    print(f"irr-directed-3000: {100 * gone:.1f} % of the edges lost a direction, {scaled.sum()} survivors scaled, {one_way.sum()} strong entries without a strong reverse")
+    assert 0.25 <= gone <= 0.35 and 0.08 <= scaled.sum() / (off.sum() / 2) <= 0.12 and one_way.sum() >= 500
+    assert not AM.strong_entries(lv2, 0.08)[scaled].any()
+    # the star
+    n, _, rp, ci, va = M.matrix("star-2000", np.float64)
+    assert n == 2000 and rp[1] == 2000 and len(np.unique(va[1: rp[1]])) == 1999          # row 0: every other row, pairwise distinct weights
+    lv = AM.Level(n, rp, ci, va)
+    rows, cols, _ = M.strong_graph(lv, 0.08)
+    assert 0 < (rows == 0).sum() < 100          # a few spokes are strong
+
+
+@pytest.mark.parametrize("name", M.IRREGULAR_SETUP_CASES)
+def test_the_models_setup_of_the_irregular_cases(name):
+    for dtype in (np.float64, np.float32):
+        H = M.cached_setup(name, dtype)
+        print(f"{name} {np.dtype(dtype).name}: levels {[l.n for l in H.levels]}, nnz {[l.nnz for l in H.levels]}, rounds {H.rounds}, coarse_direct {H.coarse_direct}")
+        assert H.bad is None and len(H.levels) >= (3 if name == "irr-spd-3000" else 2)
+        assert all((lv.diagonal() > 0).all() for lv in H.levels)
+
+
+def test_the_stars_products_reach_the_block_and_the_spill_class():
+    """level 0's coarsening of star-2000 under the default limits (32 and 4096): what the device SpGEMM meets inside the set-up without a debug knob"""
+    import spgemm_model as SM
+    H = M.cached_setup("star-2000", np.float64)
+    lv = H.levels[0]
+    A = SM.Csr(lv.n, lv.n, lv.rp, lv.ci, lv.va)
+    AP = SM.spgemm(A, H.P[0])
+    first, second = SM.products(A, H.P[0]), SM.products(H.R[0], AP)
+    c1, c2 = SM.row_classes(first), SM.row_classes(second)
+    print(f"star-2000: (empty, group, block, spill) of A P {c1}, of R (A P) {c2}; row 0 of A P has {first[0]} products and {AP.rp[1]} entries, the longest row of R (A P) {second.max()} products")
+    assert c1[2] >= 1 and c2[2] >= 1 and c1[3] + c2[3] >= 1
+    assert lv.rp[1] - lv.rp[0] >= 1999 and first[0] >= SM.BLOCK_LIMIT
+    assert (SM.GROUP_LIMIT, SM.BLOCK_LIMIT) == (32, 4096)
+
+
+def test_the_equal_hash_pairs_and_their_isolation():
+    pairs = M.equal_hash_pairs(513 * 513)
+    print(f"rows below 513^2 whose 31 hash bits agree: {pairs}")
+    assert len(pairs) == 12 and pairs[0] == (52799, 62289) and M.equal_hash_pairs(62289) == [] and M.equal_hash_pairs(62290) == [(52799, 62289)]
+    assert {(70665, 76500), (64972, 102456), (80037, 117520)} <= set(pairs)
+    h = M.murmur3_fmix32(np.arange(513 * 513)) >> np.uint64(1)
+    assert len(np.unique(h)) == 513 * 513 - 12 and all(h[i] == h[j] for i, j in pairs)
+    for name in M.TIES_CASES:
+        lv = M.level_of(name, np.float64)
+        rows, cols, _ = M.strong_graph(lv, 0.08)
+        mine = M.equal_hash_pairs(lv.n)
+        assert len(mine) == (12 if name == "ties-grid-513" else 1)
+        for i, j in mine:
+            assert cols[rows == i].tolist() == [j] and cols[rows == j].tolist() == [i], (name, i, j)
+            assert not np.isin(cols[(rows != i) & (rows != j)], [i, j]).any()
+        # round 1 decides the pair by the index bits alone: the higher row becomes the root
+        state, m1, m2 = M.mis2_round(np.full(lv.n, M.UNDECIDED, dtype=np.int64), rows, cols)
+        assert all(state[j] == M.ROOT and state[i] == M.UNDECIDED for i, j in mine)
+    assert 513 * 513 - M.GRID_THREADS == 1025 and 512 * 512 == M.GRID_THREADS
+
+
+def test_rounds_of_the_new_cases_cross_the_read_back_interval():
+    rounds = {name: M.cached_aggregate(name, np.float64)[2] for name in NEW}
+    print(f"rounds of the new cases: {rounds}")
+    assert max(rounds.values()) > 4
+    # the three sizes around one grid are one band: the same aggregates up to the last rows
+    a, b = M.cached_aggregate("edge-262143", np.float64)[0], M.cached_aggregate("edge-262145", np.float64)[0]
+    assert np.array_equal(a[:262000], b[:262000])
+
+
+# The mutants: `_variant` is M.aggregate with one rule changed; "none" is the model itself.
+MUTANTS = ["the join ignores magnitudes", "join ties go to the highest j", "pass 2 reads its own output", "pass 2 accepts roots only", "the key has no index bits",
+           "key ties go to the lower row", "m2 is taken from the keys", "the strong graph is symmetrised", "the strength test in T", "an inclusive scan numbers the roots"]
+# what has to catch what, by construction of the cases
+MUST = {"the join ignores magnitudes": SMALL_NEW, "join ties go to the highest j": SMALL_NEW, "pass 2 reads its own output": SMALL_NEW, "pass 2 accepts roots only": SMALL_NEW,
+        "the key has no index bits": M.TIES_CASES, "key ties go to the lower row": M.TIES_CASES, "m2 is taken from the keys": MUTANT_CASES,
+        "the strong graph is symmetrised": ["irr-directed-3000"], "an inclusive scan numbers the roots": MUTANT_CASES}
+
+
+def _variant_keys(state, kind):
+    i = np.arange(len(state), dtype=np.uint64)
+    low = np.zeros_like(i) if kind == "the key has no index bits" else np.uint64(0x7FFFFFFF) - i if kind == "key ties go to the lower row" else i
+    return (state.astype(np.uint64) << np.uint64(62)) | ((M.murmur3_fmix32(i) >> np.uint64(1)) << np.uint64(31)) | low
+
+
+def _variant_join(free, ok, agg, rows, cols, mag, n, kind):
+    on = free[rows] & ok[cols]
+    r, c, m = rows[on], cols[on], mag[on]
+    if kind == "the join ignores magnitudes":
+        m = np.ones(len(m))
+    best = np.full(n, -1.0)
+    np.maximum.at(best, r, m)
+    at = np.flatnonzero(m == best[r])
+    out = np.full(n, -1, dtype=np.int64)
+    if kind == "join ties go to the highest j":
+        pick = np.full(n, -1, dtype=np.int64)
+        np.maximum.at(pick, r[at], at)
+        have = pick >= 0
+    else:
+        pick = np.full(n, len(r), dtype=np.int64)
+        np.minimum.at(pick, r[at], at)
+        have = pick < len(r)
+    out[have] = agg[c[pick[have]]]
+    return out
+
+
+def _variant(lv, strength, kind, T=np.float64):
+    n = lv.n
+    if kind == "the strength test in T":
+        r_, c_, a, d = lv.rows(), lv.ci.astype(np.int64), np.asarray(lv.va, dtype=T), lv.diagonal().astype(T)
+        on = (c_ != r_) & (a != 0) & (a * a >= ((T(strength) * T(strength)) * d[r_]) * d[c_])
+        assert (a * a).dtype == np.dtype(T)
+        rows, cols, mag = r_[on], c_[on], np.abs(M._f64(lv.va))[on]
+    else:
+        rows, cols, mag = M.strong_graph(lv, strength)
+    if kind == "the strong graph is symmetrised":
+        code = np.r_[rows * n + cols, cols * n + rows]
+        _, first = np.unique(code, return_index=True)          # (sorted by row, then column; of an entry present both ways the row's own magnitude)
+        rows, cols, mag = np.r_[rows, cols][first], np.r_[cols, rows][first], np.r_[mag, mag][first]
+    state = np.full(n, M.UNDECIDED, dtype=np.int64)
+    rounds = 0
+    while (state == M.UNDECIDED).any() and rounds < 200:
+        key = _variant_keys(state, kind)
+        m1 = M._spread_max(key, rows, cols)
+        m2 = M._spread_max(key if kind == "m2 is taken from the keys" else m1, rows, cols)
+        und = state == M.UNDECIDED
+        new = state.copy()
+        new[und & (m2 == key)] = M.ROOT
+        new[und & ((m2 >> np.uint64(62)) == np.uint64(M.ROOT))] = M.OUT
+        state = new
+        rounds += 1
+    root = state == M.ROOT
+    number = np.cumsum(root) - (0 if kind == "an inclusive scan numbers the roots" else root)
+    nc = int(root.sum())
+    agg = np.where(root, number, -1).astype(np.int64)
+    one = _variant_join(~root, root, agg, rows, cols, mag, n, kind)
+    agg1 = np.where(root, agg, one)
+    if kind == "pass 2 reads its own output":          # in place, row by row
+        agg2 = agg1.copy()
+        start = np.searchsorted(rows, np.arange(n + 1))
+        for i in np.flatnonzero(agg1 < 0):
+            c, m = cols[start[i]: start[i + 1]], mag[start[i]: start[i + 1]]
+            ok = agg2[c] >= 0
+            if ok.any():
+                agg2[i] = agg2[c[ok][int(np.argmax(m[ok]))]]
+    else:
+        two = _variant_join(agg1 < 0, root if kind == "pass 2 accepts roots only" else agg1 >= 0, agg1, rows, cols, mag, n, kind)
+        agg2 = np.where(agg1 >= 0, agg1, two)
+    return agg2.astype(np.int32), nc, rounds, int((agg1 < 0).sum())
+
+
+def _caught(name, kind, dtype):
+    want = M.cached_aggregate(name, dtype)
+    got = _variant(M.level_of(name, dtype), 0.08, kind, np.dtype(dtype).type)
+    return not (got[0].tobytes() == want[0].tobytes() and got[1:3] == want[1:])
+
+
+@pytest.mark.parametrize("name", MUTANT_CASES + M.AGGREGATION_CASES)
+def test_the_scaffold_of_the_mutants_is_the_model(name):
+    for dtype in (np.float64, np.float32):
+        assert not _caught(name, "none", dtype)
+
+
+def test_the_new_cases_tell_the_mutants_apart():
+    """Byte comparison of (agg, nc, rounds) in fp64.  Every mutant but the strength test in T (fp32 only, below) is caught by the new cases named in
+    MUST; the printed lines say which of the old cases catch it -- before the new cases a mutant with an empty list there passed the whole suite."""
+    for kind in MUTANTS:
+        if kind == "the strength test in T":
+            continue
+        new = [name for name in MUTANT_CASES if _caught(name, kind, np.float64)]
+        old = [name for name in M.AGGREGATION_CASES if _caught(name, kind, np.float64)]
+        print(f"fp64 {kind}: caught by {new}; of the old cases by {old}, not by {[c for c in M.AGGREGATION_CASES if c not in old]}")
+        assert set(MUST[kind]) <= set(new), (kind, new)
+    # ... and the conditions behind them, row by row, on the three small cases
+    for name in SMALL_NEW:
+        lv = M.level_of(name, np.float64)
+        want = M.cached_aggregate(name, np.float64)[0]
+        free_after_pass_1 = _variant(lv, 0.08, "none")[3]
+        lowest = _variant(lv, 0.08, "the join ignores magnitudes")[0]
+        highest = _variant(lv, 0.08, "join ties go to the highest j")[0]
+        print(f"{name}: pass 2 assigns {free_after_pass_1} rows; {(lowest != want).sum()} rows do not follow their lowest eligible neighbour, {(highest != want).sum()} are decided by the tie rule")
+        assert free_after_pass_1 >= 1 and (lowest != want).sum() >= 1 and (highest != want).sum() >= 1
+
+
+def test_the_strength_test_in_fp32_is_printed():
+    """fp32 only: a_ij^2 >= ((s s) a_ii) a_jj evaluated in float instead of double moves an entry across the threshold only when the two sides agree
+    to 2^-24; where no case holds such an entry the mutant cannot show, and the line says so (nothing is asserted of it, as in the ILU file)"""
+    new = [name for name in MUTANT_CASES if _caught(name, "the strength test in T", np.float32)]
+    old = [name for name in M.AGGREGATION_CASES if _caught(name, "the strength test in T", np.float32)]
+    print(f"fp32 the strength test in T: caught by {new}; of the old cases by {old}")
+
+
+def test_the_directed_case_has_a_one_way_entry_that_matters():
+    """some i with j in N(i) and i not in N(j) influences the result: with the strong graph symmetrised the bytes change"""
+    assert _caught("irr-directed-3000", "the strong graph is symmetrised", np.float64) and _caught("irr-directed-3000", "the strong graph is symmetrised", np.float32)
+    for name in ("irr-spd-3000", "star-2000", "ties-62290"):          # ... and on a symmetric strong graph it is the identity
+        assert not _caught(name, "the strong graph is symmetrised", np.float64)
+
+
+IRREGULAR_STEPS = {"irr-spd-3000": 21, "star-2000": 17}          # tests/test_gpu_mis2_amg_irregular.py pins the same counts
+
+
+@pytest.mark.parametrize("name", M.IRREGULAR_SETUP_CASES)
+def test_pcg_steps_on_the_irregular_cases_are_pinned(name):
+    import krylov_model as KM
+    import sa_amg_model as SA
+    H = M.cached_setup(name, np.float64)
+    A, P, R = SA.cpu_products(H)
+    b = KM.inputs(H.levels[0].n, np.float64)[0]
+    last = SA.SaAmgPcg(A[0], np.float64, H, A, P, R).run(b, None, rtol=1e-8, max_iters=200).last
+    print(f"{name}: MIS(2) smoothed AMG-PCG {last.iterations} steps to 1e-8, operator complexity {H.operator_complexity():.3f}")
+    assert last.terminal and last.status == KM.CONVERGED and last.iterations == IRREGULAR_STEPS[name]

@@ -13,7 +13,7 @@ from cvr_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host"]
-HOST_CASES = SM.CASE_NAMES + SM.COLLISION_NAMES
+HOST_CASES = SM.CASE_NAMES + SM.COLLISION_NAMES + ["mixed-3000"]
 
 
 def _tuple(m):
