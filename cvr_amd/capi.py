@@ -112,6 +112,13 @@ class Ilu0Info(C.Structure):
                 ("is_f32", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+class McSgsInfo(C.Structure):
+    """cvr_mcsgs_info"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("ncolors", C.c_int32), ("rounds", C.c_int32), ("launches_per_apply", C.c_int32),
+                ("lanes_per_row", C.c_int32), ("max_color_rows", C.c_int32), ("min_color_rows", C.c_int32), ("is_f32", C.c_int32),
+                ("reserved", C.c_int32 * 8)]
+
+
 FSAI_MAX_ROW = 32           # include/cvr_amd.h: CVR_FSAI_MAX_ROW
 
 
@@ -206,6 +213,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_amg_export_prolongator", "cvr_amg_hierarchy_export_prolongator",
            "cvr_precond_amg_mis2", "cvr_amg_mis2_setup_host", "cvr_precond_amg_mis2_info", "cvr_amg_hierarchy_mis2_info", "cvr_amg_mis2_aggregate_host",
            "cvr_amg_mis2_aggregate_device",
+           "cvr_color_host", "cvr_color_device", "cvr_precond_mcsgs", "cvr_precond_mcsgs_info", "cvr_precond_mcsgs_export",
            "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
@@ -311,6 +319,11 @@ def lib():
         L.cvr_amg_hierarchy_mis2_info.argtypes = [C.c_void_p, C.POINTER(AmgMis2Info)]
         L.cvr_amg_mis2_aggregate_host.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.cvr_amg_mis2_aggregate_device.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+        L.cvr_color_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cvr_color_device.argtypes = [C.POINTER(CsrView), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cvr_precond_mcsgs.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_void_p]
+        L.cvr_precond_mcsgs_info.argtypes = [C.c_void_p, C.POINTER(McSgsInfo)]
+        L.cvr_precond_mcsgs_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_precond_apply_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.cvr_pcg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pcg_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
@@ -415,6 +428,39 @@ def ilu0_levels_host(rp, ci):
     if rc:
         raise CvrError(rc, "cvr_ilu0_levels_host")
     return lo[:n], up[:n], nlo.value, nup.value
+
+
+def _color(call, name, n, view):
+    color, perm, ptr = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+    nc, rounds = C.c_int32(), C.c_int32()
+    rc = call(view, color.ctypes.data, perm.ctypes.data, ptr.ctypes.data, C.byref(nc), C.byref(rounds))
+    if rc:
+        raise CvrError(rc, name)
+    return color[:n], perm[:n], ptr[: nc.value + 1], nc.value, rounds.value
+
+
+def color_host(rp, ci):
+    """cvr_color_host: (color, perm, color_ptr, ncolors, rounds) of a square CSR pattern with sorted rows, a diagonal in every row and a structurally
+    symmetric off-diagonal pattern -- the colouring by rounds on hashed keys (greedy first-fit in descending key order), the rows ordered by
+    (colour, row) and where each colour begins in that order.  Host only."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    n = len(rp) - 1
+    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
+    return _color(lambda v, *a: lib().cvr_color_host(C.byref(v), *a), "cvr_color_host", n, view)
+
+
+def color_device(rp, ci, device=0, on_device=False, n=None):
+    """cvr_color_device: the same on `device`, from host arrays, or (on_device: rp and ci are raw pointers, n the number of rows) from arrays in the
+    device's memory; the outputs are host arrays either way"""
+    if on_device:
+        view = CsrView(n, n, rp, ci, None, 0, 1)
+    else:
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        n = len(rp) - 1
+        view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
+    return _color(lambda v, *a: lib().cvr_color_device(C.byref(v), int(device), None, *a), "cvr_color_device", n, view)
 
 
 def fsai_factor_host(rp, ci, vals):
@@ -1016,6 +1062,53 @@ class Precond:
             if rc:
                 raise CvrError(rc, "cvr_precond_ilu0_export")
         return out
+
+    @classmethod
+    def mcsgs(cls, rp, ci, vals, device=0):
+        """cvr_precond_mcsgs from host CSR arrays of a square matrix whose rows are sorted, without duplicates and with a diagonal entry each, and
+        whose off-diagonal pattern is structurally symmetric (n = len(rp) - 1; the type is vals' dtype, float32 or else float64): multicolour
+        symmetric Gauss-Seidel, 2 * ncolors launches per apply.  Serves one stream at a time."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._mcsgs_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+
+    @classmethod
+    def mcsgs_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
+        """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
+        return cls._mcsgs_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
+
+    @classmethod
+    def _mcsgs_from_view(cls, view, device):
+        self = cls()
+        rc = lib().cvr_precond_mcsgs(C.byref(self._p), C.byref(view), int(device), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_mcsgs")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        return self
+
+    def mcsgs_info(self):
+        """cvr_precond_mcsgs_info: a McSgsInfo (n, nnz, ncolors, rounds, launches_per_apply, lanes_per_row, max_color_rows, min_color_rows, is_f32)"""
+        info = McSgsInfo()
+        rc = lib().cvr_precond_mcsgs_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_mcsgs_info")
+        return info
+
+    def mcsgs_export(self):
+        """cvr_precond_mcsgs_export: (color, perm, color_ptr) of the object's colouring as int32 arrays"""
+        i = self.mcsgs_info()
+        color, perm, ptr = np.zeros(max(i.n, 1), dtype=np.int32), np.zeros(max(i.n, 1), dtype=np.int32), np.zeros(i.ncolors + 1, dtype=np.int32)
+        rc = lib().cvr_precond_mcsgs_export(self._p, color.ctypes.data, perm.ctypes.data, ptr.ctypes.data)
+        if rc:
+            raise CvrError(rc, "cvr_precond_mcsgs_export")
+        return color[: i.n], perm[: i.n], ptr
 
     @classmethod
     def fsai(cls, rp, ci, vals, device=0):

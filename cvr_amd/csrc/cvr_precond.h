@@ -6,12 +6,12 @@
 // r . z kernels the kinds share, the checks every preconditioned entry point makes, and the helpers the constructors build with.  How W is built and
 // laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.  The ILU(0) kind (two level-scheduled triangular sweeps, launches
 // of their own in every solver): cvr_ilu0.hip's head.  The FSAI kind (two products on the SpMV path through two handles of the object's own):
-// cvr_fsai.hip's head.  The AMG kind (one V-cycle: a handle per level, l1-Jacobi sweeps, a segmented sum down and a gather up): cvr_amg.hip's head.
+// cvr_fsai.hip's head.  The AMG kind (one V-cycle: a handle per level, l1-Jacobi sweeps, a segmented sum down and a gather up): cvr_amg.hip's head.  The multicolour SGS kind (two sweeps of one launch per colour of a graph colouring): cvr_mcsgs.hip's head.
 // Where a new kind plugs in: DESIGN.md 5.43.
 #pragma once
 #include "cvr_krylov.h"
 
-constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2, kPrecondFsai = 3, kPrecondAmg = 4;          // cvr_precond::kind
+constexpr int32_t kPrecondBlockJacobi = 0, kPrecondChebyshev = 1, kPrecondIlu0 = 2, kPrecondFsai = 3, kPrecondAmg = 4, kPrecondMcSgs = 5;          // cvr_precond::kind
 
 #define CVR_HIDDEN __attribute__((visibility("hidden")))          // calls and data between the library's own files
 
@@ -21,6 +21,7 @@ struct Chebyshev;     // cvr_chebyshev.hip: the borrowed handle, the polynomial 
 struct Ilu0;          // cvr_ilu0.hip: the factors, the two schedules and the launch plans
 struct Fsai;          // cvr_fsai.hip: W's pattern, Wa and Wb, the two handles and the three buffers
 struct Amg;           // cvr_amg.hip: the hierarchy, a handle and three buffers per level
+struct McSgs;         // cvr_mcsgs.hip: the colouring, the two parts in perm order, the diagonal and one buffer
 
 // What a kind does behind the entry points all kinds share.
 //   apply     z = M r enqueued on `st`, by the object's type (the checks are cvr_precond_apply_device's)
@@ -37,7 +38,7 @@ struct PrecondOps {
     int (*cg_apply_f64)(const cvr_precond *, const double *r, double *z, double *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
 };
 // each in its kind's file; written nowhere (not declared const: a const table would be compiled for the device too, where its functions do not exist)
-CVR_HIDDEN extern PrecondOps kBlockJacobiOps, kChebyshevOps, kIlu0Ops, kFsaiOps, kAmgOps;
+CVR_HIDDEN extern PrecondOps kBlockJacobiOps, kChebyshevOps, kIlu0Ops, kFsaiOps, kAmgOps, kMcSgsOps;
 }
 }
 
@@ -54,6 +55,7 @@ struct cvr_precond {
     cvrh::krylov::Ilu0             *ilu = nullptr;
     cvrh::krylov::Fsai             *fsai = nullptr;
     cvrh::krylov::Amg              *amg = nullptr;
+    cvrh::krylov::McSgs            *mcsgs = nullptr;
 };
 
 namespace cvrh {

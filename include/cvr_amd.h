@@ -1089,6 +1089,75 @@ int cvr_pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, vo
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pgmres(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* ---- a colouring of A's graph, and a sixth kind of cvr_precond on it: multicolour symmetric Gauss-Seidel ----
+ * ILU(0)'s sweeps have as many stages as the longest dependency chain of the ordering, thousands on a Laplacian in its natural order.  Colour the
+ * graph so that no two coupled rows share a colour, order the rows by colour, and a triangular sweep has as many stages as there are colours,
+ * about five.  The colouring is an entry point of its own (it is also what a caller needs to reorder a matrix for cvr_precond_ilu0); the
+ * preconditioner built on it is symmetric Gauss-Seidel in that order: no factorisation, no pivot breakdown beyond a zero diagonal, usable on
+ * any sparse matrix with a diagonal, and symmetric positive definite (so CG may use it) when A is symmetric with a positive diagonal.  Kinds
+ * 0 .. 4 are unchanged; this is kind 5.  Like an ILU(0) object it is independent of any handle and is not refreshed by cvr_update_values.
+ *
+ * The colouring: cvr_color_host (pure host code, no device needed: host arrays only) and cvr_color_device (arrays_on_device 0 or 1).
+ * CSR input: a square view checked as cvr_precond_ilu0 checks one -- CVR_ERR_INVALID with cvr_last_error naming the first offending row where the
+ *   columns of a row are not strictly increasing or a row has no diagonal entry.  In addition the off-diagonal pattern must be structurally
+ *   symmetric: every stored (i, j), j != i, has a stored (j, i); stored zeros count as entries.  A violation is CVR_ERR_INVALID, and cvr_last_error
+ *   names the lowest offending row and its lowest such column.  The values are not read: csr->vals may be NULL.  n = 0 is valid; n < 2^31.
+ * Definition.  key(i) = (h(i) >> 1) << 31 | i, a 62-bit number: h is murmur3's 32-bit finaliser of uint32(i) (x ^= x >> 16; x *= 0x85ebca6b;
+ *   x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16), the function the MIS(2) keys use, without a seed and without a level: a pattern has exactly one
+ *   colouring.  All rows begin uncoloured.  One round is a pure function of the state before it: every uncoloured row whose key is greater than
+ *   the key of each of its uncoloured neighbours (the columns j != i of its row) takes the smallest colour >= 0 that none of its neighbours
+ *   holds.  Rounds repeat until no row is uncoloured.  The result equals greedy first-fit colouring of the rows in descending key order.
+ *   A row's colour is at most its number of neighbours; there is no cap on the number of colours.
+ * Outputs: color[n] (int32, 0 .. ncolors - 1, every colour used); *ncolors; *rounds, the number of rounds that coloured at least one row (0 for
+ *   n = 0); perm[n], the rows ordered by (colour, row number); color_ptr[ncolors + 1], where each colour begins in perm (color_ptr[0] = 0,
+ *   color_ptr[ncolors] = n; the array needs room for n + 1 values, since ncolors is not known before the call).
+ * On the device a round is one launch with a thread per row that reads one array of int32 words (-1 or the colour) and writes another; the count
+ *   of rows still uncoloured comes back every k rounds, k = 4 unless CVR_DEBUG=color_check=<k> is set; a round with nothing uncoloured changes
+ *   nothing, so neither a bit nor *rounds depends on k.  perm and color_ptr come from a counting sort with a stable placement.  No kernel waits on
+ *   another workgroup; the only atomics are integer (min, max, add) and order-free.  cvr_color_device synchronises `stream`.
+ * Errors: a null argument (color and perm may be NULL for n = 0), nrows != ncols, nrows >= 2^31: CVR_ERR_INVALID before any array is read;
+ *   cvr_color_host with arrays_on_device set: CVR_ERR_INVALID; `device` out of range: CVR_ERR_NO_DEVICE; cvr_create's checks of a view and the
+ *   rules above: CVR_ERR_INVALID; CVR_ERR_NOMEM.  On an error *ncolors and *rounds are 0.
+ *
+ * The preconditioner, cvr_precond_mcsgs: M = (D + L) D^-1 (D + U), z = M^-1 r.  D is A's diagonal, L holds the entries a_ij with
+ *   color[j] < color[i], U those with color[j] > color[i]; a valid colouring has no off-diagonal entry within one colour, so L + D + U = A.
+ * Set-up, on the device, from host or device arrays (read and checked as above; the values are read): the colouring; then two CSR parts with the
+ *   rows in perm order, the entries of a part in A's column order with their original column numbers and values of T; the diagonal as doubles.
+ *   A diagonal entry that is zero or not finite: CVR_ERR_STATE, cvr_last_error names the lowest such row, nothing is left allocated.  The host
+ *   waits on the scalars of the colouring, the ncolors + 1 colour offsets and the bad-row word, never on an array of n.
+ * Apply, G = lanes_per_row lanes per row by ILU(0)'s rule: G is the power of two from ceil((nnz - n) / (2 n)) up, at least 1 and at most 64, fixed
+ *   per object (CVR_DEBUG=mcsgs_lanes=<G>, a power of two 1 .. 64, overrides it when the object is built).  Lane l of a row takes the entries
+ *   l, l + G, .. of the row's part and forms s_l = +0 + t + t' + .. with t = double(a_ij) * double(v_j), left to right in fp64, every product and
+ *   addition rounded on its own; the lanes are combined by the xor butterfly (s += s of lane ^ o for o = G/2 .. 1).  Then
+ *       forward, colours 0 .. ncolors - 1, one launch per colour over its rows:    y_i = T((double(r_i) - s) / double(a_ii)),   over L with v = y;
+ *       backward, colours ncolors - 1 .. 0, one launch per colour:                 z_i = T(double(y_i) - s / double(a_ii)),   over U with v = z.
+ *   y is a buffer of the object, so one object serves one stream at a time.  cvr_precond_apply_device takes this kind: exactly 2 ncolors launches
+ *   on `stream` and nothing else, without a read-back; the same bits every call and for every alignment of r_dev and z_dev.
+ * cvr_pcg_device / cvr_pcg take this kind: cvr_pcg_device's text holds with this apply in place of z = W r; one kernel behind the sweeps forms the
+ *   partial sums of r.z and, at the start, p = z, exactly as for an ILU(0) object; behind a stop x, r and p stay untouched (z is scratch).
+ *   3 + 2 ncolors + 1 launches per step; spmv_count as with block-Jacobi.
+ * cvr_precond_get_info works for this kind (block_size, nblocks and identity_blocks are 0); cvr_precond_destroy frees everything.
+ * cvr_precond_export, cvr_precond_apply_multi_device, cvr_pcg_multi_device / cvr_pcg_multi, cvr_pbicgstab_device / cvr_pbicgstab and
+ * cvr_pgmres_device / cvr_pgmres decline this kind: CVR_ERR_STATE behind their other checks, cvr_last_error naming kind 5, "multicolour SGS".  The
+ * other kinds' info and export calls on this kind, and cvr_precond_mcsgs_info / cvr_precond_mcsgs_export on another kind or with a null argument:
+ * CVR_ERR_INVALID.  cvr_precond_mcsgs_export writes color[n], perm[n] and color_ptr[ncolors + 1] to the host.
+ * Errors of cvr_precond_mcsgs: a null argument, nrows != ncols, nrows >= 2^31: CVR_ERR_INVALID before any device work; `device` out of range:
+ * CVR_ERR_NO_DEVICE; the view's checks above: CVR_ERR_INVALID; CVR_ERR_NOMEM: an allocation failed (nothing is left allocated). */
+typedef struct {
+    int64_t n, nnz;                            /* nnz = the entries of the n rows                                           */
+    int32_t ncolors, rounds;                   /* of the colouring                                                          */
+    int32_t launches_per_apply;                /* 2 * ncolors                                                               */
+    int32_t lanes_per_row;                     /* G                                                                         */
+    int32_t max_color_rows, min_color_rows;    /* rows of the largest and of the smallest colour                            */
+    int32_t is_f32;
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_mcsgs_info;
+int cvr_color_host(const cvr_csr_view *csr, int32_t *color, int32_t *perm, int32_t *color_ptr, int32_t *ncolors, int32_t *rounds);
+int cvr_color_device(const cvr_csr_view *csr, int32_t device, void *stream, int32_t *color, int32_t *perm, int32_t *color_ptr, int32_t *ncolors, int32_t *rounds);
+int cvr_precond_mcsgs(cvr_precond **out, const cvr_csr_view *csr, int32_t device, void *stream);
+int cvr_precond_mcsgs_info(const cvr_precond *p, cvr_mcsgs_info *info);
+int cvr_precond_mcsgs_export(const cvr_precond *p, int32_t *color_host, int32_t *perm_host, int32_t *color_ptr_host);
+
 /* ---- least squares on the device: LSQR ------------------------------------------------------------------
  * min ||b - A x||_2 over x for A of any shape and rank -- over- and under-determined and rank-deficient systems included --, and with damp > 0
  * min ||b - A x||^2 + damp^2 ||x - x0||^2 (Tikhonov): LSQR of Paige and Saunders (ACM TOMS 8, 1982), the Golub-Kahan bidiagonalisation with one
