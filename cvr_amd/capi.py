@@ -193,6 +193,21 @@ class EigResult(C.Structure):
                 ("max_estimate", C.c_double)]
 
 
+LOBPCG_MAX_BLOCK = 8        # include/cvr_amd.h: CVR_LOBPCG_MAX_BLOCK
+EIG_MAX_ITERS = 4           # include/cvr_amd.h: CVR_EIG_MAX_ITERS (cvr_lobpcg only)
+
+
+class LobpcgOptions(C.Structure):
+    """cvr_lobpcg_options"""
+    _fields_ = [("nev", C.c_int32), ("which", C.c_int32), ("max_iters", C.c_int32), ("reserved0", C.c_int32), ("tol", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class LobpcgResult(C.Structure):
+    """cvr_lobpcg_result"""
+    _fields_ = [("nconv", C.c_int32), ("status", C.c_int32), ("iterations", C.c_int32), ("spmv_count", C.c_int32), ("precond_applies", C.c_int32),
+                ("restarts_without_p", C.c_int32), ("seconds", C.c_double), ("max_rel_residual", C.c_double)]
+
+
 class MmMatrix(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("nnz", C.c_int64), ("ref_numRows", C.c_int64),
                 ("ref_numCols", C.c_int64), ("ref_nItems", C.c_int64), ("ref_nItemsRaw", C.c_int64),
@@ -218,6 +233,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
+           "cvr_lobpcg_default_options", "cvr_lobpcg_device", "cvr_lobpcg",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -340,6 +356,10 @@ def lib():
         L.cvr_eigsh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult), C.c_void_p]
         L.cvr_eigsh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult)]
         L.cvr_sym_eig_host.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.cvr_lobpcg_default_options.argtypes = [C.POINTER(LobpcgOptions)]
+        L.cvr_lobpcg_default_options.restype = None
+        L.cvr_lobpcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LobpcgOptions), C.POINTER(LobpcgResult), C.c_void_p]
+        L.cvr_lobpcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LobpcgOptions), C.POINTER(LobpcgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
@@ -1724,6 +1744,53 @@ class CvrMatrix:
             raise CvrError(rc, "cvr_eigsh")
         count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
         return evals[:count], (None if evecs is None else evecs[:count, : self.nrows].T), res
+
+    def _lobpcg_options(self, nev, which, tol, max_iters):
+        opt = LobpcgOptions()
+        lib().cvr_lobpcg_default_options(C.byref(opt))
+        try:
+            opt.which = {"LA": EIG_LARGEST, "SA": EIG_SMALLEST}[which]
+        except KeyError:
+            raise ValueError(f"which = {which!r}: must be 'LA' or 'SA'") from None
+        opt.nev, opt.tol, opt.max_iters = int(nev), float(tol), int(max_iters)
+        return opt
+
+    def lobpcg(self, X, precond=None, which="SA", tol=1e-8, max_iters=200, stream=None):
+        """the X.shape[0] (1 .. LOBPCG_MAX_BLOCK) algebraically smallest ("SA") or largest ("LA") eigenvalues of a symmetric A and their eigenvectors by
+        LOBPCG on the device (cvr_lobpcg_device), with an optional Precond of any kind ("SA" only).  X: a contiguous torch device array of shape
+        (nev, ld), ld >= nrows, of the handle's type: row c carries column c of the start block in and the eigenvector of evals[c] out (the C ABI's
+        column-major block with ldx = ld).  Returns (evals: numpy, ascending; resnorms: numpy; LobpcgResult); at EIG_BREAKDOWN both are empty and X is
+        unchanged.  Synchronises the stream."""
+        if X.dim() != 2 or not X.is_contiguous():
+            raise ValueError("X must be a contiguous (nev, ld) array")
+        nev, ld = int(X.shape[0]), int(X.shape[1])
+        opt, res = self._lobpcg_options(nev, which, tol, max_iters), LobpcgResult()
+        evals, resn = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        import torch
+        torch.cuda.synchronize()
+        rc = lib().cvr_lobpcg_device(self._h, None if precond is None else precond._p, X.data_ptr(), ld, evals.ctypes.data, resn.ctypes.data, C.byref(opt),
+                                     C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_lobpcg_device")
+        count = 0 if res.status == EIG_BREAKDOWN else nev
+        return evals[:count], resn[:count], res
+
+    def lobpcg_host(self, X, precond=None, which="SA", tol=1e-8, max_iters=200):
+        """the same through a host array (cvr_lobpcg).  X: numpy of shape (nrows, nev), column c the start vector of pair c.  Returns (evals, X: the
+        eigenvectors in the same shape, resnorms, LobpcgResult); at EIG_BREAKDOWN evals and resnorms are empty and X is the start block."""
+        X = np.asarray(X, dtype=self.dtype)
+        if X.ndim != 2 or X.shape[0] < self.nrows:
+            raise ValueError("X must have shape (nrows, nev)")
+        nev = int(X.shape[1])
+        blk = np.ascontiguousarray(X[: self.nrows].T)          # row c = column c of the block
+        opt, res = self._lobpcg_options(nev, which, tol, max_iters), LobpcgResult()
+        evals, resn = np.zeros(max(nev, 1)), np.zeros(max(nev, 1))
+        rc = lib().cvr_lobpcg(self._h, None if precond is None else precond._p, blk.ctypes.data, max(self.nrows, 1), evals.ctypes.data, resn.ctypes.data,
+                              C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_lobpcg")
+        count = 0 if res.status == EIG_BREAKDOWN else nev
+        return evals[:count], blk.T, resn[:count], res
 
     def gmres(self, b, x0=None, restart=30, minv=None, stream=None, **options):
         """solves A x = b for any nonsingular A by restarted GMRES(restart) on the device (cvr_gmres_device).  b, x0 and minv are torch device

@@ -1415,6 +1415,102 @@ int cvr_eigsh(cvr_handle *h, const void *v0_host, double *evals_host, void *evec
  * Errors: m out of range, null a or w, lda < m, ldz < m with z, an element of the triangle that is not finite: CVR_ERR_INVALID. */
 int cvr_sym_eig_host(int32_t m, const double *a, int32_t lda, double *w, double *z, int32_t ldz);
 
+/* ---- a block of extreme eigenpairs with a preconditioner: LOBPCG ----------------------------------------------
+ * cvr_lobpcg_device / cvr_lobpcg find the k = nev (1 .. CVR_LOBPCG_MAX_BLOCK) algebraically smallest or largest eigenvalues of a symmetric A and their
+ * eigenvectors by the locally optimal block preconditioned conjugate gradient method (Knyazev, SIAM J. Sci. Comput. 23, 2001), optionally with a
+ * preconditioner object p of ANY kind (block-Jacobi, Chebyshev, ILU(0), FSAI, the AMG kinds, multicolour SGS): the call only goes through the object's
+ * apply, one column at a time, which is cvr_precond_apply_device's path, and through cvr_spmv_device's launch path, so any single-GPU handle of a square
+ * matrix works, in fp32 or fp64 and in any layout.  The caller guarantees symmetry (and, with p, that p suits A); nothing checks it.  p == NULL: W = R.
+ * A preconditioner approximates A^-1 and only helps the lower end: p with CVR_EIG_LARGEST is an error.
+ * Not in this version, each left out on purpose: soft locking of converged columns (W is always rebuilt from all k columns, and all k columns go on
+ * being combined until every one has converged); the generalised problem A x = lambda B x; constraints (a deflation block Y); a k-wide product
+ * through cvr_spmm_device (the block is column-major and takes k single-vector products, so every handle works, not only nvec >= 2 ones); more than
+ * 8 columns; cvr_eigsh is unchanged.
+ * X: column-major like cvr_eigsh's evecs, column c at X + c * ldx, ldx >= n, n values of the handle's type T each, any alignment of T; it carries the
+ * start block in and the eigenvectors out (values at positions >= n of a column are neither read nor written).  evals_host and resnorms_host receive k
+ * doubles each: theta_c ascending (CVR_EIG_LARGEST: the k largest, ascending) and ||A x_c - theta_c x_c||_2 as the solver formed it.
+ * CVR_EIG_BREAKDOWN: nothing is written, to X, evals_host or resnorms_host.
+ * Status: CVR_EIG_CONVERGED, CVR_EIG_MAX_ITERS (max_iters iterations done, the block as it is) or CVR_EIG_BREAKDOWN (a sum that is not finite, a
+ * start block that is not of full rank to working precision, a column of W whose norm is zero).  Column c has converged when
+ * ||A x_c - theta_c x_c||_2 <= tol * max(CVR_EIG_EPS23, |theta_c|), with ||x_c||_2 = 1 to rounding: cvr_eigsh's rule with the true residual in place of
+ * the estimate.  The call ends when all k columns have.
+ * Arithmetic, T = the handle's type; every operation below is rounded on its own (no fused multiply-add); scalars are fp64.  Every sum a.b is
+ * cvr_cg_device's fixed tree over the terms double(a_i) * double(b_i), and each sum has its own 1024 partials: no floating-point atomics, no matrix
+ * instructions, the same bits on every call and for every alignment of X.  S = [X W P] has m = 2k columns in the first iteration and when an iteration
+ * falls back (below), and 3k columns otherwise; A S = [AX AW AP] is carried beside it.
+ *   Rayleigh-Ritz step on m columns (host, plain fp64 in this order).  G = S^T S and H = S^T (A S), the lower triangles (entry (i, j), i >= j, is
+ *     S_i . S_j and S_i . (A S)_j).  Cholesky G = L L^T column by column j = 0 .. m-1: s = G_jj, s = s - L_jp * L_jp for p = 0 .. j-1 ascending; a
+ *     pivot s that is not finite, not > 0 or not > tau * G_jj is a bad pivot (with m = 3k, where dropping P is always possible,
+ *     tau = CVR_LOBPCG_PIVOT_F64 = 2^-30 for fp64 handles and CVR_LOBPCG_PIVOT_F32 = 2^-20 for fp32 ones; with m = k or 2k, tau = 0: s / G_jj is the squared sine of the angle between column j and the columns in front, and the
+ *     combination of step 7 loses a factor 1 / sqrt(s / G_jj) of T's precision -- a pivot that is merely positive, 1e-14 say, gives back an A X that
+ *     is no longer A times X); L_jj = sqrt(s); for i > j: t = G_ij, t = t - L_ip * L_jp (p ascending), L_ij = t / L_jj.
+ *     Y = L^-1 H, column by column: t = H_ij (H_ji above the diagonal), t = t - L_ip * Y_pj for p = 0 .. i-1, Y_ij = t / L_ii.  M = Y L^-T, lower
+ *     triangle, row by row: t = Y_ij, t = t - M_ip * L_jp for p = 0 .. j-1, M_ij = t / L_jj.  cvr_sym_eig_host of M gives theta ascending and Z; the k
+ *     wanted pairs are the first k (CVR_EIG_LARGEST: the last k), kept ascending.  C = L^-T Z of those: for i = m-1 .. 0: t = Z_ic,
+ *     t = t - L_pi * C_pc for p = i+1 .. m-1 ascending, C_ic = t / L_ii.
+ *   0. Start: S = [X] (the caller's block, copied), A S by k products through cvr_spmv_device's launch path (bit for bit its y), the Rayleigh-Ritz
+ *      step with m = k, and X = T(S C), AX = T((A S) C) by step 7's sums (no P).  A bad pivot here: CVR_EIG_BREAKDOWN.  The block is orthonormal and
+ *      theta are its Ritz values from here on.
+ *   1. R_c = T(double(AX_c) - theta_c * double(X_c)) and rr_c = R_c . R_c, one launch for all columns.
+ *   2. W_c = M R_c by the object's apply (k applies), or W = R without an object.  There is no locking: all k columns, every iteration.
+ *   3. Twice: h_ic = X_i . W_c for all i and c on the same W; then per value t = double(w_c), t = t - h_0c * double(x_0), ..,
+ *      t = t - h_(k-1)c * double(x_(k-1)), w_c = T(t).  Then ww_c = W_c . W_c and W_c = T(double(W_c) / sqrt(ww_c)); a ww_c that is not finite or not
+ *      > 0 ends the call with CVR_EIG_BREAKDOWN (seen at the read-back of step 6).
+ *   4. AW = A W by k products.
+ *   5. The lower triangles of G and H over the m columns, in fp64.
+ *   6. The single read-back of the iteration: G, H, rr and ww.  The residual norms are sqrt(rr_c): they belong to the X of step 1, the convergence
+ *      test uses them, and so the X returned is the X they belong to.  All converged: CVR_EIG_CONVERGED.  Otherwise, when max_iters iterations are
+ *      done: CVR_EIG_MAX_ITERS (that last pass enqueues step 1 and the read-back only).  Otherwise the Rayleigh-Ritz step; a bad pivot (or an M that
+ *      is not finite) with m = 3k: P is dropped, m = 2k, restarts_without_p counts it, and the step is tried once more on the top-left 2k x 2k blocks
+ *      of the same G and H; a bad pivot at 2k: CVR_EIG_BREAKDOWN.
+ *   7. Into the second set of blocks (the two sets alternate: no kernel reads a column that another workgroup of the same launch may be writing):
+ *      per value u = +0, u = u + C_lc * double(S_l) for l = 0 .. m-1 ascending, X'_c = T(u); AX'_c the same over A S.  P'_c and AP'_c are those sums
+ *      over l = k .. m-1 only (C~, which is C with its first k rows zeroed).  Then pp_c = P'_c . P'_c and, where pp_c is finite and > 0,
+ *      P'_c = T(double(P'_c) / sqrt(pp_c)) and AP'_c likewise (a P'_c that is zero stays zero, and the next iteration falls back).  C is uploaded once
+ *      per iteration.  theta = the new Ritz values; the next iteration has m = 3k.
+ * max_iters = 0 returns the Rayleigh-Ritz vectors of the start block with their residual norms and CVR_EIG_MAX_ITERS (or CVR_EIG_CONVERGED).
+ * iterations = the combinations of step 7 done; spmv_count = k * (1 + the iterations enqueued) and precond_applies = k * (the iterations enqueued)
+ * (with p), where the iteration that finds all columns converged counts as enqueued: its steps 2 to 5 were.  max_rel_residual = the largest
+ * sqrt(rr_c) / max(CVR_EIG_EPS23, |theta_c|).
+ * The buffers of the call are the library's, in one allocation per call: 13 k vectors (two sets of S and A S and R), each of the larger of
+ * info.x_elems and info.yext_elems values, and the partial sums.
+ * Ordering: everything is enqueued on `stream` (NULL = HIP's null stream), which is synchronised once per iteration and once before the call returns:
+ * it cannot be captured in a HIP graph.  One object serves one stream at a time, as in cvr_precond_apply_device.  Makes the handle's device current.
+ * Errors, in this order, before any device work and before the handle is looked at, each CVR_ERR_INVALID with the name in cvr_last_error: null h, X,
+ * evals, resnorms, opt or res; nev outside 1 .. CVR_LOBPCG_MAX_BLOCK; which not one of the two values; max_iters < 0; tol negative or not finite; a
+ * non-zero reserved word (reserved0, then reserved[]); ldx < 1; p != NULL with CVR_EIG_LARGEST.  Then: before cvr_preprocess: CVR_ERR_STATE;
+ * nrows != ncols, n < 3 * nev, ldx < n: CVR_ERR_INVALID; p of another n, type or device than the handle: CVR_ERR_INVALID; no device memory for the
+ * call's buffers: CVR_ERR_NOMEM, nothing allocated. */
+#define CVR_LOBPCG_MAX_BLOCK 8
+#define CVR_LOBPCG_PIVOT_F64 9.313225746154785e-10   /* 2^-30: the smallest pivot / G_jj the Cholesky step accepts, fp64 handles */
+#define CVR_LOBPCG_PIVOT_F32 9.5367431640625e-07      /* 2^-20: fp32 handles */
+#define CVR_EIG_MAX_ITERS    4   /* cvr_lobpcg only: max_iters iterations done before every column converged */
+typedef struct {
+    int32_t nev;              /* k, the columns of the block: 1 .. CVR_LOBPCG_MAX_BLOCK                        */
+    int32_t which;            /* CVR_EIG_SMALLEST (default) or CVR_EIG_LARGEST                                 */
+    int32_t max_iters;        /* >= 0, default 200                                                             */
+    int32_t reserved0;        /* must be 0                                                                     */
+    double  tol;              /* finite, >= 0, default 1e-8                                                    */
+    int32_t reserved[4];      /* must be 0 (CVR_ERR_INVALID otherwise)                                         */
+} cvr_lobpcg_options;     /* 40 bytes */
+typedef struct {
+    int32_t nconv;            /* columns that have converged                                                   */
+    int32_t status;           /* CVR_EIG_CONVERGED, CVR_EIG_MAX_ITERS or CVR_EIG_BREAKDOWN                     */
+    int32_t iterations;       /* combinations (step 7) done                                                    */
+    int32_t spmv_count;       /* products enqueued                                                             */
+    int32_t precond_applies;  /* applies of the object enqueued                                                */
+    int32_t restarts_without_p;          /* iterations that fell back to S = [X W]                              */
+    double  seconds;          /* HIP events around everything enqueued                                         */
+    double  max_rel_residual; /* the largest ||r_c|| / max(eps23, |theta_c|) of the returned block             */
+} cvr_lobpcg_result;      /* 40 bytes */
+/* nev = 1, CVR_EIG_SMALLEST, max_iters = 200, tol = 1e-8, reserved = 0 */
+void cvr_lobpcg_default_options(cvr_lobpcg_options *opt);
+int cvr_lobpcg_device(cvr_handle *h, const cvr_precond *p, void *X_dev, int64_t ldx, double *evals_host, double *resnorms_host, const cvr_lobpcg_options *opt,
+                      cvr_lobpcg_result *res, void *stream);
+/* the same with a host X (column c at X_host + c * ldx): copied up, cvr_lobpcg_device on the handle's stream, the block copied back */
+int cvr_lobpcg(cvr_handle *h, const cvr_precond *p, void *X_host, int64_t ldx, double *evals_host, double *resnorms_host, const cvr_lobpcg_options *opt,
+               cvr_lobpcg_result *res);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
