@@ -193,6 +193,20 @@ class EigResult(C.Structure):
                 ("max_estimate", C.c_double)]
 
 
+SVD_MAX_NCV = 64            # include/cvr_amd.h: CVR_SVD_MAX_NCV
+
+
+class SvdOptions(C.Structure):
+    """cvr_svd_options"""
+    _fields_ = [("nev", C.c_int32), ("ncv", C.c_int32), ("max_restarts", C.c_int32), ("reserved0", C.c_int32), ("tol", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class SvdResult(C.Structure):
+    """cvr_svd_result (status: EIG_CONVERGED, EIG_MAX_RESTARTS, EIG_BREAKDOWN or EIG_INVARIANT)"""
+    _fields_ = [("nconv", C.c_int32), ("status", C.c_int32), ("restarts", C.c_int32), ("spmv_count", C.c_int32), ("seconds", C.c_double),
+                ("max_estimate", C.c_double)]
+
+
 LOBPCG_MAX_BLOCK = 8        # include/cvr_amd.h: CVR_LOBPCG_MAX_BLOCK
 EIG_MAX_ITERS = 4           # include/cvr_amd.h: CVR_EIG_MAX_ITERS (cvr_lobpcg only)
 
@@ -234,6 +248,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
            "cvr_lobpcg_default_options", "cvr_lobpcg_device", "cvr_lobpcg",
+           "cvr_svd_default_options", "cvr_svds_device", "cvr_svds", "cvr_svd_host",
            "cvr_update_values_device", "cvr_update_values", "cvr_update_values_supported", "cvr_x_device", "cvr_y_device", "cvr_stream",
            "cvr_spmv_bench", "cvr_debug_phase_clocks", "cvr_device_copy_bench", "cvr_export_image", "cvr_export_gang", "cvr_comm_info", "cvr_plan_bound", "cvr_plan_chunks", "cvr_plan_selfcheck", "cvr_power_step_selfcheck", "cvr_mm_read", "cvr_mm_free", "cvr_mm_write_bin", "cvr_mm_read_bin",
            "cvr_fill_x", "cvr_csr_spmv_host", "cvr_verdict",
@@ -356,6 +371,13 @@ def lib():
         L.cvr_eigsh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult), C.c_void_p]
         L.cvr_eigsh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult)]
         L.cvr_sym_eig_host.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+        L.cvr_svd_default_options.argtypes = [C.POINTER(SvdOptions)]
+        L.cvr_svd_default_options.restype = None
+        L.cvr_svds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(SvdOptions),
+                                      C.POINTER(SvdResult), C.c_void_p]
+        L.cvr_svds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(SvdOptions),
+                               C.POINTER(SvdResult)]
+        L.cvr_svd_host.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.cvr_lobpcg_default_options.argtypes = [C.POINTER(LobpcgOptions)]
         L.cvr_lobpcg_default_options.restype = None
         L.cvr_lobpcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LobpcgOptions), C.POINTER(LobpcgResult), C.c_void_p]
@@ -856,6 +878,24 @@ def sym_eig_host(a, vectors=True):
     if rc:
         raise CvrError(rc, "cvr_sym_eig_host")
     return (w[:m], z) if vectors else w[:m]
+
+
+def svd_host(b, vectors=True):
+    """the singular value decomposition of b (p x q, p <= q <= SVD_MAX_NCV + 1) by cvr_svd_host.  Returns (s descending, Q of shape (p, p), P of shape
+    (q, p)) with b = Q diag(s) P^T, or s alone without vectors."""
+    b = np.asarray(b, dtype=np.float64)
+    if b.ndim != 2:
+        raise ValueError("b must be a matrix")
+    p, q = b.shape
+    col = np.asfortranarray(b)          # element (i, j) at i + j * p
+    s = np.zeros(max(p, 1))
+    Q = np.zeros((p, p), order="F") if vectors else None
+    P = np.zeros((q, p), order="F") if vectors else None
+    rc = lib().cvr_svd_host(p, q, col.ctypes.data, max(p, 1), s.ctypes.data, None if Q is None else Q.ctypes.data, max(p, 1),
+                            None if P is None else P.ctypes.data, max(q, 1))
+    if rc:
+        raise CvrError(rc, "cvr_svd_host")
+    return (s[:p], Q, P) if vectors else s[:p]
 
 
 def fill_x(n, mode=0):
@@ -1744,6 +1784,60 @@ class CvrMatrix:
             raise CvrError(rc, "cvr_eigsh")
         count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
         return evals[:count], (None if evecs is None else evecs[:count, : self.nrows].T), res
+
+    def _svd_options(self, nev, ncv, tol, max_restarts):
+        opt = SvdOptions()
+        lib().cvr_svd_default_options(C.byref(opt))
+        opt.nev, opt.ncv, opt.tol, opt.max_restarts = int(nev), int(ncv), float(tol), int(max_restarts)
+        return opt
+
+    def _svd_start(self, v0):
+        """the start vector on the host: v0, or a seeded standard normal one, of ncols values"""
+        if v0 is None:
+            return np.random.default_rng(20261021).standard_normal(max(self.ncols, 1)).astype(self.dtype)
+        v0 = np.ascontiguousarray(v0, dtype=self.dtype)
+        if len(v0) < self.ncols:
+            raise ValueError("v0 is shorter than ncols")
+        return v0
+
+    def svds(self, at, v0=None, nev=1, ncv=0, tol=1e-8, max_restarts=100, vectors=True, stream=None):
+        """the nev largest singular values of A, of any shape, and their vectors by thick-restart Golub-Kahan-Lanczos on the device (cvr_svds_device).
+        `at` is a CvrMatrix of A^T (transpose=1 on the same CSR; self for a symmetric A), as in lsqr.  v0: a torch device array of ncols values of
+        the handle's type (anything with data_ptr()), or None: a seeded numpy vector, copied up.  Returns (svals: numpy, descending; U: a torch
+        device array of shape (count, nrows) whose row c is the left vector of svals[c]; V: the same of shape (count, ncols) with the right ones;
+        both None without vectors; SvdResult); count is nev, less at EIG_INVARIANT (nconv) and 0 at EIG_BREAKDOWN.  Synchronises the stream."""
+        import torch
+        opt, res = self._svd_options(nev, ncv, tol, max_restarts), SvdResult()
+        tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+        if v0 is None:
+            v0 = torch.from_numpy(self._svd_start(None)).to("cuda")
+        nr, nc, cols = max(self.nrows, 1), max(self.ncols, 1), max(int(nev), 1)
+        svals = np.zeros(cols)
+        U = torch.zeros((cols, nr), dtype=tdt, device="cuda") if vectors else None
+        V = torch.zeros((cols, nc), dtype=tdt, device="cuda") if vectors else None
+        torch.cuda.synchronize()
+        rc = lib().cvr_svds_device(self._h, at._h, v0.data_ptr(), svals.ctypes.data, None if U is None else U.data_ptr(), nr,
+                                   None if V is None else V.data_ptr(), nc, C.byref(opt), C.byref(res), stream)
+        if rc:
+            raise CvrError(rc, "cvr_svds_device")
+        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        return svals[:count], (None if U is None else U[:count, : self.nrows]), (None if V is None else V[:count, : self.ncols]), res
+
+    def svds_host(self, at, v0=None, nev=1, ncv=0, tol=1e-8, max_restarts=100, vectors=True):
+        """the same through host arrays (cvr_svds).  Returns (svals; U: numpy of shape (nrows, count) with the left vector of svals[c] in column c; V:
+        the same of shape (ncols, count); both None without vectors; SvdResult)."""
+        opt, res = self._svd_options(nev, ncv, tol, max_restarts), SvdResult()
+        v0 = self._svd_start(v0)
+        nr, nc, cols = max(self.nrows, 1), max(self.ncols, 1), max(int(nev), 1)
+        svals = np.zeros(cols)
+        U = np.zeros((cols, nr), dtype=self.dtype) if vectors else None
+        V = np.zeros((cols, nc), dtype=self.dtype) if vectors else None
+        rc = lib().cvr_svds(self._h, at._h, v0.ctypes.data, svals.ctypes.data, None if U is None else U.ctypes.data, nr,
+                            None if V is None else V.ctypes.data, nc, C.byref(opt), C.byref(res))
+        if rc:
+            raise CvrError(rc, "cvr_svds")
+        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        return svals[:count], (None if U is None else U[:count, : self.nrows].T), (None if V is None else V[:count, : self.ncols].T), res
 
     def _lobpcg_options(self, nev, which, tol, max_iters):
         opt = LobpcgOptions()

@@ -1511,6 +1511,107 @@ int cvr_lobpcg_device(cvr_handle *h, const cvr_precond *p, void *X_dev, int64_t 
 int cvr_lobpcg(cvr_handle *h, const cvr_precond *p, void *X_host, int64_t ldx, double *evals_host, double *resnorms_host, const cvr_lobpcg_options *opt,
                cvr_lobpcg_result *res);
 
+/* ---- a few leading singular triplets of any A on the device: thick-restart Golub-Kahan-Lanczos ---------------
+ * cvr_svds_device / cvr_svds find the nev largest singular values of A (nrows x ncols, any shape) with their left and right singular vectors:
+ * Golub-Kahan-Lanczos bidiagonalisation with full two-sided reorthogonalisation (classical Gram-Schmidt applied twice, GMRES's kernels) and a thick
+ * restart on Ritz vectors (Baglama and Reichel, SIAM J. Sci. Comput. 27, 2005; Hernandez, Roman and Tomas, ETNA 31, 2008).  It is the rectangular twin
+ * of cvr_eigsh_device and works on A itself, not on A^T A: the condition number is not squared and nothing fills in.  `a` is any single-GPU handle,
+ * in fp32 or fp64 and in any layout, and `at` a handle of A^T (cvr_options.transpose = 1 on the same CSR; `a` itself for a symmetric A), as in
+ * cvr_lsqr_device: the solver only goes through cvr_spmv_device's launch path of the two handles.
+ * Not in this version, each left out on purpose: the smallest singular values (they need harmonic-Ritz restarts to be useful); shift-and-invert; more
+ * than one GPU; a block variant; an implicit A^T without a second handle.
+ * v0_dev: the start vector, ncols values of the handles' type T in the memory of their device, any alignment of T; it is not written.
+ * svals_host receives the singular values found, nev doubles in descending order (CVR_EIG_INVARIANT: the first nconv, which may be none;
+ * CVR_EIG_BREAKDOWN: nothing is written, to svals_host, U_dev or V_dev; whatever is not written keeps the caller's bytes).  U_dev and V_dev may each
+ * be NULL independently (the same svals); otherwise the left vector of svals_host[c] is column c of U_dev, nrows values of T at U_dev + c * ldu,
+ * ldu >= nrows, and the right one column c of V_dev, ncols values at V_dev + c * ldv, ldv >= ncols, any alignment; values beyond the column length,
+ * and columns beyond the returned count, are never touched.
+ * The buffers of the call are the library's, in one allocation per call: m + 1 right-basis columns v_0 .. v_m whose stride covers a's info.x_elems
+ * and whose element ncols stays 0; m left-basis columns u_0 .. u_(m-1) whose stride covers at's info.x_elems and whose element nrows stays 0; w of
+ * a's info.yext_elems values and z of at's; and nev + (m - nev) / 2 more columns of either kind that take the restart's output (which is then copied
+ * back over the bases: no kernel reads a column that another workgroup of the same launch may be writing).
+ * Arithmetic, T = the handles' type, m = ncv; every operation below is rounded on its own (no fused multiply-add); scalars are fp64.  Every sum a.b is
+ * cvr_cg_device's fixed tree over the terms double(a_i) * double(b_i), and each sum has its own 1024 partials.
+ *   Start: s = v0.v0.  s not finite or not > 0: CVR_EIG_BREAKDOWN, nothing is written.  Otherwise v_0 = T(double(v0) / sqrt(s)).  The first cycle runs
+ *     the steps j = 0 .. m-1; a cycle behind a restart that kept k triplets runs j = k .. m-1.
+ *   Step j, left half: w = A v_j through cvr_spmv_device's launch path of `a` (bit for bit its y).  Then cvr_gmres_device's two Gram-Schmidt passes
+ *     against u_0 .. u_(j-1), unchanged.  Pass 1: h_i = u_i . w for i < j, all on the same w; then t = double(w), t = t - h_0 * double(u_0), ...,
+ *     t = t - h_(j-1) * double(u_(j-1)) in that order, w = T(t) (one rounding to T).  Pass 2, the same on the new w.  For j = 0 there is no column:
+ *     nothing is summed or subtracted and w stays as it is.  ww1 = w.w behind pass 1 and ww = w.w behind pass 2 (for j = 0 the same sum twice: w.w
+ *     of A v_0), as in cvr_eigsh_device; alpha_j = sqrt(ww).  The Gram-Schmidt coefficients only orthogonalise: they do not enter the projected
+ *     matrix.  ww1 or ww not finite: CVR_EIG_BREAKDOWN.  ww <= 0.25 * ww1 -- which alpha_j == 0 satisfies, and for j = 0 nothing else does --: the left
+ *     half is closed at step j ("twice is enough": see cvr_eigsh_device; ww1 is taken behind pass 1 and not in front of it, because in front of it w
+ *     holds its whole component beta_j u_(j-1), or the spike, which says nothing about closure).  Otherwise u_j = T(double(w) / alpha_j).
+ *   Step j, right half: z = A^T u_j through the launch path of `at`; the same two passes against v_0 .. v_j (j + 1 columns); zz1 and zz likewise;
+ *     beta_(j+1) = sqrt(zz); zz1 or zz not finite: CVR_EIG_BREAKDOWN; zz <= 0.25 * zz1: the right half is closed at step j; otherwise
+ *     v_(j+1) = T(double(z) / beta_(j+1)).
+ *   The projected matrix B has p rows (left vectors) and q columns (right vectors), p = q = m at the end of a full cycle.  In the first cycle it is
+ *     upper bidiagonal: B_(j,j) = alpha_j, B_(j,j+1) = beta_(j+1).  Behind a restart that kept k triplets: B_(c,c) = sigma_c for c < k, the spike
+ *     B_(c,k) = s_c in column k, and from there bidiagonal as before (B_(j,j) = alpha_j for j >= k, B_(j,j+1) = beta_(j+1)).  alpha and beta stay in
+ *     a state cell on the device, which the host reads once per cycle; sigma and s are the host's from the restart.
+ *     A right half closed at step j: A^T u_j lies in span(v_0 .. v_j); p = q = j + 1, B is square (beta_(j+1) is not part of it) and its q triplets are
+ *     exact: cvr_eigsh_device's closed-space rule.  A left half closed at step j: A v_j lies in span(u_0 .. u_(j-1)); p = j and q = j + 1, B is the
+ *     j x (j + 1) matrix whose last column holds beta_j in row j - 1 (or the spike, when j = k), and its j triplets are exact.  j = 0 (A v_0 = 0, a
+ *     zero matrix for one): there is nothing to return: CVR_EIG_INVARIANT with nconv = 0, and nothing is written to svals_host, U_dev or V_dev.
+ *   End of a cycle: cvr_svd_host of B gives sigma_0 >= .. >= sigma_(p-1), Q (p x p) and P (q x p) with B = Q diag(sigma) P^T.  The wanted triplets are
+ *     the first min(nev, p).  The estimate of triplet c is e_c = |beta_m * Q[m-1,c]| (a closed space: 0), and the triplet has converged when
+ *     e_c <= tol * max(eps23, sigma_c) with eps23 = CVR_EIG_EPS23.  nconv = the wanted triplets that have converged.  The cycle ends the call
+ *       when nconv == nev, or a half is closed with p >= nev: CVR_EIG_CONVERGED (a closed space: every triplet is exact and nconv = nev);
+ *       when a half is closed with p < nev: CVR_EIG_INVARIANT, the p triplets are returned and nconv = p;
+ *       when restarts == max_restarts: CVR_EIG_MAX_RESTARTS, the wanted triplets as they are, nconv as counted.
+ *     max_estimate = the largest e_c / max(eps23, sigma_c) among the returned triplets (none returned: 0).
+ *   Thick restart: k = nev + min(nconv, (m - nev) / 2) in integers (at most m - 1).  The k leading triplets are kept: sigma_c, s_c = beta_m * Q[m-1,c],
+ *     and per value u = +0, u = u + P[l,c] * double(v_l) for l = 0 .. m-1 ascending (each product and each addition rounded on its own),
+ *     new v_c = T(u); new u_c the same from Q[l,c] and u_l.  The new v_k is the old v_m.  The cycle continues at step k.
+ *   The vectors returned are formed by the same rule from the p left and q right columns into U_dev and V_dev; they are not renormalised.
+ * restarts = the restarts done; spmv_count = the products enqueued through both handles: 2 m in the first cycle and 2 (m - k) in each later one,
+ * whether or not a breakdown or a closed space ends the cycle early (the kernels behind it return without writing).  Per step two products and ten
+ * vector launches (five per half: sums, update, sums, update, norm; step 0 has eight, its left half having no sums); a restart is two launches of
+ * the product and three device copies.
+ * Ordering: everything is enqueued on `stream` (NULL = HIP's null stream), which is synchronised once per cycle and once before the call returns: it
+ * cannot be captured in a HIP graph.  Mutable handles' images are ordered as cvr_spmv_device orders them.  Makes the handles' device current.
+ * Errors, in this order, before any device work and before a handle is looked at, each CVR_ERR_INVALID with the name in cvr_last_error: null a, at,
+ * v0, svals, opt or res; nev < 1; ncv other than 0 or nev + 2 .. CVR_SVD_MAX_NCV; max_restarts < 0; reserved0 not 0; tol negative or not finite; a
+ * non-zero word of reserved[]; ldu < 1 with U; ldv < 1 with V.  Then: either handle before cvr_preprocess: CVR_ERR_STATE.  Then, each
+ * CVR_ERR_INVALID: at not ncols x nrows of a; different value types; different devices; ncv > min(nrows, ncols), or the default ncv below nev + 2
+ * (the matrix too small); ldu < nrows with U; ldv < ncols with V.  No device memory for the call's buffers: CVR_ERR_NOMEM, nothing allocated.
+ * The status codes are cvr_eigsh's (CVR_EIG_CONVERGED, CVR_EIG_MAX_RESTARTS, CVR_EIG_BREAKDOWN, CVR_EIG_INVARIANT). */
+#define CVR_SVD_MAX_NCV 64
+typedef struct {
+    int32_t nev;              /* triplets wanted, >= 1                                                       */
+    int32_t ncv;              /* m: 0 = min(min(nrows, ncols), max(2 * nev + 1, 20), 64), else nev + 2 .. CVR_SVD_MAX_NCV, and <= min(nrows, ncols) */
+    int32_t max_restarts;     /* >= 0; 0: one cycle of m steps                                               */
+    int32_t reserved0;        /* must be 0                                                                   */
+    double  tol;              /* finite, >= 0: triplet c has converged when e_c <= tol * max(eps23, sigma_c) */
+    int32_t reserved[4];      /* must be 0 (CVR_ERR_INVALID otherwise)                                       */
+} cvr_svd_options;        /* 40 bytes */
+typedef struct {
+    int32_t nconv;            /* wanted triplets that have converged (CVR_EIG_INVARIANT: the triplets returned) */
+    int32_t status;           /* CVR_EIG_CONVERGED, CVR_EIG_MAX_RESTARTS, CVR_EIG_BREAKDOWN or CVR_EIG_INVARIANT */
+    int32_t restarts;         /* restarts done                                                               */
+    int32_t spmv_count;       /* products enqueued through both handles, those behind a stop included        */
+    double  seconds;          /* HIP events around everything enqueued                                       */
+    double  max_estimate;     /* the largest e_c / max(eps23, sigma_c) among the returned triplets           */
+} cvr_svd_result;         /* 32 bytes */
+/* nev = 1, ncv = 0, max_restarts = 100, tol = 1e-8, reserved = 0 */
+void cvr_svd_default_options(cvr_svd_options *opt);
+int cvr_svds_device(cvr_handle *a, cvr_handle *at, const void *v0_dev, double *svals_host, void *U_dev, int64_t ldu, void *V_dev, int64_t ldv,
+                    const cvr_svd_options *opt, cvr_svd_result *res, void *stream);
+/* the same with host v0 (ncols values), U (column c at U_host + c * ldu) and V: copied up, cvr_svds_device on a's stream, the vectors copied back */
+int cvr_svds(cvr_handle *a, cvr_handle *at, const void *v0_host, double *svals_host, void *U_host, int64_t ldu, void *V_host, int64_t ldv,
+             const cvr_svd_options *opt, cvr_svd_result *res);
+/* The dense singular value decomposition of the projected matrix, on the host, the sibling of cvr_sym_eig_host: B (p x q, 1 <= p <= q <=
+ * CVR_SVD_MAX_NCV + 1, element (i, j) read at b[i + j * ldb]) = Q diag(s) P^T by the one-sided cyclic Jacobi method of Hestenes by rows (plane
+ * rotations between rows i < j of B until every pair is orthogonal to 2^-52 of the product of its norms; a row that has fallen below 2^-52 of B's
+ * Frobenius norm is a zero singular value and is left alone), plain fp64 in a fixed order: the same input gives the same bits every time.  s receives
+ * the p singular values descending; equal values keep the order of the rows they ended at.  uq (may be NULL) receives Q, p x p orthonormal, the left
+ * vector of s[c] at uq + c * lduq, its sign fixed so that its component of largest magnitude (the first of them) is positive; vp (may be NULL)
+ * receives P, q x p with orthonormal columns, the right vector of s[c] at vp + c * ldvp.  Where s[c] is at most q 2^-52 s[0], the row's direction is
+ * rounding noise: that column of P is the unit vector the other columns leave most of (the first of them), orthogonalised against them twice, so P
+ * stays orthonormal for rank-deficient B.
+ * Errors: p or q out of range, null b or s, ldb < p, lduq < p with uq, ldvp < q with vp, an element that is not finite: CVR_ERR_INVALID. */
+int cvr_svd_host(int32_t p, int32_t q, const double *b, int32_t ldb, double *s, double *uq, int32_t lduq, double *vp, int32_t ldvp);
+
 /* the handle's own device vectors (valid until cvr_destroy) and stream */
 void *cvr_x_device(cvr_handle *h);
 void *cvr_y_device(cvr_handle *h);
