@@ -156,6 +156,15 @@ class AmgMis2Info(C.Structure):
     _fields_ = [("mis2", C.c_int32), ("reserved0", C.c_int32), ("rounds", C.c_int32 * AMG_MAX_LEVELS), ("reserved", C.c_int32 * 8)]
 
 
+AMG_SETUP_PLAIN, AMG_SETUP_SMOOTHED, AMG_SETUP_MIS2 = 0, 1, 2          # include/cvr_amd.h: CVR_AMG_SETUP_*
+AMG_SETUPS = {"plain": AMG_SETUP_PLAIN, "smoothed": AMG_SETUP_SMOOTHED, "mis2": AMG_SETUP_MIS2}
+
+
+class AmgBlockInfo(C.Structure):
+    """cvr_amg_block_info"""
+    _fields_ = [("nvec", C.c_int32), ("setup", C.c_int32), ("buffer_bytes", C.c_int64), ("reserved", C.c_int32 * 8)]
+
+
 class SpGemmInfo(C.Structure):
     """cvr_spgemm_info_t"""
     _fields_ = [("nrows", C.c_int64), ("ncols", C.c_int64), ("inner", C.c_int64), ("nnz", C.c_int64), ("products", C.c_int64), ("max_row_products", C.c_int64),
@@ -241,7 +250,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_amg_smoothed", "cvr_amg_smoothed_setup_host", "cvr_precond_amg_smoothed_info", "cvr_amg_hierarchy_smoothed_info",
            "cvr_precond_amg_export_prolongator", "cvr_amg_hierarchy_export_prolongator",
            "cvr_precond_amg_mis2", "cvr_amg_mis2_setup_host", "cvr_precond_amg_mis2_info", "cvr_amg_hierarchy_mis2_info", "cvr_amg_mis2_aggregate_host",
-           "cvr_amg_mis2_aggregate_device",
+           "cvr_amg_mis2_aggregate_device", "cvr_precond_amg_block", "cvr_precond_amg_block_info",
            "cvr_color_host", "cvr_color_device", "cvr_precond_mcsgs", "cvr_precond_mcsgs_info", "cvr_precond_mcsgs_export",
            "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
@@ -348,6 +357,8 @@ def lib():
         L.cvr_amg_mis2_setup_host.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.cvr_precond_amg_mis2_info.argtypes = [C.c_void_p, C.POINTER(AmgMis2Info)]
         L.cvr_amg_hierarchy_mis2_info.argtypes = [C.c_void_p, C.POINTER(AmgMis2Info)]
+        L.cvr_precond_amg_block.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(CsrView), C.POINTER(AmgOptions), C.c_int32, C.c_double, C.c_int32, C.c_void_p]
+        L.cvr_precond_amg_block_info.argtypes = [C.c_void_p, C.POINTER(AmgBlockInfo)]
         L.cvr_amg_mis2_aggregate_host.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.cvr_amg_mis2_aggregate_device.argtypes = [C.POINTER(CsrView), C.c_double, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int, C.c_void_p]
         L.cvr_color_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -1275,6 +1286,51 @@ class Precond:
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
         return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega, mis2=True)
 
+    @classmethod
+    def amg_block(cls, matrix, rp, ci, vals, nvec, setup="plain", omega=0.0, **options):
+        """cvr_precond_amg_block: the kind-4 object of Precond.amg (setup="plain"; omega is ignored), Precond.amg_smoothed ("smoothed") or
+        Precond.amg_mis2 ("mis2") -- the same hierarchy byte for byte -- built for blocks of up to nvec = K columns, 1 .. 8: apply_multi and
+        CvrMatrix.pcg_multi / pcg_multi_host take it for 1 <= nvec <= K, one V-cycle for all columns.  For K >= 2 `matrix` must have the plain
+        layout (nvec >= 2 at creation).  apply, pcg and pcg_host take it as any kind-4 object."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._amg_block_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), nvec, setup, omega, options)
+
+    @classmethod
+    def amg_block_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, nvec, is_f32=False, setup="plain", omega=0.0, **options):
+        """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
+        return cls._amg_block_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), nvec, setup, omega, options)
+
+    @classmethod
+    def _amg_block_from_view(cls, matrix, view, nvec, setup, omega, options):
+        self = cls()
+        opt = amg_options(**options)
+        if isinstance(setup, str):
+            if setup not in AMG_SETUPS:
+                raise ValueError(f"setup = {setup!r}: one of {sorted(AMG_SETUPS)}")
+            setup = AMG_SETUPS[setup]
+        rc = lib().cvr_precond_amg_block(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), int(setup), float(omega), int(nvec), None)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, "cvr_precond_amg_block")
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        self._matrix = matrix
+        return self
+
+    def amg_block_info(self):
+        """cvr_precond_amg_block_info: an AmgBlockInfo (nvec = K, setup, buffer_bytes); CvrError on an object built another way"""
+        info = AmgBlockInfo()
+        rc = lib().cvr_precond_amg_block_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_amg_block_info")
+        return info
+
     def amg_mis2_info(self):
         """cvr_precond_amg_mis2_info: an AmgMis2Info (mis2, the MIS rounds of every level); all zero of a kind-4 object built another way"""
         info = AmgMis2Info()
@@ -1342,7 +1398,8 @@ class Precond:
 
     def apply_multi(self, R_ptr, ldr, Z_ptr, ldz, nvec, stream=None):
         """asynchronous Z = M^-1 R on row-major device blocks of n rows of ldr / ldz values, 1 <= nvec <= 8 columns
-        (cvr_precond_apply_multi_device); column c of Z is bit for bit apply()'s z for column c of R; the blocks must not overlap"""
+        (cvr_precond_apply_multi_device); column c of Z is bit for bit apply()'s z for column c of R; the blocks must not overlap.  Takes
+        block-Jacobi objects and, for nvec up to the width they were built for, Precond.amg_block's"""
         rc = lib().cvr_precond_apply_multi_device(self._p, R_ptr, ldr, Z_ptr, ldz, nvec, stream)
         if rc:
             raise CvrError(rc, "cvr_precond_apply_multi_device")
@@ -1640,7 +1697,8 @@ class CvrMatrix:
 
     def pcg_multi(self, precond, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, stream=None):
         """cg_multi preconditioned by a Precond object (cvr_pcg_multi_device): Z = M^-1 R by its k-wide apply in place of a diagonal; the
-        blocks and the list of nvec CgResult are cg_multi's.  Column j is bit for bit pcg()'s result for B[:, j] and X[:, j]."""
+        blocks and the list of nvec CgResult are cg_multi's.  Column j is bit for bit pcg()'s result for B[:, j] and X[:, j].  Takes block-Jacobi
+        objects and, for nvec up to the width they were built for, Precond.amg_block's (one V-cycle per step for all columns)."""
         opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(int(nvec), 1))()
         rc = lib().cvr_pcg_multi_device(self._h, precond._p, B_ptr, ldb, X_ptr, ldx, nvec, C.byref(opt), res, stream)
         if rc:
@@ -1648,8 +1706,8 @@ class CvrMatrix:
         return list(res)
 
     def pcg_multi_host(self, precond, B, X0=None, rtol=None, max_iters=None, check_every=0):
-        """the same through host arrays (cvr_pcg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec).  Returns (X of shape
-        (nrows, nvec), list of CgResult)."""
+        """the same through host arrays (cvr_pcg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec), for the objects pcg_multi
+        takes.  Returns (X of shape (nrows, nvec), list of CgResult)."""
         B, X, k = self._host_blocks(B, X0)
         opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(k, 1))()
         rc = lib().cvr_pcg_multi(self._h, precond._p, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)

@@ -19,48 +19,22 @@
 // The device set-up (cvr_precond_amg_mis2: setup_mis2 below) builds the same smoothed object with no level loop on the host: the MIS(2) aggregation
 // and the diagonal are kernels (cvr_amg_mis2.hip), steps 1 - 5 are SmoothedBuild::coarsen, every level's CSR, dinv, agg and P_l stay in device arrays
 // of the object's own, and the exports copy from them when first asked (fetch_level, fetch_prolongator).  DESIGN.md 5.44.
+// cvr_precond_amg_block (cvr_amg_block.hip) builds the same object through this file's constructor with Amg::width = K: the set-up is the one above,
+// untouched; every handle of the object's own is created with cvr_options.nvec = K and every buffer holds K columns (cvr_amg_dev.h).  This file's
+// cycle serves its single-vector calls on those buffers at ld = 1, behind amg_zero_pads_kernel; the K-wide cycle is cvr_amg_block.hip's.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
 #include "cvr_precond.h"
-#include "cvr_amg.h"
+#include "cvr_amg_dev.h"
 #include "cvr_amg_mis2.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
 
-namespace cvrh {
-namespace krylov {
-
-struct AmgLevel {
-    int64_t     n = 0, nc = 0;
-    cvr_handle *h = nullptr;          // level 0: borrowed; a directly solved coarsest level: none
-    bool        own = false;
-    void       *d_dinv = nullptr, *d_agg = nullptr, *d_mrp = nullptr, *d_mem = nullptr;
-    void       *d_r = nullptr, *d_z = nullptr, *d_q = nullptr;
-    cvr_handle *hp = nullptr, *hr = nullptr;          // the smoothed kind above the coarsest level: the object's handles of P_l and R_l ...
-    void       *d_t = nullptr, *d_e = nullptr;        // ... R_l's input and P_l's output
-    void       *d_arp = nullptr, *d_aci = nullptr, *d_ava = nullptr;          // the device set-up (cvr_precond_amg_mis2): the level's CSR (row_ptr[0] = 0) ...
-    void       *d_prp = nullptr, *d_pci = nullptr, *d_pva = nullptr;          // ... and P_l's above the coarsest level, kept for the exports
-};
-
-struct Amg {
-    amg::Hierarchy        H;          // the host's copy: what the info and the export return
-    bool                  on_demand = false;          // the device set-up: a level's arrays come to H when an export first asks (fetch_level, fetch_prolongator)
-    std::vector<AmgLevel> lv;
-    void                 *d_winv = nullptr;
-    int                   products = 0;          // of one apply
-};
-
-}  // namespace krylov
-}  // namespace cvrh
-
 namespace {
 
 // ---- the device half
-
-// the elements of a thread of a level kernel: a grid-stride loop, whatever grid the level was given
-#define CVR_AMG_ELEMENTS(i, n) for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < (n); i += (long long)gridDim.x * kThreads)
 
 // z_i = T(dinv_i * r_i)
 template <typename T>
@@ -153,14 +127,14 @@ __global__ __launch_bounds__(CVR_AMG_MAX_COARSE) void amg_dense_kernel(const T *
     z[i] = (T)s;
 }
 
-// ---- the host half
-
-template <typename... P, typename... A>
-void launch_level(void (*kernel)(P...), long long n, hipStream_t st, A... args)
+// a block object's single-vector calls: the pad slots of the SpMV inputs at ld = 1 (cvr_amg_dev.h); at most 2 * CVR_AMG_MAX_LEVELS of them
+template <typename T>
+__global__ __launch_bounds__(64) void amg_zero_pads_kernel(T *const *__restrict__ pads, int count)
 {
-    const long long blocks = std::min<long long>((n + kThreads - 1) / kThreads, kBlocks);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)std::max<long long>(blocks, 1)), dim3(kThreads), 0, st, args...);
+    if ((int)threadIdx.x < count) *pads[threadIdx.x] = (T)0;
 }
+
+// ---- the host half
 
 constexpr const char *kEntry = "cvr_precond_amg";          // (as the allocation messages of both constructors begin)
 
@@ -289,8 +263,8 @@ struct SmoothedBuild {
         cvr_spgemm_info_t ci;
         if (const int rc = cvr_spgemm_get_info(o.AC.g, &ci)) return rc;
         // the two transfer handles, from the device arrays
-        if (const int rc = make_handle(&dl.hp, pv, p->device, 0)) return rc;
-        if (const int rc = make_handle(&dl.hr, rv, p->device, 0)) return rc;
+        if (const int rc = make_handle(&dl.hp, pv, p->device, 0, p->amg->width)) return rc;
+        if (const int rc = make_handle(&dl.hr, rv, p->device, 0, p->amg->width)) return rc;
         HIP_TRY(hipDeviceSynchronize());          // (the handles' copies are complete before the step's arrays go)
         o.pv = pv;
         o.d_pva = d_pva;
@@ -309,7 +283,7 @@ struct SmoothedBuild {
             if (const int rc = upload_level(f, is_f32, cur_bufs, "level 0's row_ptr", "level 0's col_idx", "level 0's values", &cur)) return rc;
         } else {
             dl.own = true;
-            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
+            if (const int rc = make_handle(&dl.h, cur, p->device, 0, a->width)) return rc;
         }
         const long long n = f.n;
         if (const int rc = upload(kEntry, &dl.d_dinv, f.dinv.data(), f.dinv.size(), "dinv")) return rc;
@@ -340,9 +314,9 @@ struct SmoothedBuild {
     }
 };
 
-size_t x_bytes_of(const cvr_handle *h) { return h->vsz * (size_t)std::max<int64_t>(h->info.x_elems, h->info.ncols + 1); }
+size_t x_bytes_of(const cvr_handle *h, size_t cols) { return h->vsz * cols * (size_t)std::max<int64_t>(h->info.x_elems, h->info.ncols + 1); }
 
-enum class Mode { kPlain, kSmoothed, kMis2 };
+enum class Mode { kPlain = CVR_AMG_SETUP_PLAIN, kSmoothed = CVR_AMG_SETUP_SMOOTHED, kMis2 = CVR_AMG_SETUP_MIS2 };
 const char *entry_of(Mode m) { return m == Mode::kMis2 ? "cvr_precond_amg_mis2" : m == Mode::kSmoothed ? "cvr_precond_amg_smoothed" : "cvr_precond_amg"; }
 
 // row_ptr[i] -= base
@@ -441,8 +415,8 @@ int device_copy(void **out, const void *src, size_t bytes, const char *what, hip
 template <typename T>
 int setup_mis2(cvr_precond *p, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, hipStream_t st, cvr_csr_view *cur_out)
 {
-    const char     *entry = entry_of(Mode::kMis2);
     Amg            *a = p->amg;
+    const char     *entry = a->entry;
     amg::Hierarchy &H = a->H;
     const int       is_f32 = p->is_f32;
     const int64_t   n0 = p->n;
@@ -523,7 +497,7 @@ int setup_mis2(cvr_precond *p, const cvr_csr_view *csr, const cvr_amg_options *o
         H.rounds[level] = rounds;
         if (level > 0) {
             dl.own = true;
-            if (const int rc = make_handle(&dl.h, cur, p->device, 0)) return rc;
+            if (const int rc = make_handle(&dl.h, cur, p->device, 0, a->width)) return rc;
         }
         SmoothedBuild::Coarse o;
         if (const int rc = SmoothedBuild::coarsen<T>(p, dl, cur, n, nc, omega, st, o)) return rc;
@@ -561,7 +535,8 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
 {
     Amg          *a = p->amg;
     const bool    smoothed = mode != Mode::kPlain;
-    const char   *entry = entry_of(mode);
+    const char   *entry = a->entry;
+    const size_t  K = (size_t)std::max<int32_t>(a->width, 1);          // columns per buffer
     SmoothedBuild sb;
     if (mode == Mode::kMis2) {
         if (const int rc = p->is_f32 ? setup_mis2<float>(p, csr, opt, omega, st, &sb.cur) : setup_mis2<double>(p, csr, opt, omega, st, &sb.cur)) return rc;
@@ -601,7 +576,11 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
     } catch (const std::bad_alloc &) {
         return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
     }
-    Scratch s;
+    Scratch    s;
+    const auto buffer = [&](void **out, size_t bytes, const char *what) {          // zeroed once, counted
+        a->buffer_bytes += (int64_t)(bytes ? bytes : 1);
+        return zeroed(kEntry, out, bytes, what);
+    };
     for (size_t l = 0; l < L; l++) {
         const amg::Level &hl = H.lv[l];
         AmgLevel         &dl = a->lv[l];
@@ -612,27 +591,27 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
         else if (smoothed) {
             if (last && !H.coarse_direct) {          // (the levels above it got theirs in their coarsening step)
                 dl.own = true;
-                if (const int rc = make_handle(&dl.h, sb.cur, p->device, 0)) return rc;
+                if (const int rc = make_handle(&dl.h, sb.cur, p->device, 0, a->width)) return rc;
             }
         } else if (!(last && H.coarse_direct)) {
             dl.own = true;
             cvr_csr_view lv{};
             if (const int rc = upload_level(hl, p->is_f32, s, "a level's row_ptr", "a level's col_idx", "a level's values", &lv)) return rc;
-            if (const int rc = make_handle(&dl.h, lv, p->device, 0)) return rc;
+            if (const int rc = make_handle(&dl.h, lv, p->device, 0, a->width)) return rc;
         }
         if (smoothed) {
             if (last && !dl.d_dinv)          // (the device set-up has left every level's there)
                 if (const int rc = upload(kEntry, &dl.d_dinv, hl.dinv.data(), hl.dinv.size(), "dinv")) return rc;
             // r is R_(l-1)'s output, z is P_(l-1)'s input beside A_l's, t is R_l's input, e is P_l's output; zeroed: the pad slots stay 0
             const AmgLevel *up = l > 0 ? &a->lv[l - 1] : nullptr;
-            size_t          rb = vsz * (size_t)std::max<int64_t>(hl.n, 1), zb = dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1);
-            if (up) rb = std::max(rb, y_ext_bytes(up->hr)), zb = std::max(zb, x_bytes_of(up->hp));
-            if (const int rc = zeroed(kEntry, &dl.d_r, rb, "r")) return rc;
-            if (const int rc = zeroed(kEntry, &dl.d_z, zb, "z")) return rc;
-            if (const int rc = zeroed(kEntry, &dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+            size_t          rb = vsz * K * (size_t)std::max<int64_t>(hl.n, 1), zb = dl.h ? x_ext_bytes(dl.h, (int)K) : vsz * K * (size_t)(hl.n + 1);
+            if (up) rb = std::max(rb, y_ext_bytes(up->hr, (int)K)), zb = std::max(zb, x_bytes_of(up->hp, K));
+            if (const int rc = buffer(&dl.d_r, rb, "r")) return rc;
+            if (const int rc = buffer(&dl.d_z, zb, "z")) return rc;
+            if (const int rc = buffer(&dl.d_q, dl.h ? y_ext_bytes(dl.h, (int)K) : vsz, "q")) return rc;
             if (!last) {
-                if (const int rc = zeroed(kEntry, &dl.d_t, x_bytes_of(dl.hr), "t")) return rc;
-                if (const int rc = zeroed(kEntry, &dl.d_e, y_ext_bytes(dl.hp), "e")) return rc;
+                if (const int rc = buffer(&dl.d_t, x_bytes_of(dl.hr, K), "t")) return rc;
+                if (const int rc = buffer(&dl.d_e, y_ext_bytes(dl.hp, (int)K), "e")) return rc;
             }
             continue;
         }
@@ -643,9 +622,22 @@ int build(cvr_precond *p, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_
             if (const int rc = upload(kEntry, &dl.d_mem, hl.mem.data(), sizeof(int32_t) * hl.mem.size(), "the aggregates' members")) return rc;
         }
         // r, z, q, zeroed: z[n] is the pad slot of an SpMV input and is never written again
-        if (const int rc = zeroed(kEntry, &dl.d_r, vsz * (size_t)std::max<int64_t>(hl.n, 1), "r")) return rc;
-        if (const int rc = zeroed(kEntry, &dl.d_z, dl.h ? x_ext_bytes(dl.h) : vsz * (size_t)(hl.n + 1), "z")) return rc;
-        if (const int rc = zeroed(kEntry, &dl.d_q, dl.h ? y_ext_bytes(dl.h) : vsz, "q")) return rc;
+        if (const int rc = buffer(&dl.d_r, vsz * K * (size_t)std::max<int64_t>(hl.n, 1), "r")) return rc;
+        if (const int rc = buffer(&dl.d_z, dl.h ? x_ext_bytes(dl.h, (int)K) : vsz * K * (size_t)(hl.n + 1), "z")) return rc;
+        if (const int rc = buffer(&dl.d_q, dl.h ? y_ext_bytes(dl.h, (int)K) : vsz, "q")) return rc;
+    }
+    if (a->width >= 2) {          // the pads of the single-vector calls: element n of every z and t (at ld = K a block call writes there)
+        std::vector<void *> pads;
+        try {
+            for (size_t l = 0; l < L; l++) {
+                pads.push_back(static_cast<uint8_t *>(a->lv[l].d_z) + vsz * (size_t)a->lv[l].n);
+                if (a->lv[l].d_t) pads.push_back(static_cast<uint8_t *>(a->lv[l].d_t) + vsz * (size_t)a->lv[l].n);
+            }
+        } catch (const std::bad_alloc &) {
+            return fail(CVR_ERR_NOMEM, "%s: out of host memory", entry);
+        }
+        a->npads = (int)pads.size();
+        if (const int rc = upload(kEntry, &a->d_pads, pads.data(), sizeof(void *) * pads.size(), "the pad list")) return rc;
     }
     if (H.coarse_direct)
         if (const int rc = upload(kEntry, &a->d_winv, H.winv.data(), H.winv.size(), "the coarsest level's inverse")) return rc;
@@ -671,6 +663,7 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
     const size_t    L = a->lv.size();
     const int       sweeps = a->H.opt.sweeps;
     const long long n = pc->n;
+    if (a->npads > 0) hipLaunchKernelGGL(amg_zero_pads_kernel<T>, dim3(1), dim3(64), 0, st, static_cast<T *const *>(a->d_pads), a->npads);
     with_flags([&](auto AL) { launch(precond_copy_in_kernel<T, AL>, st, r, static_cast<T *>(a->lv[0].d_r), n); }, al);
     HIP_TRY(hipGetLastError());
     for (size_t l = 0; l + 1 < L; l++) {
@@ -704,6 +697,11 @@ int enqueue_cycle(const cvr_precond *pc, const T *r, bool al, hipStream_t st)
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
+
+}  // namespace
+
+namespace cvrh {
+namespace krylov {
 
 int amg_apply_any(const cvr_precond *p, const void *r, void *z, hipStream_t st)
 {
@@ -745,27 +743,28 @@ void amg_release(cvr_precond *p)
             if (buf) (void)hipFree(buf);
     }
     if (a->d_winv) (void)hipFree(a->d_winv);
+    if (a->d_pads) (void)hipFree(a->d_pads);
     delete a;
     p->amg = nullptr;
 }
-
-}  // namespace
-
-namespace cvrh {
-namespace krylov {
+template int amg_cg_apply<float>(const cvr_precond *, const float *, float *, float *, double *, const void *, bool, hipStream_t, int *);
+template int amg_cg_apply<double>(const cvr_precond *, const double *, double *, double *, double *, const void *, bool, hipStream_t, int *);
 
 PrecondOps kAmgOps = {kPrecondAmg, "AMG", amg_apply_any, amg_release, amg_cg_apply<float>, amg_cg_apply<double>};
 
 }  // namespace krylov
 }  // namespace cvrh
 
-namespace {
+namespace cvrh {
+namespace krylov {
 
-// cvr_precond_amg, cvr_precond_amg_smoothed and cvr_precond_amg_mis2: one constructor, the smoothed kinds with their omega as given
-int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, Mode mode, double omega, void *stream)
+// cvr_precond_amg, cvr_precond_amg_smoothed and cvr_precond_amg_mis2 (width = 0): one constructor, the smoothed kinds with their omega as given;
+// cvr_precond_amg_block (width = K): the same behind its own checks of setup and nvec, with its name in the messages and the level-0 handle's checks
+int amg_construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, int32_t setup, double omega, int32_t width, void *stream)
 {
+    const Mode  mode = (Mode)setup;
     const bool  smoothed = mode != Mode::kPlain;
-    const char *entry = entry_of(mode);
+    const char *entry = width > 0 ? "cvr_precond_amg_block" : entry_of(mode);
     if (!out || !h || !csr) return fail(CVR_ERR_INVALID, "null argument");
     *out = nullptr;
     cvr_amg_options o;
@@ -780,6 +779,12 @@ int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const c
     if (const int rc = check_square_preprocessed(h, entry, "an AMG preconditioner needs")) return rc;
     if (h->info.nrows != csr->nrows) return fail(CVR_ERR_INVALID, "%s: the view has nrows = %lld, the handle nrows = %lld", entry, (long long)csr->nrows, (long long)h->info.nrows);
     if ((csr->is_f32 != 0) != (h->vsz == 4)) return fail(CVR_ERR_INVALID, "%s: the view's type is %s, the handle's %s", entry, csr->is_f32 ? "fp32" : "fp64", h->vsz == 4 ? "fp32" : "fp64");
+    if (width >= 2) {          // level 0's products are k-wide through the borrowed handle
+        if (!cvr_spmm_supported(h))
+            return fail(CVR_ERR_STATE, "%s: nvec = %d, but the handle's image is not the plain layout; create it with cvr_options.nvec >= 2 for level 0's k-wide products", entry, width);
+        if ((uint64_t)(h->info.ncols + 1) * (uint64_t)width * h->vsz > 0xffffffffull)
+            return fail(CVR_ERR_INVALID, "%s: a block of %lld rows of %d values exceeds the 4 GiB a buffer descriptor addresses", entry, (long long)(h->info.ncols + 1), width);
+    }
     if (!csr->arrays_on_device) {
         if (const int rc = check_csr(csr, true)) return rc;
         if (const int rc = amg::check_structure(csr->nrows, csr->row_ptr, csr->col_idx, entry)) return rc;
@@ -794,34 +799,39 @@ int construct(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const c
         return fail(CVR_ERR_NOMEM, "out of host memory");
     }
     p->kind = kPrecondAmg;
-    p->ops = &kAmgOps;
+    p->ops = width > 0 ? &kAmgBlockOps : &kAmgOps;
+    p->multi_width = width;
     p->device = h->device;
     p->n = csr->nrows;
     p->bs = 0;
     p->is_f32 = csr->is_f32 ? 1 : 0;
     p->amg = a;
+    a->entry = entry;
+    a->width = width;
+    a->setup = setup;
     if (const int rc = build(p, h, csr, &o, mode, omega, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
     return CVR_OK;
 }
 
-}  // namespace
+}  // namespace krylov
+}  // namespace cvrh
 
 extern "C" {
 
 int cvr_precond_amg(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, void *stream)
 {
-    return construct(out, h, csr, opt, Mode::kPlain, 0.0, stream);
+    return amg_construct(out, h, csr, opt, CVR_AMG_SETUP_PLAIN, 0.0, 0, stream);
 }
 
 int cvr_precond_amg_smoothed(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream)
 {
-    return construct(out, h, csr, opt, Mode::kSmoothed, omega, stream);
+    return amg_construct(out, h, csr, opt, CVR_AMG_SETUP_SMOOTHED, omega, 0, stream);
 }
 
 int cvr_precond_amg_mis2(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, double omega, void *stream)
 {
-    return construct(out, h, csr, opt, Mode::kMis2, omega, stream);
+    return amg_construct(out, h, csr, opt, CVR_AMG_SETUP_MIS2, omega, 0, stream);
 }
 
 int cvr_precond_amg_mis2_info(const cvr_precond *p, cvr_amg_mis2_info *info)

@@ -10,8 +10,8 @@
 // unrolled over the kSpmmBlock columns there can be, so a column's accumulators and scalars are registers; nvec itself is a runtime argument.
 // Every column has its own state cell.  A column that has stopped is not written any more (its bit in the kernels' `live` mask is clear; its
 // values are still loaded and computed with where they share a sub-block with a live column, and dropped); the others go on.
-// The preconditioner is an argument of the one solve function: none, the diagonal opt->minv_dev, or a block-Jacobi object, whose k-wide apply
-// (cvr_pcg_multi.hip's pcgm_apply_kernel through cvr_precond.h's block_jacobi_cgm_apply) is enqueued between cgm_update_kernel<T, false, LV, AL> and
+// The preconditioner is an argument of the one solve function: none, the diagonal opt->minv_dev, or an object whose kind has a k-wide apply
+// (PrecondOps::cgm_apply: block-Jacobi's pcgm_apply_kernel, cvr_pcg_multi.hip; a cvr_precond_amg_block object's cycle, cvr_amg_block.hip), which is enqueued between cgm_update_kernel<T, false, LV, AL> and
 // cgm_direction_kernel<T, true, LV>: column j then gets bit for bit what cvr_pcg_device gives for b = B[:, j], x0 = X[:, j].
 // The host side is cvr_krylov.h's driver: the cells and the kernels are in cvr_cg_multi_kernels.h, this file adds the step and the read-back of all
 // columns.
@@ -51,28 +51,31 @@ using namespace cvrh::krylov;
 
 namespace {
 
-// the object's apply on the call's blocks: Z = W R and r . z per column; at the start P = Z too
+// the object's apply on the call's blocks, through its kind's table: Z = M R and r . z per column; at the start P = Z too
 template <typename T>
-hipError_t launch_apply(const Workspace<T> &w, const Call<T> &c, const cvr_precond *pc, bool start, hipStream_t st)
+int launch_apply(const Workspace<T> &w, const Call<T> &c, const cvr_precond *pc, bool start, hipStream_t st, int *spmms)
 {
-    return block_jacobi_cgm_apply<T>(pc, w.r, w.z, w.p, c.n, c.nvec, c.lv, w.part, w.cells, start, st);
+    return precond_cgm_apply<T>(pc, w.r, w.z, w.p, c.n, c.nvec, c.lv, w.part, w.cells, start, st, spmms);
 }
 
 // the three vector launches of step k (the product Q = A P is enqueued in front of them), four with an object: its apply in front of the direction.
 // Without a preconditioner z is r.
 template <typename T>
-hipError_t launch_step(const Workspace<T> &w, const Call<T> &c, const cvr_precond *pc, int k, hipStream_t st)
+int launch_step(const Workspace<T> &w, const Call<T> &c, const cvr_precond *pc, int k, hipStream_t st, int *spmms)
 {
     with_flags([&](auto LV) { launch(cgm_pq_kernel<T, LV>, st, w.p, w.q, c.n, c.nvec, w.part_pq, w.cells); }, c.lv);
     with_flags([&](auto PRE, auto LV, auto AL) { launch(cgm_update_kernel<T, PRE, LV, AL>, st, c.x, c.ldx, w.r, w.z, w.p, w.q, c.minv, c.n, c.nvec, w.part_pq, w.part, w.cells, k); },
                c.minv != nullptr, c.lv, c.al);
-    if (pc)
-        if (const hipError_t e = launch_apply(w, c, pc, false, st)) return e;
+    if (pc) {
+        HIP_TRY(hipGetLastError());
+        if (const int rc = launch_apply(w, c, pc, false, st, spmms)) return rc;
+    }
     with_flags([&](auto PRE, auto LV) { launch(cgm_direction_kernel<T, PRE, LV>, st, w.p, PRE ? w.z : w.r, c.n, c.nvec, w.part, w.cells, k, c.rtol); }, w.z != nullptr, c.lv);
-    return hipGetLastError();
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
 }
 
-// cvr_krylov.h's driver with the block's start, step and cells.  pc: a block-Jacobi object or null; with one, minv is null (the entry points see to it)
+// cvr_krylov.h's driver with the block's start, step and cells.  pc: an object behind check_multi, or null; with one, minv is null (the entry points see to it)
 template <typename T>
 int cg_multi_solve(cvr_handle *h, const cvr_precond *pc, bool single, const T *B, int64_t ldb, T *X, int64_t ldx, int32_t nvec, const cvr_cg_options *opt,
                    cvr_cg_result *res, hipStream_t st)
@@ -97,7 +100,8 @@ int cg_multi_solve(cvr_handle *h, const cvr_precond *pc, bool single, const T *B
     int spmms = 1;
     with_flags([&](auto PRE, auto LV, auto AL) { launch(cgm_init_kernel<T, PRE, LV, AL>, st, c.b, c.ldb, c.minv, w.q, w.r, w.z, w.p, c.n, c.nvec, w.part); }, c.minv != nullptr, c.lv, c.al);
     HIP_TRY(hipGetLastError());
-    if (pc) HIP_TRY(launch_apply(w, c, pc, true, st));
+    if (pc)
+        if (const int rc = launch_apply(w, c, pc, true, st, &spmms)) return rc;
     hipLaunchKernelGGL(cgm_check_kernel, dim3(1), dim3(kThreads), 0, st, w.part, has_z ? 1 : 0, opt->rtol, nvec, w.cells);
     HIP_TRY(hipGetLastError());
 
@@ -107,8 +111,7 @@ int cg_multi_solve(cvr_handle *h, const cvr_precond *pc, bool single, const T *B
         [&](int k) -> int {
             if (const int rc = product(h, single, w, nvec, st)) return rc;
             spmms++;
-            HIP_TRY(launch_step(w, c, pc, k, st));
-            return CVR_OK;
+            return launch_step(w, c, pc, k, st, &spmms);
         },
         [&](int, bool *stopped) -> int {          // stopped: every column has
             if (const int rc = read_cell(cells, w.cells, sizeof(CgCell) * (size_t)nvec, st)) return rc;
@@ -153,7 +156,7 @@ int check_pcg_multi(const cvr_handle *h, const cvr_precond *p, const void *B, co
     if (const int rc = check_block_args(nvec, ldb, ldx)) return rc;
     if (const int rc = check_handle(h, nvec, nvec == 1 && ldb == 1 && ldx == 1, "cvr_pcg_multi")) return rc;
     if (const int rc = check_precond_pair(h, p, "cvr_pcg_multi")) return rc;
-    return check_block_jacobi(p, "cvr_pcg_multi");
+    return check_multi(p, nvec, "cvr_pcg_multi");
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
-// cvr_pcg_multi.hip -- the block-Jacobi object with several right-hand sides (include/cvr_amd.h: cvr_precond_apply_multi_device; cvr_pcg_multi_device
-// and cvr_pcg_multi are cvr_cg_multi.hip's): Z = W R for row-major blocks of up to kSpmmBlock columns, on its own and in the form the batched solver enqueues.
+// cvr_pcg_multi.hip -- the block-Jacobi object with several right-hand sides (include/cvr_amd.h: cvr_precond_apply_multi_device, the entry point of
+// every kind whose table has apply_multi; cvr_pcg_multi_device and cvr_pcg_multi are cvr_cg_multi.hip's): Z = W R for row-major blocks of up to kSpmmBlock columns, on its own and in the form the batched solver enqueues.
 //   precond_apply_multi_kernel   Z = W R
 //   pcgm_apply_kernel            the same inside the solver, with per column the partial sums of r . z (set 1 of cgm_direction_kernel<T, true, LV>) and,
 //                                at the start, P = Z
@@ -8,7 +8,7 @@
 // all columns, row k bs + j of R comes in sub-blocks of kPack<T> columns (CVR_CG_MULTI_SUBBLOCKS), and every column keeps its own fp64 sum in a
 // register: s = t_0, then s += t_j, each product and addition rounded on its own -- per column the operations of apply_sums in its order, so column c
 // of Z has the bits cvr_precond_apply_device gives for column c of R.
-// The solver is cvr_cg_multi.hip's cg_multi_solve, which enqueues pcgm_apply_kernel through block_jacobi_cgm_apply (cvr_precond.h); this file launches
+// The solver is cvr_cg_multi.hip's cg_multi_solve, which enqueues pcgm_apply_kernel through kBlockJacobiOps' cgm_apply (cvr_precond.h); this file launches
 // no cgm_* kernel and holds no solve loop (cvr_cg_multi_kernels.h is included for the cells, the column walk and the constants).
 #include "cvr_cg_multi_kernels.h"
 #include "cvr_precond.h"
@@ -138,14 +138,22 @@ namespace cvrh {
 namespace krylov {
 
 template <typename T>
-hipError_t block_jacobi_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st)
+int block_jacobi_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st, int *)
 {
     with_flags([&](auto START, auto LV) { launch(pcgm_apply_kernel<T, START, LV>, st, static_cast<const T *>(pc->d_w), (int)pc->bs, R, Z, P, n, nvec, part, static_cast<const CgCell *>(cells)); },
                start, lv);
-    return hipGetLastError();
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
 }
-template hipError_t block_jacobi_cgm_apply<float>(const cvr_precond *, const float *, float *, float *, long long, int, bool, double *, const void *, bool, hipStream_t);
-template hipError_t block_jacobi_cgm_apply<double>(const cvr_precond *, const double *, double *, double *, long long, int, bool, double *, const void *, bool, hipStream_t);
+template int block_jacobi_cgm_apply<float>(const cvr_precond *, const float *, float *, float *, long long, int, bool, double *, const void *, bool, hipStream_t, int *);
+template int block_jacobi_cgm_apply<double>(const cvr_precond *, const double *, double *, double *, long long, int, bool, double *, const void *, bool, hipStream_t, int *);
+
+int block_jacobi_apply_multi(const cvr_precond *p, const void *R, int64_t ldr, void *Z, int64_t ldz, int32_t nvec, hipStream_t st)
+{
+    if (p->n == 0) return CVR_OK;
+    HIP_TRY(p->is_f32 ? launch_apply_multi<float>(p, R, ldr, Z, ldz, nvec, st) : launch_apply_multi<double>(p, R, ldr, Z, ldz, nvec, st));
+    return CVR_OK;
+}
 
 }  // namespace krylov
 }  // namespace cvrh
@@ -158,12 +166,10 @@ int cvr_precond_apply_multi_device(const cvr_precond *p, const void *R_dev, int6
     if (R_dev == Z_dev) return fail(CVR_ERR_INVALID, "cvr_precond_apply_multi_device: R and Z are the same block");
     if (nvec < 1 || nvec > kCols) return fail(CVR_ERR_INVALID, "nvec = %d: 1 to %d columns per call", nvec, kCols);
     if (ldr < nvec || ldz < nvec) return fail(CVR_ERR_INVALID, "ldr = %lld, ldz = %lld: each must be >= nvec = %d", (long long)ldr, (long long)ldz, nvec);
-    if (const int rc = check_block_jacobi(p, "cvr_precond_apply_multi_device")) return rc;
+    if (const int rc = check_multi(p, nvec, "cvr_precond_apply_multi_device")) return rc;
     if (p->n == 0) return CVR_OK;
     HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(p->is_f32 ? launch_apply_multi<float>(p, R_dev, ldr, Z_dev, ldz, nvec, (hipStream_t)stream)
-                      : launch_apply_multi<double>(p, R_dev, ldr, Z_dev, ldz, nvec, (hipStream_t)stream));
-    return CVR_OK;
+    return p->ops->apply_multi(p, R_dev, ldr, Z_dev, ldz, nvec, (hipStream_t)stream);
 }
 
 }  // extern "C"

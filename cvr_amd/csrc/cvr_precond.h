@@ -6,7 +6,7 @@
 // r . z kernels the kinds share, the checks every preconditioned entry point makes, and the helpers the constructors build with.  How W is built and
 // laid out: cvr_precond.hip's head.  The Chebyshev kind: cvr_chebyshev.hip's head.  The ILU(0) kind (two level-scheduled triangular sweeps, launches
 // of their own in every solver): cvr_ilu0.hip's head.  The FSAI kind (two products on the SpMV path through two handles of the object's own):
-// cvr_fsai.hip's head.  The AMG kind (one V-cycle: a handle per level, l1-Jacobi sweeps, a segmented sum down and a gather up): cvr_amg.hip's head.  The multicolour SGS kind (two sweeps of one launch per colour of a graph colouring): cvr_mcsgs.hip's head.
+// cvr_fsai.hip's head.  The AMG kind (one V-cycle: a handle per level, l1-Jacobi sweeps, a segmented sum down and a gather up): cvr_amg.hip's head; its K-wide cycle: cvr_amg_block.hip's.  The multicolour SGS kind (two sweeps of one launch per colour of a graph colouring): cvr_mcsgs.hip's head.
 // Where a new kind plugs in: DESIGN.md 5.43.
 #pragma once
 #include "cvr_krylov.h"
@@ -20,7 +20,7 @@ namespace krylov {
 struct Chebyshev;     // cvr_chebyshev.hip: the borrowed handle, the polynomial and the three buffers
 struct Ilu0;          // cvr_ilu0.hip: the factors, the two schedules and the launch plans
 struct Fsai;          // cvr_fsai.hip: W's pattern, Wa and Wb, the two handles and the three buffers
-struct Amg;           // cvr_amg.hip: the hierarchy, a handle and three buffers per level
+struct Amg;           // cvr_amg_dev.h: the hierarchy, a handle and three buffers per level
 struct McSgs;         // cvr_mcsgs.hip: the colouring, the two parts in perm order, the diagonal and one buffer
 
 // What a kind does behind the entry points all kinds share.
@@ -29,6 +29,11 @@ struct McSgs;         // cvr_mcsgs.hip: the colouring, the two parts in perm ord
 //   cg_apply  "z = M r inside a CG solve", enqueued on `st`: z and the partial sums of r . z into part_rz (set 1 of cg_direction_kernel<T, true>);
 //             start: before the state cell exists, p = z as well; otherwise nothing is written once the cell (a CgCell) holds a stop.  r, z and p are
 //             the solver's buffers; *spmvs grows by the products enqueued; the solver's T is the object's type (check_precond_pair)
+//   apply_multi  Z = M R for a row-major block of nvec columns (cvr_precond_apply_multi_device behind its checks; n == 0 included)
+//   cgm_apply    cg_apply for the blocks of batched CG (ld = nvec each): Z = M R and per column the partial sums of r . z into that column's set 1
+//                of `part`; lv: the solver's blocks take 16-byte packets; cells: the columns' CgCells; start: P = Z as well, else a column whose
+//                cell holds a stop is not written
+//   The last three are null where a kind has no block form: the two multi entry points decline such an object (decline_multi).
 struct PrecondOps {
     int32_t     kind;
     const char *name;          // as the error texts spell it
@@ -36,6 +41,11 @@ struct PrecondOps {
     void (*release)(cvr_precond *);
     int (*cg_apply_f32)(const cvr_precond *, const float *r, float *z, float *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
     int (*cg_apply_f64)(const cvr_precond *, const double *r, double *z, double *p, double *part_rz, const void *cell, bool start, hipStream_t st, int *spmvs);
+    int (*apply_multi)(const cvr_precond *, const void *R, int64_t ldr, void *Z, int64_t ldz, int32_t nvec, hipStream_t st) = nullptr;
+    int (*cgm_apply_f32)(const cvr_precond *, const float *R, float *Z, float *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st,
+                         int *spmvs) = nullptr;
+    int (*cgm_apply_f64)(const cvr_precond *, const double *R, double *Z, double *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st,
+                         int *spmvs) = nullptr;
 };
 // each in its kind's file; written nowhere (not declared const: a const table would be compiled for the device too, where its functions do not exist)
 CVR_HIDDEN extern PrecondOps kBlockJacobiOps, kChebyshevOps, kIlu0Ops, kFsaiOps, kAmgOps, kMcSgsOps;
@@ -50,6 +60,7 @@ struct cvr_precond {
     int32_t  bs = 1, is_f32 = 0;
     void    *d_w = nullptr;          // nblocks * bs * bs values of T, every block transposed
     int32_t  kind = kPrecondBlockJacobi;
+    int32_t  multi_width = 0;          // an object built for blocks of at most this many columns (cvr_precond_amg_block); 0: whatever the entry point takes
     const cvrh::krylov::PrecondOps *ops = nullptr;          // the kind's table: every constructor sets it beside `kind`
     cvrh::krylov::Chebyshev        *cheb = nullptr;
     cvrh::krylov::Ilu0             *ilu = nullptr;
@@ -159,11 +170,24 @@ inline int check_precond_pair(const cvr_handle *h, const cvr_precond *p, const c
     return CVR_OK;
 }
 
-// ... and, behind both, the entry points that take block-Jacobi objects only
+// ... and, behind both, the entry point that takes block-Jacobi objects only (cvr_precond_export)
+inline int decline_not_block_jacobi(const cvr_precond *p, const char *entry)
+{
+    return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (%s): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, p->ops->name, kPrecondBlockJacobi);
+}
 inline int check_block_jacobi(const cvr_precond *p, const char *entry)
 {
-    if (p->kind != kPrecondBlockJacobi)
-        return fail(CVR_ERR_STATE, "%s: the preconditioner is of kind %d (%s): this entry point takes block-Jacobi objects (kind %d) only", entry, p->kind, p->ops->name, kPrecondBlockJacobi);
+    if (p->kind != kPrecondBlockJacobi) return decline_not_block_jacobi(p, entry);
+    return CVR_OK;
+}
+
+// ... or the objects whose table has the block form: an object without it is declined in the words above (block-Jacobi was the first kind with one,
+// and the words are pinned), an object built for fewer columns than the call's is CVR_ERR_INVALID
+inline int check_multi(const cvr_precond *p, int32_t nvec, const char *entry)
+{
+    if (!p->ops->apply_multi || !p->ops->cgm_apply_f32 || !p->ops->cgm_apply_f64) return decline_not_block_jacobi(p, entry);
+    if (p->multi_width > 0 && nvec > p->multi_width)
+        return fail(CVR_ERR_INVALID, "%s: nvec = %d, but the preconditioner was built for blocks of at most %d columns (cvr_precond_amg_block's nvec)", entry, nvec, p->multi_width);
     return CVR_OK;
 }
 
@@ -184,6 +208,13 @@ static int precond_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, doubl
 {
     if constexpr (sizeof(T) == 4) return pc->ops->cg_apply_f32(pc, r, z, p, part_rz, cell, start, st, spmvs);
     else return pc->ops->cg_apply_f64(pc, r, z, p, part_rz, cell, start, st, spmvs);
+}
+// ... and batched CG's: the kind's cgm_apply (behind check_multi)
+template <typename T>
+static int precond_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st, int *spmvs)
+{
+    if constexpr (sizeof(T) == 4) return pc->ops->cgm_apply_f32(pc, R, Z, P, n, nvec, lv, part, cells, start, st, spmvs);
+    else return pc->ops->cgm_apply_f64(pc, R, Z, P, n, nvec, lv, part, cells, start, st, spmvs);
 }
 
 // cvr_chebyshev.hip: kChebyshevOps' apply and release.  (The two have been names the library exports since they were cvr_precond.hip's calls into
@@ -206,10 +237,10 @@ template <typename T, typename R> CVR_HIDDEN int ilu0_apply(const cvr_precond *p
 // ... and what GMRES does with M^-1 u: x_i = T(double(x_i) + double(zu_i)) under the gate (one launch on the solvers' grid); al: x is 16-byte aligned
 template <typename T> CVR_HIDDEN int ilu0_add_to_x(T *x, const T *zu, long long n, const Ilu0Gate &gate, bool al, hipStream_t st);
 
-// cvr_pcg_multi.hip: block-Jacobi's cg_apply for the blocks of batched CG, Z = W R and per column the partial sums of r . z into that column's
-// set 1 of `part`; lv: the library's blocks take 16-byte packets.  cells: the columns' CgCells
+// cvr_pcg_multi.hip: kBlockJacobiOps' apply_multi and cgm_apply (Z = W R; the products counted: none)
+CVR_HIDDEN int block_jacobi_apply_multi(const cvr_precond *p, const void *R, int64_t ldr, void *Z, int64_t ldz, int32_t nvec, hipStream_t st);
 template <typename T>
-CVR_HIDDEN hipError_t block_jacobi_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st);
+CVR_HIDDEN int block_jacobi_cgm_apply(const cvr_precond *pc, const T *R, T *Z, T *P, long long n, int nvec, bool lv, double *part, const void *cells, bool start, hipStream_t st, int *spmvs);
 
 // ---- what the constructors build with (cvr_precond.hip).  `entry`: the constructor's name as its messages begin
 
@@ -249,8 +280,9 @@ struct CVR_HIDDEN HostCsr {
 };
 CVR_HIDDEN int stage_host(const char *entry, const cvr_csr_view *c, HostCsr &h, bool with_values, hipStream_t st);
 
-// a handle of an object's own: cvr_create + cvr_preprocess of a view of device arrays with the default options on the object's device
-CVR_HIDDEN int make_handle(cvr_handle **out, const cvr_csr_view &device_view, int device, int transpose);
+// a handle of an object's own: cvr_create + cvr_preprocess of a view of device arrays with the default options on the object's device; nvec >= 2:
+// with cvr_options.nvec = nvec, the plain layout
+CVR_HIDDEN int make_handle(cvr_handle **out, const cvr_csr_view &device_view, int device, int transpose, int nvec = 1);
 
 // The end of a constructor whose build failed with `rc`: destroys the half-made object and returns rc with the build's message still in place
 // (cvr_destroy of a half-made handle may write one of its own)

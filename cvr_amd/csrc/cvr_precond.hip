@@ -301,7 +301,8 @@ int block_jacobi_cg_apply(const cvr_precond *pc, const T *r, T *z, T *p, double 
 namespace cvrh {
 namespace krylov {
 
-PrecondOps kBlockJacobiOps = {kPrecondBlockJacobi, "block-Jacobi", block_jacobi_apply, block_jacobi_release, block_jacobi_cg_apply<float>, block_jacobi_cg_apply<double>};
+PrecondOps kBlockJacobiOps = {kPrecondBlockJacobi,          "block-Jacobi",          block_jacobi_apply,           block_jacobi_release,          block_jacobi_cg_apply<float>,
+                              block_jacobi_cg_apply<double>, block_jacobi_apply_multi, block_jacobi_cgm_apply<float>, block_jacobi_cgm_apply<double>};
 
 // ---- the constructors' helpers (cvr_precond.h)
 
@@ -389,12 +390,13 @@ int stage_host(const char *entry, const cvr_csr_view *c, HostCsr &h, bool with_v
     return CVR_OK;
 }
 
-int make_handle(cvr_handle **out, const cvr_csr_view &device_view, int device, int transpose)
+int make_handle(cvr_handle **out, const cvr_csr_view &device_view, int device, int transpose, int nvec)
 {
     cvr_options opt;
     cvr_default_options(&opt);
     opt.device = device;
     opt.transpose = transpose;
+    if (nvec >= 2) opt.nvec = nvec;
     if (const int rc = cvr_create(out, &device_view, &opt)) {
         *out = nullptr;
         return rc;

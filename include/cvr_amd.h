@@ -729,8 +729,9 @@ int cvr_chebyshev_bounds(cvr_handle *h, int32_t power_iters, double eig_ratio, d
  *   with u where L's sweep has double(r) (y_i = T(u_i - s)), the result zu in a buffer of the call, then x_i = T(double(x_i) + double(zu_i)).
  *   A kernel behind a stop writes nothing that reaches x or the result; spmv_count as with block-Jacobi.
  * cvr_precond_get_info works for this kind (block_size, nblocks and identity_blocks are 0); cvr_precond_destroy frees everything.
- * cvr_precond_export, cvr_precond_apply_multi_device and cvr_pcg_multi_device / cvr_pcg_multi take block-Jacobi objects only: CVR_ERR_STATE behind
- * their other checks, cvr_last_error naming the kind.  cvr_precond_chebyshev_info on this kind: CVR_ERR_INVALID.
+ * cvr_precond_export, cvr_precond_apply_multi_device and cvr_pcg_multi_device / cvr_pcg_multi decline this kind (the first takes block-Jacobi objects
+ * only, the others those and cvr_precond_amg_block's): CVR_ERR_STATE behind their other checks, cvr_last_error naming the kind.
+ * cvr_precond_chebyshev_info on this kind: CVR_ERR_INVALID.
  * Errors of cvr_precond_ilu0: a null argument, nrows != ncols: CVR_ERR_INVALID before any device work; `device` out of range: CVR_ERR_NO_DEVICE; the
  * view's checks above: CVR_ERR_INVALID; CVR_ERR_NOMEM: an allocation failed (nothing is left allocated).  cvr_precond_ilu0_info and
  * cvr_precond_ilu0_export: a null argument, or an object of another kind: CVR_ERR_INVALID. */
@@ -860,7 +861,8 @@ int cvr_fsai_factor_host(const cvr_csr_view *csr, int64_t *row_ptr, int32_t *col
  *   (steps enqueued), P the products of an apply.
  * cvr_precond_get_info works for this kind (block_size, nblocks and identity_blocks are 0); cvr_precond_destroy frees the handles and the buffers.
  * cvr_precond_export, cvr_precond_apply_multi_device, cvr_pcg_multi_device / cvr_pcg_multi, cvr_pbicgstab_device / cvr_pbicgstab and
- * cvr_pgmres_device / cvr_pgmres decline this kind: CVR_ERR_STATE behind their other checks, cvr_last_error naming "kind 4 (AMG)".  The *_info and
+ * cvr_pgmres_device / cvr_pgmres decline this kind: CVR_ERR_STATE behind their other checks, cvr_last_error naming "kind 4 (AMG)".  (The two multi
+ * entry points take a kind-4 object only when cvr_precond_amg_block built it; one of this constructor's is declined as ever.)  The *_info and
  * *_export calls of the other kinds return CVR_ERR_INVALID on this kind, and this kind's return it on the others.
  * Errors of cvr_precond_amg, in this order, before any device work: a null out, h or csr; the options (opt NULL: the defaults; max_levels outside
  * 1 .. CVR_AMG_MAX_LEVELS, coarse_size outside 1 .. CVR_AMG_MAX_COARSE, sweeps outside 1 .. 4, strength not in [0, 1), coarse_scale not finite or
@@ -1021,7 +1023,7 @@ int cvr_amg_hierarchy_mis2_info(const cvr_amg_hierarchy *hier, cvr_amg_mis2_info
 int cvr_amg_mis2_aggregate_host(const cvr_csr_view *csr, double strength, int32_t *agg, int64_t *nc, int32_t *rounds);
 int cvr_amg_mis2_aggregate_device(const cvr_csr_view *csr_on_device, double strength, int32_t *agg_dev, int64_t *nc, int32_t *rounds, int device, void *stream);
 
-/* The object with several right-hand sides: Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
+/* The object with several right-hand sides (a block-Jacobi object; a cvr_precond_amg_block object: its section below): Z = W R for 1 <= nvec <= 8 columns at once.  R_dev and Z_dev: row-major blocks of exactly n rows of
  * ldr / ldz values of the object's type (row i holds the values of all columns at i) in the memory of the object's device; values at positions
  * >= nvec of a row are neither read nor written; any alignment of the element type; the blocks must not overlap.
  * Column c of Z is bit for bit what cvr_precond_apply_device gives for column c of R: the same left-to-right sum from t_0, every product and every
@@ -1050,6 +1052,63 @@ int cvr_pcg_multi_device(cvr_handle *h, const cvr_precond *p, const void *B_dev,
                          const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
 /* the same with host B and X (nrows x nvec each, row-major, ld = nvec; X in and out), as cvr_cg_multi */
 int cvr_pcg_multi(cvr_handle *h, const cvr_precond *p, const void *B_host, void *X_host, int32_t nvec, const cvr_cg_options *opt, cvr_cg_result *res);
+
+/* ---- the fifth kind for blocks of right-hand sides: one V-cycle for up to 8 vectors, and batched PCG on it ----
+ * A fourth way to build a kind-4 object.  An AMG apply is bound by its launches (the many small coarse-level products), not by bytes; a cycle that
+ * carries K vectors through every level issues the launches of a cycle for one and reads every level's image, dinv, agg and winv once for all K
+ * columns.  The three constructors above, their objects and the entry points that decline them are unchanged: block support is this constructor's.
+ * Object.  cvr_precond_amg_block(out, h, csr, opt, setup, omega, nvec, stream) returns a kind-4 object whose hierarchy is byte for byte what the
+ *   constructor named by `setup` builds from the same h, csr, opt, omega and stream -- cvr_precond_amg (CVR_AMG_SETUP_PLAIN; omega is ignored),
+ *   cvr_precond_amg_smoothed (CVR_AMG_SETUP_SMOOTHED) or cvr_precond_amg_mis2 (CVR_AMG_SETUP_MIS2): it is that constructor's set-up, not a copy of it.
+ *   cvr_precond_amg_info, cvr_precond_amg_export_level, cvr_precond_amg_smoothed_info, cvr_precond_amg_export_prolongator and
+ *   cvr_precond_amg_mis2_info work on it unchanged, and everything said above of the borrowed handle, the CSR input, n = 0, one stream at a time,
+ *   cvr_precond_get_info and cvr_precond_destroy holds.
+ * Width.  nvec = K, 1 .. 8, is the width the object is built for.  Every handle the object owns (the coarse operators, and P_l and R_l of the
+ *   smoothed set-ups; R_l from the transposed arrays as above) is created with cvr_options.nvec = K: the plain layout for K >= 2, the default options
+ *   for K = 1.  Every per-level buffer (r, z, q, t, e) is a row-major block of K columns with the fixed leading dimension K, sized from the handle's
+ *   x_elems / yext_elems rows and zeroed once; the pad row of an SpMV input (row n_l of z and t) lies at one place for every block call and is never
+ *   written.  cvr_amg_block_info.buffer_bytes is the sum of these blocks.
+ * Level 0.  h is borrowed.  For K >= 2 it must satisfy cvr_spmm_supported(h), else CVR_ERR_STATE (create it with cvr_options.nvec >= 2), and
+ *   (ncols + 1) * K values beyond 4 GiB is CVR_ERR_INVALID; both right behind the constructor's other checks of h.
+ * Single-vector calls.  cvr_precond_apply_device and cvr_pcg_device / cvr_pcg take the object as they take any kind-4 object: they run the cycle
+ *   above (steps 1 - 6; 3' and 5' for the smoothed set-ups) with each product through the level's handle at nvec = 1, ld = 1 (cvr_spmv_device's
+ *   launch path), on the same buffers read as vectors.  At ld = 1 the pad of an SpMV input is element n_l, which a block call writes: the cycle
+ *   begins with one small launch that zeroes those elements.  The bits are those of the cycle with a caller's handle of each exported level created
+ *   with cvr_options.nvec = K in place of the object's.  They are not necessarily those of an ordinary object of the same set-up, whose handles have
+ *   the default layout (another summation order inside a product).
+ * cvr_precond_apply_multi_device(p, R, ldr, Z, ldz, nvec, stream) takes the object for 1 <= nvec <= K: copy-in (R of ldr -> r_0 of K), the cycle
+ *   with k-wide kernels and each product through cvr_spmm_device's path (launch on the plain image at ld = K, inside the update ordering of a
+ *   mutable level-0 handle; K = 1: cvr_spmv_device's path), copy-out (z_0 -> Z of ldz).  Column c of Z is bit for bit cvr_precond_apply_device of
+ *   the same object on column c of R, for every nvec, ldr, ldz and alignment of the element type: per column the kernels perform the single-vector
+ *   kernels' operations in their order (fp64, each rounded on its own, one rounding to T per stored value, no fused multiply-add), and a column of
+ *   the k-wide product has cvr_spmv_device's bits.  Values at positions >= nvec of a row of R are not read, of a row of Z not written.  Columns
+ *   nvec .. K - 1 of the object's buffers keep what an earlier call left; nothing reads them.  The call only enqueues, reads nothing back, and no
+ *   kernel waits on another workgroup.  A thread owns a row of a level (an aggregate in the restriction; a row of the dense inverse, each W value
+ *   loaded once for all columns) and moves its K values in 16-byte packets where K and the type allow it.  nvec > K: CVR_ERR_INVALID naming both
+ *   numbers, behind the call's other checks in their order.
+ * cvr_pcg_multi_device / cvr_pcg_multi take the object under cvr_pcg_multi_device's contract above, word for word: for every column j, column j of
+ *   X and res[j].iterations, .status, .residual_norm and .b_norm are bit for bit cvr_pcg_device's on the same handle and object for b = B[:, j],
+ *   x0 = X[:, j] -- for every check_every, ldb, ldx and alignment.  The cycle touches only the object's buffers and computes all nvec columns
+ *   whatever their cells say; the apply's last launch writes Z, per column the partial sums of r.z into set 1 and, at the start, P = Z, for live
+ *   columns only: a column whose cell holds a stop is not written.  spmv_count = 1 + P + (1 + P) * (steps enqueued), P the products of an apply (a
+ *   k-wide product counts once).  nvec > K: CVR_ERR_INVALID, behind the call's other checks.  nvec = 1 with ldb = ldx = 1 runs on every single-GPU
+ *   handle, as before (the object's own level-0 handle is the one it was built with).
+ * cvr_precond_export, cvr_pbicgstab_device / cvr_pbicgstab and cvr_pgmres_device / cvr_pgmres decline the object as they decline kind 4.
+ * Errors of cvr_precond_amg_block, in this order, before any device work: a null out, h or csr; setup outside 0 .. 2; nvec outside 1 .. 8:
+ *   CVR_ERR_INVALID; then everything the constructor named by `setup` checks, in its order and with its codes, the texts that name an entry point
+ *   beginning with cvr_precond_amg_block.
+ * cvr_precond_amg_block_info fills a cvr_amg_block_info.  An object of another kind: CVR_ERR_INVALID ("... is of kind k, not an AMG object"); a
+ *   kind-4 object of another constructor: CVR_ERR_INVALID, "was not built by cvr_precond_amg_block"; a null argument: CVR_ERR_INVALID. */
+#define CVR_AMG_SETUP_PLAIN    0               /* cvr_precond_amg's set-up                                                  */
+#define CVR_AMG_SETUP_SMOOTHED 1               /* cvr_precond_amg_smoothed's                                                */
+#define CVR_AMG_SETUP_MIS2     2               /* cvr_precond_amg_mis2's                                                    */
+typedef struct {
+    int32_t nvec, setup;                       /* K and CVR_AMG_SETUP_* as given                                            */
+    int64_t buffer_bytes;                      /* device bytes of the per-level blocks r, z, q, t, e                        */
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_amg_block_info;                          /* 48 bytes */
+int cvr_precond_amg_block(cvr_precond **out, cvr_handle *h, const cvr_csr_view *csr, const cvr_amg_options *opt, int32_t setup, double omega, int32_t nvec, void *stream);
+int cvr_precond_amg_block_info(const cvr_precond *p, cvr_amg_block_info *info);
 
 /* BiCGSTAB preconditioned by such an object.  Everything cvr_bicgstab_device's text above fixes holds word for word -- the handles, b_dev and x_dev,
  * the options and the result, r = b - A x by the scaled product, every update, the fixed-tree sums, alpha, omega and beta, the stop rules and status
