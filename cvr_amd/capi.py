@@ -112,6 +112,15 @@ class Ilu0Info(C.Structure):
                 ("is_f32", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
+ILU0_MAX_SWEEPS = 64        # include/cvr_amd.h: CVR_ILU0_MAX_SWEEPS
+
+
+class Ilu0JacobiInfo(C.Structure):
+    """cvr_ilu0_jacobi_info"""
+    _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("sweeps", C.c_int32), ("launches_per_apply", C.c_int32), ("lanes_per_row", C.c_int32),
+                ("levels_lower", C.c_int32), ("levels_upper", C.c_int32), ("is_f32", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
 class McSgsInfo(C.Structure):
     """cvr_mcsgs_info"""
     _fields_ = [("n", C.c_int64), ("nnz", C.c_int64), ("ncolors", C.c_int32), ("rounds", C.c_int32), ("launches_per_apply", C.c_int32),
@@ -244,6 +253,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_precond_block_jacobi", "cvr_precond_get_info", "cvr_precond_export", "cvr_precond_apply_device", "cvr_precond_destroy", "cvr_pcg_device", "cvr_pcg",
            "cvr_precond_chebyshev", "cvr_precond_chebyshev_info", "cvr_chebyshev_bounds",
            "cvr_precond_ilu0", "cvr_precond_ilu0_info", "cvr_precond_ilu0_export", "cvr_ilu0_levels_host",
+           "cvr_precond_ilu0_jacobi", "cvr_precond_ilu0_jacobi_info",
            "cvr_precond_fsai", "cvr_precond_fsai_info", "cvr_precond_fsai_export", "cvr_fsai_factor_host",
            "cvr_amg_default_options", "cvr_precond_amg", "cvr_precond_amg_info", "cvr_precond_amg_export_level", "cvr_amg_setup_host", "cvr_amg_hierarchy_info",
            "cvr_amg_hierarchy_export_level", "cvr_amg_hierarchy_destroy",
@@ -328,6 +338,8 @@ def lib():
         L.cvr_precond_ilu0_info.argtypes = [C.c_void_p, C.POINTER(Ilu0Info)]
         L.cvr_precond_ilu0_export.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_ilu0_levels_host.argtypes = [C.POINTER(CsrView), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.cvr_precond_ilu0_jacobi.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_int32, C.c_void_p]
+        L.cvr_precond_ilu0_jacobi_info.argtypes = [C.c_void_p, C.POINTER(Ilu0JacobiInfo)]
         L.cvr_precond_fsai.argtypes = [C.POINTER(C.c_void_p), C.POINTER(CsrView), C.c_int32, C.c_void_p]
         L.cvr_precond_fsai_info.argtypes = [C.c_void_p, C.POINTER(FsaiInfo)]
         L.cvr_precond_fsai_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1106,15 +1118,45 @@ class Precond:
         return cls._ilu0_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
 
     @classmethod
-    def _ilu0_from_view(cls, view, device):
+    def _ilu0_from_view(cls, view, device, sweeps=None):
         self = cls()
-        rc = lib().cvr_precond_ilu0(C.byref(self._p), C.byref(view), int(device), None)
+        if sweeps is None:
+            name, rc = "cvr_precond_ilu0", lib().cvr_precond_ilu0(C.byref(self._p), C.byref(view), int(device), None)
+        else:
+            name, rc = "cvr_precond_ilu0_jacobi", lib().cvr_precond_ilu0_jacobi(C.byref(self._p), C.byref(view), int(sweeps), int(device), None)
         if rc:
             self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_ilu0")
+            raise CvrError(rc, name)
         lib().cvr_precond_get_info(self._p, C.byref(self.info))
         self.dtype = np.float32 if self.info.is_f32 else np.float64
         return self
+
+    @classmethod
+    def ilu0_jacobi(cls, rp, ci, vals, sweeps, device=0):
+        """cvr_precond_ilu0_jacobi from host CSR arrays, read as Precond.ilu0 reads them: the same ILU(0) factors, each triangular solve of the apply
+        replaced by `sweeps` (1 .. ILU0_MAX_SWEEPS) Jacobi sweeps -- 2 * sweeps launches per apply whatever the level structure.  Kind 2: pcg,
+        pbicgstab and pgmres take it as they take Precond.ilu0's.  Serves one stream at a time."""
+        rp = np.ascontiguousarray(rp, dtype=np.int64)
+        ci = np.ascontiguousarray(ci, dtype=np.int32)
+        f32 = np.asarray(vals).dtype == np.float32
+        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+        n = len(rp) - 1
+        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+        return cls._ilu0_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device, sweeps)
+
+    @classmethod
+    def ilu0_jacobi_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, sweeps, is_f32=False, device=0):
+        """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
+        return cls._ilu0_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device, sweeps)
+
+    def ilu0_jacobi_info(self):
+        """cvr_precond_ilu0_jacobi_info: an Ilu0JacobiInfo (n, nnz, sweeps, launches_per_apply, lanes_per_row, levels_*, is_f32)"""
+        info = Ilu0JacobiInfo()
+        rc = lib().cvr_precond_ilu0_jacobi_info(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, "cvr_precond_ilu0_jacobi_info")
+        return info
 
     def ilu0_info(self):
         """cvr_precond_ilu0_info: an Ilu0Info (n, nnz, levels_*, launches_*, max_level_width, lanes_per_row, wide_threshold, is_f32)"""

@@ -1,5 +1,5 @@
 // cvr_ilu0.hip -- the ILU(0) preconditioner, the third kind of cvr_precond (include/cvr_amd.h: cvr_precond_ilu0, cvr_precond_ilu0_info,
-// cvr_precond_ilu0_export, cvr_ilu0_levels_host).  A ~ L U on A's own pattern, L unit lower and U upper triangular; z = U^-1 L^-1 r is two sparse
+// cvr_precond_ilu0_export, cvr_ilu0_levels_host; cvr_precond_ilu0_jacobi, cvr_precond_ilu0_jacobi_info: the Jacobi-swept apply, below).  A ~ L U on A's own pattern, L unit lower and U upper triangular; z = U^-1 L^-1 r is two sparse
 // triangular solves, each scheduled by levels: a row's level is one more than the largest level among the rows it reads, so the rows of a level are
 // independent and the levels run in order.
 //   Analysis, on the host, once, O(nnz): the checks (square, columns strictly increasing, a diagonal in every row), the level of every row in L
@@ -17,23 +17,26 @@
 //   In the merged kernels the vector being solved for is read and written in the same launch by different wavefronts of the workgroup: those loads
 //   are agent-scope atomic loads (they bypass the CU's vector L1), never const __restrict__; the stores are complete before the barrier.
 // The same device function forms a row in both kernels, so the bits do not depend on the plan.
+//   The Jacobi-swept object (cvr_precond_ilu0_jacobi, Ilu0::sweeps = s >= 1): the same analysis, factors and row sum (row_sum), but each exact
+//   sweep is replaced by s Jacobi sweeps on its triangular system, 2 s launches per apply whatever the levels.  A launch (jacobi_sweep_kernel) covers
+//   all n rows in natural order through a row-ordered slot array (cvr_ilu0_slots.h), reads one buffer and writes another -- never in place -- so the
+//   read side was written by an earlier launch: plain const __restrict__ loads, no barrier, nothing waits on another workgroup.
+//     L: y(0) = r, read in place;  y(k)_i = T(double(r_i) - S_i(y(k-1))), k = 1 .. s, alternating between two buffers of the object;
+//        the last L launch also writes z(0)_i = T(double(y(s)_i) / double(u_ii)) for the row it has just formed.
+//     U: z(k)_i = T((double(y(s)_i) - S'_i(z(k-1))) / double(u_ii)), k = 1 .. s, alternating between the caller's z and a third buffer of the object,
+//        z(k) in the caller's z when s - k is even: z(s) lands there for odd and even s.
+//   ilu0_apply is the one place that switches on `sweeps`; the solvers see kind 2 and nothing else.
 // (The reference has no solver and no preconditioner: its Ntimes loop, spmv.cpp:1024, recomputes one y.)
 #include "cvr_krylov.h"
 #include "cvr_cg_kernels.h"
 #include "cvr_precond.h"
+#include "cvr_ilu0_slots.h"
 
 using namespace cvrh;
 using namespace cvrh::krylov;
 
 namespace cvrh {
 namespace krylov {
-
-// a row in a sweep's order: its entries of the sweep's triangle are beg .. beg + cnt - 1 (U: the diagonal lies at beg - 1)
-struct Ilu0Slot {
-    long long beg;
-    int32_t   cnt, row;
-};
-static_assert(sizeof(Ilu0Slot) == 16, "one 16-byte load per row");
 
 struct Ilu0Launch {
     int32_t lvl0, nlvl;          // the levels it covers
@@ -55,6 +58,10 @@ struct Ilu0 {
     void     *d_f = nullptr;          // nnz values of T in the CSR's positions: L strictly below the diagonal, U from the diagonal up
     void     *d_y = nullptr;          // n values of T
     Ilu0Sweep lo, up;
+    // the Jacobi-swept object only (sweeps >= 1; 0: the exact object, which has none of these)
+    int32_t   sweeps = 0;
+    Ilu0Slot *d_rows_lo = nullptr, *d_rows_up = nullptr;          // n each, in natural row order
+    void     *d_y2 = nullptr, *d_w = nullptr;                     // n values of T each: y's second buffer (sweeps >= 2), z's other buffer
 };
 
 }  // namespace krylov
@@ -96,10 +103,10 @@ __device__ __forceinline__ bool gate_closed(const Ilu0Gate &g)
     return false;
 }
 
-// One row of a sweep by the G lanes of its group (lane l of them; every lane of the wavefront comes here, `active` or not: the butterfly is the
-// whole wavefront's).  v: the vector being solved for (y in L's sweep, z in U's), rhs: r or y.
-template <typename T, typename R, bool UPPER, bool COH>
-__device__ __forceinline__ void sweep_row(bool active, const Ilu0Slot &s, int l, int G, const int32_t *__restrict__ ci, const T *__restrict__ f, const R *rhs, T *v)
+// The sum of one row of a triangle over v by the G lanes of its group (lane l of them; every lane of the wavefront comes here, `active` or not: the
+// butterfly is the whole wavefront's): the same value in all G lanes.  The exact and the Jacobi sweeps both form their rows with it.
+template <bool COH, typename T, typename V>
+__device__ __forceinline__ double row_sum(bool active, const Ilu0Slot &s, int l, int G, const int32_t *__restrict__ ci, const T *__restrict__ f, const V *v)
 {
     double acc = 0;
     if (active)
@@ -108,6 +115,14 @@ __device__ __forceinline__ void sweep_row(bool active, const Ilu0Slot &s, int l,
             acc += (double)f[q] * (double)load_solved<COH>(v + ci[q]);
         }
     for (int o = G >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    return acc;
+}
+
+// One row of an exact sweep.  v: the vector being solved for (y in L's sweep, z in U's), rhs: r or y.
+template <typename T, typename R, bool UPPER, bool COH>
+__device__ __forceinline__ void sweep_row(bool active, const Ilu0Slot &s, int l, int G, const int32_t *__restrict__ ci, const T *__restrict__ f, const R *rhs, T *v)
+{
+    const double acc = row_sum<COH>(active, s, l, G, ci, f, (const T *)v);
     if (active && l == 0) {
         double t = (double)rhs[s.row] - acc;
         if constexpr (UPPER) t = t / (double)f[s.beg - 1];
@@ -145,6 +160,32 @@ __global__ __launch_bounds__(kMergedThreads) void sweep_merged_kernel(const Ilu0
             sweep_row<T, R, UPPER, true>(active, s, l, G, ci, f, rhs, v);
         }
         __syncthreads();          // (with its fence: the level's stores are complete before any wavefront reads them)
+    }
+}
+
+// One Jacobi sweep over all n rows in natural order (slots[i] is row i), G lanes a row: out_i from `in` of the launch before, never in place.
+//   L (UPPER false): out_i = T(double(rhs_i) - S_i(in)); rhs is r, and so is `in` in the first sweep (V = R).  Z0: the last L sweep, which also writes
+//     z0_i = T(double(out_i) / double(u_ii)), the diagonal lying behind the row's part of L.
+//   U (UPPER true):  out_i = T((double(rhs_i) - S'_i(in)) / double(u_ii)); rhs is y(s).
+// `in` and `rhs` were written before this launch and are only read (they may be the same array); out and z0 are other arrays.
+template <typename T, typename V, typename R, bool UPPER, bool Z0>
+__global__ __launch_bounds__(kThreads) void jacobi_sweep_kernel(const Ilu0Slot *__restrict__ slots, long long n, int G, const int32_t *__restrict__ ci, const T *__restrict__ f,
+                                                                const R *rhs, const V *in, T *__restrict__ out, T *__restrict__ z0, Ilu0Gate gate)
+{
+    if (gate_closed(gate)) return;
+    const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const long long i = t / G;
+    const int       l = (int)(t - i * G);
+    const bool      active = i < n;
+    Ilu0Slot        s{0, 0, 0};
+    if (active) s = slots[i];
+    const double acc = row_sum<false>(active, s, l, G, ci, f, in);
+    if (active && l == 0) {
+        double v = (double)rhs[i] - acc;
+        if constexpr (UPPER) v = v / (double)f[s.beg - 1];
+        const T y = (T)v;
+        out[i] = y;
+        if constexpr (Z0) z0[i] = (T)((double)y / (double)f[s.beg + s.cnt]);
     }
 }
 
@@ -231,6 +272,33 @@ int enqueue_sweep(const Ilu0 *u, const Ilu0Sweep &sw, const R *rhs, T *v, const 
                                (const int32_t *)u->d_ci, f, rhs, v, gate);
         }
     }
+    HIP_TRY(hipGetLastError());
+    return CVR_OK;
+}
+
+// one Jacobi sweep enqueued: all n rows, G lanes each
+template <typename T, typename V, typename R, bool UPPER, bool Z0>
+void enqueue_jacobi(const Ilu0 *u, long long n, const R *rhs, const V *in, T *out, T *z0, const Ilu0Gate &gate, hipStream_t st)
+{
+    const long long groups = (n * u->G + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL((jacobi_sweep_kernel<T, V, R, UPPER, Z0>), dim3((unsigned)groups), dim3(kThreads), 0, st, (const Ilu0Slot *)(UPPER ? u->d_rows_up : u->d_rows_lo), n, (int)u->G,
+                       (const int32_t *)u->d_ci, static_cast<const T *>(u->d_f), rhs, in, out, z0, gate);
+}
+
+// The swept apply: 2 * sweeps launches.  y(k) lies in the object's y buffer k & 1, z(k) in the caller's z when sweeps - k is even, else in w.
+template <typename T, typename R>
+int jacobi_apply(const Ilu0 *u, long long n, const R *r, T *z, const Ilu0Gate &gate, hipStream_t st)
+{
+    const int s = u->sweeps;
+    T        *yb[2] = {static_cast<T *>(u->d_y2), static_cast<T *>(u->d_y)}, *w = static_cast<T *>(u->d_w);
+    const auto zbuf = [&](int k) { return (s - k) % 2 == 0 ? z : w; };
+    if (s == 1) enqueue_jacobi<T, R, R, false, true>(u, n, r, r, yb[1], zbuf(0), gate, st);
+    else {
+        enqueue_jacobi<T, R, R, false, false>(u, n, r, r, yb[1], (T *)nullptr, gate, st);
+        for (int k = 2; k < s; k++) enqueue_jacobi<T, T, R, false, false>(u, n, r, (const T *)yb[(k - 1) & 1], yb[k & 1], (T *)nullptr, gate, st);
+        enqueue_jacobi<T, T, R, false, true>(u, n, r, (const T *)yb[(s - 1) & 1], yb[s & 1], zbuf(0), gate, st);
+    }
+    for (int k = 1; k <= s; k++) enqueue_jacobi<T, T, T, true, false>(u, n, (const T *)yb[s & 1], (const T *)zbuf(k - 1), zbuf(k), (T *)nullptr, gate, st);
     HIP_TRY(hipGetLastError());
     return CVR_OK;
 }
@@ -346,7 +414,7 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
 
     std::vector<int32_t>  lvl_lo, lvl_up, order, lptr;
     std::vector<int64_t>  dpos;
-    std::vector<Ilu0Slot> slots_lo, slots_up;
+    std::vector<Ilu0Slot> slots_lo, slots_up, rows_lo, rows_up;
     try {
         lvl_lo.assign((size_t)n, 0);
         lvl_up.assign((size_t)n, 0);
@@ -367,6 +435,10 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
         if (const int rc = upload_sweep(n, h.rp, dpos.data(), order, lptr, false, u->lo, st, slots_lo)) return rc;
         plan_sweep(n, lvl_up.data(), nup, u->wide, order, lptr, u->up);
         if (const int rc = upload_sweep(n, h.rp, dpos.data(), order, lptr, true, u->up, st, slots_up)) return rc;
+        if (u->sweeps > 0) {          // the Jacobi sweeps walk the rows in natural order
+            ilu0_row_slots(n, h.rp, dpos.data(), false, rows_lo);
+            ilu0_row_slots(n, h.rp, dpos.data(), true, rows_up);
+        }
     } catch (const std::bad_alloc &) {
         return fail(CVR_ERR_NOMEM, "cvr_precond_ilu0: out of host memory for the analysis (%lld rows)", (long long)n);
     }
@@ -374,6 +446,17 @@ int build(cvr_precond *p, const cvr_csr_view *csr, hipStream_t st)
     if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&u->d_ci), sizeof(int32_t) * (size_t)nnz, "col_idx")) return rc;
     if (const int rc = device_alloc(kEntry, &u->d_f, vsz * (size_t)nnz, "the factors")) return rc;
     if (const int rc = device_alloc(kEntry, &u->d_y, vsz * (size_t)n, "y")) return rc;
+    if (u->sweeps > 0) {
+        if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&u->d_rows_lo), sizeof(Ilu0Slot) * (size_t)n, "L's rows in natural order")) return rc;
+        if (const int rc = device_alloc(kEntry, reinterpret_cast<void **>(&u->d_rows_up), sizeof(Ilu0Slot) * (size_t)n, "U's rows in natural order")) return rc;
+        if (u->sweeps > 1)
+            if (const int rc = device_alloc(kEntry, &u->d_y2, vsz * (size_t)n, "y's second buffer")) return rc;
+        if (const int rc = device_alloc(kEntry, &u->d_w, vsz * (size_t)n, "z's second buffer")) return rc;
+        HIP_TRY(hipMemcpyAsync(u->d_rows_lo, rows_lo.data(), sizeof(Ilu0Slot) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(u->d_rows_up, rows_up.data(), sizeof(Ilu0Slot) * (size_t)n, hipMemcpyHostToDevice, st));
+        if (u->d_y2) HIP_TRY(hipMemsetAsync(u->d_y2, 0, vsz * (size_t)n, st));
+        HIP_TRY(hipMemsetAsync(u->d_w, 0, vsz * (size_t)n, st));
+    }
     Scratch s;
     void   *d_rp = nullptr, *d_dpos = nullptr, *d_a = nullptr, *d_bad = nullptr, *d_va = nullptr;
     if (const int rc = scratch_alloc(kEntry, s, &d_rp, sizeof(int64_t) * (size_t)(n + 1), "row_ptr")) return rc;
@@ -414,6 +497,7 @@ int ilu0_apply(const cvr_precond *pc, const R *r, T *z, const Ilu0Gate &gate, hi
 {
     const Ilu0 *u = pc->ilu;
     if (!u || pc->n == 0) return CVR_OK;
+    if (u->sweeps > 0) return jacobi_apply<T, R>(u, (long long)pc->n, r, z, gate, st);
     T *y = static_cast<T *>(u->d_y);
     if (const int rc = enqueue_sweep<T, R, false>(u, u->lo, r, y, gate, st)) return rc;
     return enqueue_sweep<T, T, true>(u, u->up, (const T *)y, z, gate, st);
@@ -460,7 +544,8 @@ void ilu0_release(cvr_precond *p)
 {
     Ilu0 *u = p->ilu;
     if (!u) return;
-    for (void *buf : {(void *)u->d_ci, u->d_f, u->d_y, (void *)u->lo.d_slots, (void *)u->lo.d_lptr, (void *)u->up.d_slots, (void *)u->up.d_lptr})
+    for (void *buf : {(void *)u->d_ci, u->d_f, u->d_y, (void *)u->lo.d_slots, (void *)u->lo.d_lptr, (void *)u->up.d_slots, (void *)u->up.d_lptr, (void *)u->d_rows_lo,
+                      (void *)u->d_rows_up, u->d_y2, u->d_w})
         if (buf) (void)hipFree(buf);
     delete u;
     p->ilu = nullptr;
@@ -473,17 +558,17 @@ PrecondOps kIlu0Ops = {kPrecondIlu0, "ILU(0)", ilu0_apply_any, ilu0_release, ilu
 }  // namespace krylov
 }  // namespace cvrh
 
-extern "C" {
+namespace {
 
-int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device, void *stream)
+// both constructors behind their own argument checks; sweeps = 0: the exact object
+int construct(cvr_precond **out, const cvr_csr_view *csr, int32_t sweeps, int32_t device, void *stream, const char *entry)
 {
-    if (!out || !csr) return fail(CVR_ERR_INVALID, "null argument");
     *out = nullptr;
     if (csr->nrows != csr->ncols) return fail(CVR_ERR_INVALID, "ILU(0) needs a square matrix (%lld x %lld)", (long long)csr->nrows, (long long)csr->ncols);
     if (csr->nrows < 0) return fail(CVR_ERR_INVALID, "null or negative-size CSR view");
     if (device < 0 || device >= cvr_device_count()) return fail(CVR_ERR_NO_DEVICE, "device %d of %d", device, cvr_device_count());
     cvr::debug_refresh();
-    Range range("cvr_precond_ilu0");
+    Range range(entry);
     HIP_TRY(hipSetDevice(device));
     cvr_precond *p = new (std::nothrow) cvr_precond;
     Ilu0        *u = new (std::nothrow) Ilu0;
@@ -501,8 +586,45 @@ int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device,
     p->ilu = u;
     u->G = 1;
     u->wide = kDefaultWide;
+    u->sweeps = sweeps;
     if (const int rc = build(p, csr, (hipStream_t)stream)) return abandon(p, rc);
     *out = p;
+    return CVR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvr_precond_ilu0(cvr_precond **out, const cvr_csr_view *csr, int32_t device, void *stream)
+{
+    if (!out || !csr) return fail(CVR_ERR_INVALID, "null argument");
+    return construct(out, csr, 0, device, stream, "cvr_precond_ilu0");
+}
+
+int cvr_precond_ilu0_jacobi(cvr_precond **out, const cvr_csr_view *csr, int32_t sweeps, int32_t device, void *stream)
+{
+    if (!out || !csr) return fail(CVR_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (sweeps < 1 || sweeps > CVR_ILU0_MAX_SWEEPS) return fail(CVR_ERR_INVALID, "cvr_precond_ilu0_jacobi: sweeps = %d, not in 1 .. %d", sweeps, CVR_ILU0_MAX_SWEEPS);
+    return construct(out, csr, sweeps, device, stream, "cvr_precond_ilu0_jacobi");
+}
+
+int cvr_precond_ilu0_jacobi_info(const cvr_precond *p, cvr_ilu0_jacobi_info *info)
+{
+    if (!p || !info) return fail(CVR_ERR_INVALID, "null argument");
+    if (p->kind != kPrecondIlu0 || !p->ilu) return fail(CVR_ERR_INVALID, "cvr_precond_ilu0_jacobi_info: the preconditioner is of kind %d, not an ILU(0) object (kind %d)", p->kind, kPrecondIlu0);
+    const Ilu0 *u = p->ilu;
+    if (u->sweeps < 1) return fail(CVR_ERR_INVALID, "cvr_precond_ilu0_jacobi_info: the object is an exact ILU(0) object (cvr_precond_ilu0), not one of cvr_precond_ilu0_jacobi");
+    memset(info, 0, sizeof(*info));
+    info->n = p->n;
+    info->nnz = u->nnz;
+    info->sweeps = u->sweeps;
+    info->launches_per_apply = p->n > 0 ? 2 * u->sweeps : 0;
+    info->lanes_per_row = u->G;
+    info->levels_lower = u->lo.levels;
+    info->levels_upper = u->up.levels;
+    info->is_f32 = p->is_f32;
     return CVR_OK;
 }
 
@@ -518,6 +640,7 @@ int cvr_precond_ilu0_info(const cvr_precond *p, cvr_ilu0_info *info)
     info->levels_upper = u->up.levels;
     info->launches_lower = (int32_t)u->lo.plan.size();
     info->launches_upper = (int32_t)u->up.plan.size();
+    if (u->sweeps > 0) info->launches_lower = info->launches_upper = p->n > 0 ? u->sweeps : 0;          // (a Jacobi-swept object: what an apply enqueues)
     info->max_level_width = std::max(u->lo.max_width, u->up.max_width);
     info->lanes_per_row = u->G;
     info->wide_threshold = u->wide;

@@ -750,6 +750,45 @@ int cvr_precond_ilu0_info(const cvr_precond *p, cvr_ilu0_info *info);
 int cvr_precond_ilu0_export(const cvr_precond *p, void *vals_host);
 int cvr_ilu0_levels_host(const cvr_csr_view *csr, int32_t *lower_level, int32_t *upper_level, int32_t *n_lower, int32_t *n_upper);
 
+/* ---- ILU(0) with Jacobi-swept triangular solves: 2 * sweeps launches per apply, whatever the levels ------
+ * The same object as cvr_precond_ilu0's -- kind 2, the same input rules, checks, analysis and factorisation on the device, the same factor bits
+ * (cvr_precond_ilu0_export returns them), the same G -- but each exact triangular solve of the apply is replaced by a fixed number s = `sweeps` of
+ * Jacobi sweeps on the triangular system (Anzt, Chow, Dongarra 2015; Chow, Patel 2015).  A sweep is one launch over all n rows with every row
+ * independent, so an apply is exactly 2 s launches on `stream` and nothing else (none when n = 0), without a read-back, where the exact object needs
+ * one launch or one workgroup barrier per level.  s is fixed, so the apply is a fixed linear operator; for a symmetric positive definite A it is
+ * symmetric positive definite (U = D L^T: M^-1 = Lt^-T D^-1 Lt^-1 with Lt^-1 = sum over j <= s of (I - L)^j, unit lower triangular), so PCG may use it.
+ * Arithmetic.  S_i(v) is the exact apply's row sum over L's part of row i, S'_i(v) over U's part right of the diagonal: G lanes a row, lane l takes
+ *   the entries l, l + G, .. in column order from +0 in fp64, every product and addition rounded on its own, the lanes combined by the xor butterfly
+ *   G/2 .. 1.  With y(0) = r, read as it is (type T, or double where GMRES hands over its fp64 combination):
+ *       L:  y(k)_i = T(double(r_i) - S_i(y(k-1))),                              k = 1 .. s;
+ *       U:  z(0)_i = T(double(y(s)_i) / double(u_ii)),   z(k)_i = T((double(y(s)_i) - S'_i(z(k-1))) / double(u_ii)),   k = 1 .. s;   z = z(s).
+ *   z(0) is written by the last L launch.  Every sweep reads one array and writes another: y(k) alternates between two buffers of the object, z(k)
+ *   between z_dev and a third, z(s) in z_dev for odd and even s; no launch waits on another workgroup.  After k sweeps the rows of L-level < k hold
+ *   the exact sweep's bits, after k U sweeps those of U-level <= k: with s >= max(levels_lower, levels_upper - 1) the apply equals the exact
+ *   object's bit for bit.
+ * Aliasing: r_dev and z_dev must not overlap at all (z_dev holds intermediate sweeps while r_dev is still read), and neither may be memory of the
+ *   object.  cvr_precond_apply_device declines r_dev == z_dev as for every kind; cvr_pcg*, cvr_pbicgstab* and cvr_pgmres* pass buffers of their own
+ *   that never overlap.  The result has the same bits on every call, for every alignment of r_dev and z_dev.  The buffers are the object's, so one
+ *   object serves one stream at a time.
+ * Everything the ILU(0) section above says of kind 2 holds with launches_lower = launches_upper = s: cvr_precond_apply_device, cvr_pcg_device /
+ *   cvr_pcg (3 + 2 s + 1 launches per step), cvr_pbicgstab* and cvr_pgmres* take the object, under the same stop rules (every sweep launch returns at
+ *   its top behind a stop) and with the same spmv_count; cvr_precond_export, cvr_precond_apply_multi_device and cvr_pcg_multi* decline it with
+ *   CVR_ERR_STATE.  cvr_precond_ilu0_info works on it and reports launches_lower = launches_upper = s.  CVR_DEBUG=ilu_lanes is honoured as there.
+ * Errors of cvr_precond_ilu0_jacobi: a null argument, sweeps < 1 or sweeps > CVR_ILU0_MAX_SWEEPS: CVR_ERR_INVALID before any device work; then
+ * cvr_precond_ilu0's.  cvr_precond_ilu0_jacobi_info: a null argument, an object of another kind or one built by cvr_precond_ilu0: CVR_ERR_INVALID. */
+#define CVR_ILU0_MAX_SWEEPS 64
+typedef struct {
+    int64_t n, nnz;                            /* nnz = row_ptr[n]                                                          */
+    int32_t sweeps;                            /* s                                                                         */
+    int32_t launches_per_apply;                /* 2 s (0 when n = 0)                                                        */
+    int32_t lanes_per_row;                     /* G                                                                         */
+    int32_t levels_lower, levels_upper;        /* of the exact sweeps: s >= max(levels_lower, levels_upper - 1) is exact    */
+    int32_t is_f32;
+    int32_t reserved[8];                       /* 0                                                                         */
+} cvr_ilu0_jacobi_info;
+int cvr_precond_ilu0_jacobi(cvr_precond **out, const cvr_csr_view *csr, int32_t sweeps, int32_t device, void *stream);
+int cvr_precond_ilu0_jacobi_info(const cvr_precond *p, cvr_ilu0_jacobi_info *info);
+
 /* ---- a fourth kind of cvr_precond: FSAI, z = Wb^T (Wa r) by two products on the SpMV path --------------
  * The factorised sparse approximate inverse (Kolotilina-Yeremin) of a symmetric positive definite A: M^-1 = W^T D^-1 W with W unit lower triangular
  * on the pattern of A's lower triangle.  Like ILU(0) it couples unknowns across the whole matrix; unlike ILU(0) its apply is no triangular sweep but
