@@ -182,6 +182,7 @@ class SpGemmInfo(C.Structure):
 
 
 GMRES_MAX_RESTART = 64      # include/cvr_amd.h: CVR_GMRES_MAX_RESTART
+APPLY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)      # cvr_apply_fn: (ctx, v_dev, z_dev, n, stream) -> int
 
 
 class LsqrInfo(C.Structure):
@@ -264,7 +265,7 @@ SYMBOLS = ["cvr_default_options", "cvr_last_error", "cvr_version", "cvr_device_c
            "cvr_color_host", "cvr_color_device", "cvr_precond_mcsgs", "cvr_precond_mcsgs_info", "cvr_precond_mcsgs_export",
            "cvr_spgemm_create", "cvr_spgemm_get_info", "cvr_spgemm_csr_device", "cvr_spgemm_export", "cvr_spgemm_numeric_device", "cvr_spgemm_destroy", "cvr_spgemm_host",
            "cvr_precond_apply_multi_device", "cvr_pcg_multi_device", "cvr_pcg_multi",
-           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
+           "cvr_pbicgstab_device", "cvr_pbicgstab", "cvr_pgmres_device", "cvr_pgmres", "cvr_fgmres_device", "cvr_fgmres", "cvr_lsqr_device", "cvr_lsqr", "cvr_minres_device", "cvr_minres",
            "cvr_eig_default_options", "cvr_eigsh_device", "cvr_eigsh", "cvr_sym_eig_host",
            "cvr_lobpcg_default_options", "cvr_lobpcg_device", "cvr_lobpcg",
            "cvr_svd_default_options", "cvr_svds_device", "cvr_svds", "cvr_svd_host",
@@ -385,6 +386,8 @@ def lib():
         L.cvr_pbicgstab.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_pgmres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_pgmres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
+        L.cvr_fgmres_device.argtypes = [C.c_void_p, C.c_void_p, APPLY_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
+        L.cvr_fgmres.argtypes = [C.c_void_p, C.c_void_p, APPLY_FN, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_lsqr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo), C.c_void_p]
         L.cvr_lsqr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(LsqrInfo)]
         L.cvr_minres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo), C.c_void_p]
@@ -2016,6 +2019,43 @@ class CvrMatrix:
         opt = self._gmres_options("pgmres_host", options, None)
         b, x = self._host_vectors(b, x0)
         return x[: self.nrows], self._solve("cvr_pgmres", opt, (precond._p, b.ctypes.data, x.ctypes.data, int(restart)))
+
+    def _fgmres(self, symbol, name, precond, apply, head, tail, options):
+        """one cvr_fgmres* call: the Python `apply` wrapped in an APPLY_FN that lives as long as the call; an exception it raises becomes the return
+        code 1 and is raised again behind the C call"""
+        opt = self._gmres_options(name, options, None)
+        raised = []
+
+        def trampoline(_ctx, v_ptr, z_ptr, n, stream):
+            try:
+                return int(apply(v_ptr, z_ptr, n, stream) or 0)
+            except BaseException as e:  # noqa: BLE001
+                raised.append(e)
+                return 1
+
+        fn = APPLY_FN(trampoline) if apply is not None else APPLY_FN()
+        try:
+            return self._solve(symbol, opt, (None if precond is None else precond._p, fn, None) + head, tail)
+        except CvrError:
+            if raised:
+                raise raised[0]
+            raise
+
+    def fgmres(self, b, restart=30, precond=None, apply=None, x0=None, stream=None, **options):
+        """flexible restarted GMRES(restart) on the device (cvr_fgmres_device): z_j = M_j^-1 v_j is kept for every column and x = x0 + Z y, so the
+        preconditioner may be any kind of Precond (`precond`), or a Python callable `apply(v_ptr, z_ptr, n, stream) -> int` that leaves z = M^-1 v
+        complete in stream order on `stream` (raw device pointers of n values of the handle's type; its k-th call belongs to step k; a non-zero
+        return or an exception ends the solve, the exception is raised again here), or neither (then bit for bit gmres without minv).  b, x0, the
+        options (rtol, max_iters, check_every) and the return value are gmres's."""
+        x = b.new_zeros(max(self.nrows, 1)) if x0 is None else x0
+        res = self._fgmres("cvr_fgmres_device", "fgmres", precond, apply, (b.data_ptr(), x.data_ptr(), int(restart)), (stream,), options)
+        return (x[: self.nrows] if x0 is None else x), res
+
+    def fgmres_host(self, b, restart=30, precond=None, apply=None, x0=None, **options):
+        """the same through host arrays (cvr_fgmres): b and the start vector x0 (None: zero) of nrows values; `apply` still gets device pointers and
+        the handle's stream.  Returns (x, CgResult)."""
+        b, x = self._host_vectors(b, x0)
+        return x[: self.nrows], self._fgmres("cvr_fgmres", "fgmres_host", precond, apply, (b.ctypes.data, x.ctypes.data, int(restart)), (), options)
 
     def spmm(self, X, iters=1):
         """Y = A X for the k columns of X (host array of shape (ncols, k)) in one pass per block of 8 (cvr_spmm); returns (Y of shape

@@ -1,5 +1,5 @@
 // cvr_gmres_kernels.h -- the state cell, the vector kernels and the column-group macro of GMRES(m) (cvr_gmres.hip: cvr_gmres_device,
-// cvr_pgmres_device).  What each kernel does: cvr_gmres.hip's head.
+// cvr_pgmres_device; cvr_fgmres.hip: cvr_fgmres_device).  What each kernel does: cvr_gmres.hip's head.
 #pragma once
 #include "cvr_krylov.h"
 #include "cvr_basis_groups.h"

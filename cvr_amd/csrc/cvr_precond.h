@@ -1,6 +1,6 @@
 // cvr_precond.h -- the preconditioner object as the solvers see it, shared by the files that hold the objects (cvr_precond.hip: block-Jacobi,
 // cvr_chebyshev.hip: the Chebyshev kind, cvr_pcg_multi.hip: the k-wide block-Jacobi apply) and the solvers that take one (cvr_cg.hip, cvr_cg_multi.hip,
-// cvr_bicgstab.hip, cvr_gmres.hip): the struct with its kind and its table of operations (PrecondOps: one per kind, defined in the kind's file; the
+// cvr_bicgstab.hip, cvr_gmres.hip, cvr_fgmres.hip): the struct with its kind and its table of operations (PrecondOps: one per kind, defined in the kind's file; the
 // entry points all kinds share and the CG solver call through it, and nothing branches on the kind but BiCGSTAB and GMRES for ILU(0)'s gated sweeps),
 // the block-Jacobi apply of one packet (every solver forms z = W r by this code, so the same r gives the same bits in all of them), the copy and
 // r . z kernels the kinds share, the checks every preconditioned entry point makes, and the helpers the constructors build with.  How W is built and

@@ -202,6 +202,30 @@ def laplacian_2d(m, dtype=np.float64):
     return n, n, rp, cols[order].astype(np.int32), vals[order].astype(dtype)
 
 
+def upwind_2d(m, cx=-0.5, cy=-0.25, dtype=np.float64):
+    """Convection-diffusion on an m x m grid with Dirichlet boundaries, first-order upwind: diffusion 1 (the 5-point Laplacian above) plus the
+    convection (bx, by) . grad u with cx = bx h and cy = by h.  Row: 4 + |cx| + |cy| on the diagonal, -1 to the four grid neighbours and -|cx|, -|cy|
+    more to the upwind one in each direction: for cx > 0 the west neighbour (j - 1), for cx < 0 the east one (j + 1); cy likewise with i.
+    Nonsymmetric for cx or cy != 0 and weakly diagonally dominant by rows for every cx, cy.  The default flow goes towards the smaller indices, so
+    the extra weight lies in the UPPER triangle: the plain-aggregation AMG set-up inverts its coarsest matrix by an LDL^T that reads the lower
+    triangle, which then is the Laplacian's and has positive pivots; with cx, cy > 0 it reads the heavier triangle and declines the matrix.
+    Returns (n, n, row_ptr, col_idx, vals), the columns of a row ascending."""
+    n = m * m
+    i, j = np.divmod(np.arange(n, dtype=np.int64), m)
+    rows, cols, vals = [], [], []
+    for ok, off, v in ((i > 0, -m, -1.0 - max(cy, 0.0)), (j > 0, -1, -1.0 - max(cx, 0.0)), (np.ones(n, dtype=bool), 0, 4.0 + abs(cx) + abs(cy)),
+                       (j < m - 1, 1, -1.0 - max(-cx, 0.0)), (i < m - 1, m, -1.0 - max(-cy, 0.0))):
+        r = np.flatnonzero(ok)
+        rows.append(r)
+        cols.append(r + off)
+        vals.append(np.full(len(r), v))
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    order = np.lexsort((cols, rows))
+    rp = np.zeros(n + 1, dtype=np.int64)
+    rp[1:] = np.cumsum(np.bincount(rows, minlength=n))
+    return n, n, rp, cols[order].astype(np.int32), vals[order].astype(dtype)
+
+
 def block_diag_spd(n, bs, cond=1e3, seed=11, dtype=np.float64):
     """An exactly block-diagonal symmetric positive definite matrix (the block-Jacobi preconditioner's test family): dense blocks of bs rows (the last
     one shorter when bs does not divide n), each Q diag(lambda) Q^T with a random orthogonal Q and eigenvalues spread log-uniformly over [1, cond] --

@@ -1187,6 +1187,52 @@ int cvr_pgmres_device(cvr_handle *h, const cvr_precond *p, const void *b_dev, vo
 /* the same with host b and x (nrows values each; x in and out), as cvr_cg */
 int cvr_pgmres(cvr_handle *h, const cvr_precond *p, const void *b_host, void *x_host, int32_t restart, const cvr_cg_options *opt, cvr_cg_result *res);
 
+/* ---- flexible GMRES(m): every kind of cvr_precond, or a caller's apply ----
+ * cvr_pgmres forms x as x += M^-1 (V y): a second apply per cycle on an fp64 combination, which only block-Jacobi and ILU(0) have a form for, and
+ * which is right only when M^-1 is the same linear operator at every step.  Flexible GMRES (Saad, SIAM J. Sci. Comput. 14, 1993) keeps
+ * z_j = M_j^-1 v_j for every column of the cycle and forms x = x0 + Z y: no apply outside the steps, and M_j may differ from step to step.  The
+ * price is `restart` more vectors.  The options, the result, the status codes, the range of `restart` (1 .. CVR_GMRES_MAX_RESTART), check_every and
+ * the ordering on `stream` are cvr_gmres_device's; the start of the call and of every cycle, the two Gram-Schmidt passes, the rotations, the
+ * scalars, the fixed-tree sums and the stop rules are its text word for word with w = T(A z_j).
+ *
+ * Which preconditioner is used: exactly one of three cases.
+ *   p != NULL    any kind that cvr_precond_apply_device accepts (an object of cvr_precond_amg_block included), z_j = M^-1 v_j by that entry point's
+ *                arithmetic for the kind.  (The kinds that are symmetric positive definite by construction -- Chebyshev, FSAI, plain AMG -- are taken
+ *                as well: whether they help on a nonsymmetric A is the caller's judgement.)
+ *   fn != NULL   z_j = whatever fn leaves in z_dev, see below.
+ *   neither      z_j = v_j, Z is the basis itself (nothing is copied): x, iterations, status, residual_norm and b_norm are bit for bit what
+ *                cvr_gmres_device returns without minv_dev.
+ * Both set: CVR_ERR_INVALID.  opt->minv_dev != NULL: CVR_ERR_INVALID in all three cases (the diagonal is cvr_gmres_device's).
+ *
+ * Storage: restart + 1 basis vectors and, with a preconditioner, `restart` columns of Z, each an SpMV input of the handle (ncols + 1 values), in the
+ *   call's one allocation; CVR_ERR_NOMEM names both counts and the bytes.  No fp64 combination is kept.
+ * Forming x from q columns (q = 0: nothing): y as in cvr_gmres_device.  Per element u = +0; for i = 0..q-1: u = u + y_i * double(Z_i);
+ *   x_i = T(double(x_i) + u).  One launch.
+ * Stops inside a batch: a block-Jacobi or ILU(0) apply behind a stop writes nothing.  The other kinds' applies and the callback are not gated: for
+ *   the steps the host has enqueued behind a stop they still run (the callback is still called), on vectors that hold no meaning, and write columns
+ *   of Z that nothing reads -- the steps are ordered so that a column x is still owed is never written before x is formed.  The contract that
+ *   follows: x and the result do not depend on check_every.
+ * spmv_count: the handle's own products enqueued, 1 + the steps + the restarts, as cvr_gmres_device counts.  The products that an object's apply
+ *   makes (Chebyshev, FSAI, AMG) are not counted, and a callback's are unknown.
+ *
+ * The callback: int fn(ctx, v_dev, z_dev, n, stream), called on the host, in the calling thread, while step k is being enqueued (once per step, in the
+ *   order of the steps, so its k-th call, counted from 0, belongs to step k).  v_dev and z_dev are 16-byte-aligned buffers of the library of n
+ *   values of the handle's type on the handle's device; they do not overlap.  It must leave z = M_k^-1 v complete in stream order on `stream`
+ *   (cast to hipStream_t): it may enqueue there, or synchronise and do anything else.  It must not call into this library with the same handle.  A
+ *   non-zero return ends the solve with CVR_ERR_STATE, cvr_last_error naming the callback's code and the step; nothing further is enqueued, the
+ *   call's buffers are released behind what is enqueued, and x_dev holds no meaning.
+ *
+ * Errors, in this order.  Before any device work and before the handle is looked at: cvr_cg_device's argument checks (p may be null); p and fn
+ * both set; opt->minv_dev != NULL; restart < 1 or restart > CVR_GMRES_MAX_RESTART: CVR_ERR_INVALID.  Then: before cvr_preprocess: CVR_ERR_STATE;
+ * nrows != ncols: CVR_ERR_INVALID; with p, the three mismatches of cvr_pcg_device, each CVR_ERR_INVALID with "cvr_fgmres" in cvr_last_error; no
+ * device memory for the call's buffers: CVR_ERR_NOMEM, nothing allocated. */
+typedef int (*cvr_apply_fn)(void *ctx, const void *v_dev, void *z_dev, int64_t n, void *stream);
+int cvr_fgmres_device(cvr_handle *h, const cvr_precond *p, cvr_apply_fn fn, void *ctx, const void *b_dev, void *x_dev, int32_t restart,
+                      const cvr_cg_options *opt, cvr_cg_result *res, void *stream);
+/* the same with host b and x (nrows values each; x in and out), as cvr_cg */
+int cvr_fgmres(cvr_handle *h, const cvr_precond *p, cvr_apply_fn fn, void *ctx, const void *b_host, void *x_host, int32_t restart,
+               const cvr_cg_options *opt, cvr_cg_result *res);
+
 /* ---- a colouring of A's graph, and a sixth kind of cvr_precond on it: multicolour symmetric Gauss-Seidel ----
  * ILU(0)'s sweeps have as many stages as the longest dependency chain of the ordering, thousands on a Laplacian in its natural order.  Colour the
  * graph so that no two coupled rows share a colour, order the rows by colour, and a triangular sweep has as many stages as there are colours,
