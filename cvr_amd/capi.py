@@ -316,7 +316,6 @@ def lib():
         L.cvr_spmv_scaled_device.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         L.cvr_spmv_scaled.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_void_p]
         L.cvr_cg_default_options.argtypes = [C.POINTER(CgOptions)]
-        L.cvr_cg_default_options.restype = None
         L.cvr_cg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
         L.cvr_cg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CgOptions), C.POINTER(CgResult)]
         L.cvr_cg_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(CgOptions), C.POINTER(CgResult), C.c_void_p]
@@ -393,24 +392,23 @@ def lib():
         L.cvr_minres_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo), C.c_void_p]
         L.cvr_minres.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(CgOptions), C.POINTER(CgResult), C.POINTER(MinresInfo)]
         L.cvr_eig_default_options.argtypes = [C.POINTER(EigOptions)]
-        L.cvr_eig_default_options.restype = None
         L.cvr_eigsh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult), C.c_void_p]
         L.cvr_eigsh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(EigOptions), C.POINTER(EigResult)]
         L.cvr_sym_eig_host.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.cvr_svd_default_options.argtypes = [C.POINTER(SvdOptions)]
-        L.cvr_svd_default_options.restype = None
         L.cvr_svds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(SvdOptions),
                                       C.POINTER(SvdResult), C.c_void_p]
         L.cvr_svds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(SvdOptions),
                                C.POINTER(SvdResult)]
         L.cvr_svd_host.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.cvr_lobpcg_default_options.argtypes = [C.POINTER(LobpcgOptions)]
-        L.cvr_lobpcg_default_options.restype = None
         L.cvr_lobpcg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LobpcgOptions), C.POINTER(LobpcgResult), C.c_void_p]
         L.cvr_lobpcg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(LobpcgOptions), C.POINTER(LobpcgResult)]
         L.cvr_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.cvr_update_values.argtypes = [C.c_void_p, C.c_void_p]
         L.cvr_update_values_supported.argtypes = [C.c_void_p]
+        for f in ("cvr_cg_default_options", "cvr_eig_default_options", "cvr_svd_default_options", "cvr_lobpcg_default_options"):
+            getattr(L, f).restype = None
         for f in ("cvr_x_device", "cvr_y_device", "cvr_stream"):
             getattr(L, f).argtypes = [C.c_void_p]
             getattr(L, f).restype = C.c_void_p
@@ -483,15 +481,37 @@ def row_partition(row_ptr, nparts, row_cost_milli=0):
     return bounds
 
 
+def _host_view(rp, ci, vals=None, shape=None):
+    """(view, keep) of host CSR arrays: a CsrView of a square matrix of len(rp) - 1 rows, or of shape = (nrows, ncols), over the arrays made contiguous
+    in the ABI's types (vals: float32 stays, anything else becomes float64; None: the pattern alone), and `keep` = (rp, ci[, vals]), those arrays.
+    The view holds raw pointers into them and no reference: whoever passes the view to C holds `keep` until that call has returned.  Raises the
+    ValueError of a short row_ptr, col_idx or vals; loads no library."""
+    rp = np.ascontiguousarray(rp, dtype=np.int64)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    nrows, ncols = (len(rp) - 1,) * 2 if shape is None else shape
+    if vals is None:
+        return CsrView(nrows, ncols, rp.ctypes.data, ci.ctypes.data, None, 0, 0), (rp, ci)
+    f32 = np.asarray(vals).dtype == np.float32
+    va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
+    if len(rp) != nrows + 1:
+        raise ValueError("row_ptr must have nrows + 1 entries")
+    if nrows > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
+        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    return CsrView(int(nrows), int(ncols), rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), (rp, ci, va)
+
+
+def _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False):
+    """the CsrView of a square matrix of n rows whose CSR arrays are the caller's, in a device's memory (raw pointers)"""
+    return CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1)
+
+
 def ilu0_levels_host(rp, ci):
     """cvr_ilu0_levels_host: (lower_level, upper_level, n_lower, n_upper) of a square CSR pattern with sorted rows and a diagonal in every row -- the
     level of each row in the L and the U sweep of Precond.ilu0, and the number of levels of each.  Host only."""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    n = len(rp) - 1
+    view, keep = _host_view(rp, ci)
+    n = view.nrows
     lo, up = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
     nlo, nup = C.c_int32(), C.c_int32()
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
     rc = lib().cvr_ilu0_levels_host(C.byref(view), lo.ctypes.data, up.ctypes.data, C.byref(nlo), C.byref(nup))
     if rc:
         raise CvrError(rc, "cvr_ilu0_levels_host")
@@ -511,43 +531,27 @@ def color_host(rp, ci):
     """cvr_color_host: (color, perm, color_ptr, ncolors, rounds) of a square CSR pattern with sorted rows, a diagonal in every row and a structurally
     symmetric off-diagonal pattern -- the colouring by rounds on hashed keys (greedy first-fit in descending key order), the rows ordered by
     (colour, row) and where each colour begins in that order.  Host only."""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    n = len(rp) - 1
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
-    return _color(lambda v, *a: lib().cvr_color_host(C.byref(v), *a), "cvr_color_host", n, view)
+    view, keep = _host_view(rp, ci)
+    return _color(lambda v, *a: lib().cvr_color_host(C.byref(v), *a), "cvr_color_host", view.nrows, view)
 
 
 def color_device(rp, ci, device=0, on_device=False, n=None):
     """cvr_color_device: the same on `device`, from host arrays, or (on_device: rp and ci are raw pointers, n the number of rows) from arrays in the
     device's memory; the outputs are host arrays either way"""
-    if on_device:
-        view = CsrView(n, n, rp, ci, None, 0, 1)
-    else:
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        n = len(rp) - 1
-        view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, None, 0, 0)
-    return _color(lambda v, *a: lib().cvr_color_device(C.byref(v), int(device), None, *a), "cvr_color_device", n, view)
+    view, keep = (_device_view(n, rp, ci, None), None) if on_device else _host_view(rp, ci)
+    return _color(lambda v, *a: lib().cvr_color_device(C.byref(v), int(device), None, *a), "cvr_color_device", view.nrows, view)
 
 
 def fsai_factor_host(rp, ci, vals):
     """cvr_fsai_factor_host: (row_ptr, col_idx, wa, wb, bad_row) of the FSAI factor W of a square CSR matrix with sorted rows and a diagonal in every
     row -- what Precond.fsai computes on the device, in host code (the type is vals' dtype, float32 or else float64).  bad_row is None, or the lowest
     row whose pivot is not finite or not > 0: the arrays then hold the rows before it.  Host only."""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    f32 = np.asarray(vals).dtype == np.float32
-    dtype = np.float32 if f32 else np.float64
-    va = np.ascontiguousarray(vals, dtype=dtype)
-    n = len(rp) - 1
-    room = max(int(rp[-1]), 1) if n > 0 else 1
-    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
+    view, keep = _host_view(rp, ci, vals)
+    n, dtype = view.nrows, keep[2].dtype
+    room = max(int(keep[0][-1]), 1) if n > 0 else 1
     wrp, wci = np.zeros(n + 1, dtype=np.int64), np.zeros(room, dtype=np.int32)
     wa, wb = np.zeros(room, dtype=dtype), np.zeros(room, dtype=dtype)
     bad = C.c_int64(-1)
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
     rc = lib().cvr_fsai_factor_host(C.byref(view), wrp.ctypes.data, wci.ctypes.data, wa.ctypes.data, wb.ctypes.data, C.byref(bad))
     if rc and not (rc == ERR_STATE and bad.value >= 0):
         raise CvrError(rc, "cvr_fsai_factor_host")
@@ -564,6 +568,15 @@ def amg_options(**kw):
             raise TypeError(f"cvr_amg_options has no field {k}")
         setattr(o, k, v)
     return o
+
+
+def _amg_setup(setup):
+    """CVR_AMG_SETUP_* of Precond.amg_block's `setup`: a name of AMG_SETUPS, or the number itself"""
+    if not isinstance(setup, str):
+        return setup
+    if setup not in AMG_SETUPS:
+        raise ValueError(f"setup = {setup!r}: one of {sorted(AMG_SETUPS)}")
+    return AMG_SETUPS[setup]
 
 
 class AmgLevel:
@@ -592,31 +605,7 @@ def amg_setup_host(rp, ci, vals, **options):
     """cvr_amg_setup_host: (AmgInfo, [AmgLevel, ...]) of the AMG hierarchy of a square CSR matrix with sorted rows and a diagonal in every row -- what
     Precond.amg builds, in host code (the type is vals' dtype, float32 or else float64; options as amg_options).  A diagonal entry or a pivot of the
     coarsest matrix that is not finite or not > 0 raises CvrError (ERR_STATE) with .bad = (level, row).  Host only."""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    f32 = np.asarray(vals).dtype == np.float32
-    dtype = np.float32 if f32 else np.float64
-    va = np.ascontiguousarray(vals, dtype=dtype)
-    n = len(rp) - 1
-    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-    L = lib()
-    opt = amg_options(**options)
-    h, bad_level, bad_row = C.c_void_p(), C.c_int32(-1), C.c_int64(-1)
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
-    rc = L.cvr_amg_setup_host(C.byref(h), C.byref(view), C.byref(opt), C.byref(bad_level), C.byref(bad_row))
-    if rc:
-        e = CvrError(rc, "cvr_amg_setup_host")
-        e.bad = (bad_level.value, bad_row.value) if bad_level.value >= 0 else None
-        raise e
-    try:
-        info = AmgInfo()
-        rc = L.cvr_amg_hierarchy_info(h, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_amg_hierarchy_info")
-        return info, [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
-    finally:
-        L.cvr_amg_hierarchy_destroy(h)
+    return _amg_hierarchy_host("cvr_amg_setup_host", rp, ci, vals, options)
 
 
 class AmgProlongator:
@@ -640,27 +629,20 @@ def amg_smoothed_setup_host(rp, ci, vals, omega=0.0, **options):
     """cvr_amg_smoothed_setup_host: (AmgInfo, AmgSmoothedInfo, [AmgLevel, ...], [AmgProlongator, ...]) of the smoothed-aggregation hierarchy of a
     square CSR matrix with sorted rows and a diagonal in every row -- what Precond.amg_smoothed builds, in host code.  omega = 0.0: the default 4/3.
     Errors as amg_setup_host.  Host only."""
-    return _amg_smoothed_setup_host("cvr_amg_smoothed_setup_host", rp, ci, vals, omega, options)[:4]
+    return _amg_hierarchy_host("cvr_amg_smoothed_setup_host", rp, ci, vals, options, omega)[:4]
 
 
 def amg_mis2_setup_host(rp, ci, vals, omega=0.0, **options):
     """cvr_amg_mis2_setup_host: (AmgInfo, AmgSmoothedInfo, [AmgLevel, ...], [AmgProlongator, ...], AmgMis2Info) of the smoothed-aggregation hierarchy
     with the MIS(2) aggregation -- what Precond.amg_mis2 builds, in host code.  Errors as amg_smoothed_setup_host.  Host only."""
-    return _amg_smoothed_setup_host("cvr_amg_mis2_setup_host", rp, ci, vals, omega, options)
+    return _amg_hierarchy_host("cvr_amg_mis2_setup_host", rp, ci, vals, options, omega)
 
 
 def amg_mis2_aggregate_host(rp, ci, vals, strength=0.08):
     """cvr_amg_mis2_aggregate_host: (agg as int32, nc, rounds) of the MIS(2) aggregation of a square CSR matrix with sorted rows and a diagonal entry
     in every row.  Host only."""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    f32 = np.asarray(vals).dtype == np.float32
-    va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-    n = len(rp) - 1
-    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-    agg, nc, rounds = np.full(n, -1, dtype=np.int32), C.c_int64(-1), C.c_int32(-1)
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
+    view, keep = _host_view(rp, ci, vals)
+    agg, nc, rounds = np.full(view.nrows, -1, dtype=np.int32), C.c_int64(-1), C.c_int32(-1)
     rc = lib().cvr_amg_mis2_aggregate_host(C.byref(view), float(strength), agg.ctypes.data, C.byref(nc), C.byref(rounds))
     if rc:
         raise CvrError(rc, "cvr_amg_mis2_aggregate_host")
@@ -670,65 +652,47 @@ def amg_mis2_aggregate_host(rp, ci, vals, strength=0.08):
 def amg_mis2_aggregate_device(n, row_ptr_dev, col_idx_dev, vals_dev, agg_dev, is_f32=False, strength=0.08, device=0, stream=None):
     """cvr_amg_mis2_aggregate_device: (nc, rounds); agg_dev receives n int32 values.  CSR arrays and agg_dev in the memory of `device` (raw pointers)"""
     nc, rounds = C.c_int64(-1), C.c_int32(-1)
-    view = CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1)
+    view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
     rc = lib().cvr_amg_mis2_aggregate_device(C.byref(view), float(strength), agg_dev, C.byref(nc), C.byref(rounds), int(device), stream)
     if rc:
         raise CvrError(rc, "cvr_amg_mis2_aggregate_device")
     return nc.value, rounds.value
 
 
-def _amg_smoothed_setup_host(entry, rp, ci, vals, omega, options):
-    """the set-up through `entry` (cvr_amg_smoothed_setup_host or cvr_amg_mis2_setup_host) and everything the hierarchy exports"""
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    f32 = np.asarray(vals).dtype == np.float32
-    dtype = np.float32 if f32 else np.float64
-    va = np.ascontiguousarray(vals, dtype=dtype)
-    n = len(rp) - 1
-    if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-    L = lib()
+def _amg_hierarchy_host(entry, rp, ci, vals, options, *omega):
+    """the host set-up through `entry` and everything its hierarchy exports: (info, levels) of cvr_amg_setup_host; with omega, of
+    cvr_amg_smoothed_setup_host or cvr_amg_mis2_setup_host, (info, sinfo, levels, prolongators, minfo)"""
+    view, keep = _host_view(rp, ci, vals)
+    L, dtype = lib(), keep[2].dtype
     opt = amg_options(**options)
     h, bad_level, bad_row = C.c_void_p(), C.c_int32(-1), C.c_int64(-1)
-    view = CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0)
-    rc = getattr(L, entry)(C.byref(h), C.byref(view), C.byref(opt), float(omega), C.byref(bad_level), C.byref(bad_row))
+    rc = getattr(L, entry)(C.byref(h), C.byref(view), C.byref(opt), *map(float, omega), C.byref(bad_level), C.byref(bad_row))
     if rc:
         e = CvrError(rc, entry)
         e.bad = (bad_level.value, bad_row.value) if bad_level.value >= 0 else None
         raise e
     try:
         info, sinfo, minfo = AmgInfo(), AmgSmoothedInfo(), AmgMis2Info()
-        rc = L.cvr_amg_hierarchy_info(h, C.byref(info)) or L.cvr_amg_hierarchy_smoothed_info(h, C.byref(sinfo)) or L.cvr_amg_hierarchy_mis2_info(h, C.byref(minfo))
+        rc = L.cvr_amg_hierarchy_info(h, C.byref(info))
+        if omega:
+            rc = rc or L.cvr_amg_hierarchy_smoothed_info(h, C.byref(sinfo)) or L.cvr_amg_hierarchy_mis2_info(h, C.byref(minfo))
         if rc:
             raise CvrError(rc, "cvr_amg_hierarchy_info")
         levels = [_amg_export(L.cvr_amg_hierarchy_export_level, h, info, l, dtype) for l in range(info.levels)]
+        if not omega:
+            return info, levels
         return info, sinfo, levels, [_amg_export_prolongator(L.cvr_amg_hierarchy_export_prolongator, h, info, sinfo, l, dtype) for l in range(info.levels - 1)], minfo
     finally:
         L.cvr_amg_hierarchy_destroy(h)
-
-
-def _host_csr(csr):
-    """(nrows, ncols, rp, ci, va, f32) of a (nrows, ncols, row_ptr, col_idx, vals) tuple, the arrays contiguous and of the ABI's types"""
-    nrows, ncols, rp, ci, va = csr
-    rp = np.ascontiguousarray(rp, dtype=np.int64)
-    ci = np.ascontiguousarray(ci, dtype=np.int32)
-    f32 = np.asarray(va).dtype == np.float32
-    va = np.ascontiguousarray(va, dtype=np.float32 if f32 else np.float64)
-    if len(rp) != nrows + 1:
-        raise ValueError("row_ptr must have nrows + 1 entries")
-    if nrows > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-        raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-    return int(nrows), int(ncols), rp, ci, va, f32
 
 
 def spgemm_host(a_csr, b_csr):
     """cvr_spgemm_host: (row_ptr, col_idx, vals) of C = A B for two (nrows, ncols, row_ptr, col_idx, vals) tuples of host arrays of one dtype (float32
     or else float64) -- what SpGemm computes on the device, in host code, by the two calls of the ABI.  B's rows must be strictly ascending in
     column: a violation raises CvrError (ERR_INVALID) with .bad_row.  Host only."""
-    m, k, arp, aci, ava, af32 = _host_csr(a_csr)
-    k2, n, brp, bci, bva, bf32 = _host_csr(b_csr)
-    va_ = CsrView(m, k, arp.ctypes.data, aci.ctypes.data, ava.ctypes.data, int(af32), 0)
-    vb_ = CsrView(k2, n, brp.ctypes.data, bci.ctypes.data, bva.ctypes.data, int(bf32), 0)
+    va_, keep_a = _host_view(*a_csr[2:], shape=a_csr[:2])
+    vb_, keep_b = _host_view(*b_csr[2:], shape=b_csr[:2])
+    m = va_.nrows
     crp, bad = np.zeros(m + 1, dtype=np.int64), C.c_int64(-1)
 
     def call(ci_ptr, va_ptr):
@@ -739,7 +703,7 @@ def spgemm_host(a_csr, b_csr):
             raise e
     call(None, None)
     nnz = int(crp[m])
-    cci, cva = np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=np.float32 if af32 else np.float64)
+    cci, cva = np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1), dtype=keep_a[2].dtype)
     call(cci.ctypes.data, cva.ctypes.data)
     return crp, cci[:nnz], cva[:nnz]
 
@@ -754,10 +718,9 @@ class SpGemm:
     def create(cls, a_csr, b_csr, device=0, stream=None):
         """from two (nrows, ncols, row_ptr, col_idx, vals) tuples of host arrays of one dtype; A may be unsorted with duplicates, B's rows must
         be strictly ascending in column"""
-        m, k, arp, aci, ava, af32 = _host_csr(a_csr)
-        k2, n, brp, bci, bva, bf32 = _host_csr(b_csr)
-        return cls._from_views(CsrView(m, k, arp.ctypes.data, aci.ctypes.data, ava.ctypes.data, int(af32), 0),
-                               CsrView(k2, n, brp.ctypes.data, bci.ctypes.data, bva.ctypes.data, int(bf32), 0), device, stream)
+        va_, keep_a = _host_view(*a_csr[2:], shape=a_csr[:2])
+        vb_, keep_b = _host_view(*b_csr[2:], shape=b_csr[:2])
+        return cls._from_views(va_, vb_, device, stream)
 
     @classmethod
     def from_device(cls, a_dev, b_dev, is_f32=False, device=0, stream=None):
@@ -1052,53 +1015,49 @@ class Precond:
         self.info = PrecondInfo()
 
     @classmethod
+    def _build(cls, entry, *args, matrix=None):
+        """the object of one constructor of the ABI, entry(&p, *args).  A view among args points into arrays its maker returned beside it (_host_view's
+        `keep`): the calling constructor holds them in a local until this returns.  matrix: the CvrMatrix the object borrows, kept alive with it."""
+        self = cls()
+        rc = getattr(lib(), entry)(C.byref(self._p), *args)
+        if rc:
+            self._p = C.c_void_p()
+            raise CvrError(rc, entry)
+        lib().cvr_precond_get_info(self._p, C.byref(self.info))
+        self.dtype = np.float32 if self.info.is_f32 else np.float64
+        if matrix is not None:
+            self._matrix = matrix
+        return self
+
+    def _info(self, entry, struct_type):
+        """one info call of the ABI, entry(p, &info): the filled struct_type"""
+        info = struct_type()
+        rc = getattr(lib(), entry)(self._p, C.byref(info))
+        if rc:
+            raise CvrError(rc, entry)
+        return info
+
+    @classmethod
     def block_jacobi(cls, rp, ci, vals, block_size, device=0):
         """cvr_precond_block_jacobi from host CSR arrays of a square matrix (n = len(rp) - 1; the type is vals' dtype, float32 or else float64)"""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), block_size, device)
+        view, keep = _host_view(rp, ci, vals)
+        return cls._build("cvr_precond_block_jacobi", C.byref(view), int(block_size), int(device), None)
 
     @classmethod
     def block_jacobi_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, block_size, is_f32=False, device=0):
         """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
-        return cls._from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), block_size, device)
-
-    @classmethod
-    def _from_view(cls, view, block_size, device):
-        self = cls()
-        rc = lib().cvr_precond_block_jacobi(C.byref(self._p), C.byref(view), int(block_size), int(device), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_block_jacobi")
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        return self
+        view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
+        return cls._build("cvr_precond_block_jacobi", C.byref(view), int(block_size), int(device), None)
 
     @classmethod
     def chebyshev(cls, matrix, degree, lmin, lmax):
         """cvr_precond_chebyshev: z = p_degree(A) r, the Chebyshev polynomial for a spectrum in [lmin, lmax], applied through `matrix`'s own SpMV.  The
         object borrows the CvrMatrix (kept alive here; close the object before the matrix) and serves one stream at a time."""
-        self = cls()
-        rc = lib().cvr_precond_chebyshev(C.byref(self._p), matrix._h, int(degree), float(lmin), float(lmax))
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_chebyshev")
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        self._matrix = matrix
-        return self
+        return cls._build("cvr_precond_chebyshev", matrix._h, int(degree), float(lmin), float(lmax), matrix=matrix)
 
     def chebyshev_info(self):
         """cvr_precond_chebyshev_info: dict(degree, is_f32, lmin, lmax, a, b) with the degree coefficients a[k], b[k] (a[0] = 0, b[0] = c0) as fp64 arrays"""
-        ci = ChebyshevInfo()
-        rc = lib().cvr_precond_chebyshev_info(self._p, C.byref(ci))
-        if rc:
-            raise CvrError(rc, "cvr_precond_chebyshev_info")
+        ci = self._info("cvr_precond_chebyshev_info", ChebyshevInfo)
         return dict(degree=ci.degree, is_f32=ci.is_f32, lmin=ci.lmin, lmax=ci.lmax, a=np.array(ci.a[: ci.degree], dtype=np.float64),
                     b=np.array(ci.b[: ci.degree], dtype=np.float64))
 
@@ -1106,68 +1065,36 @@ class Precond:
     def ilu0(cls, rp, ci, vals, device=0):
         """cvr_precond_ilu0 from host CSR arrays of a square matrix whose rows are sorted, without duplicates and with a diagonal entry each
         (n = len(rp) - 1; the type is vals' dtype, float32 or else float64).  Serves one stream at a time."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._ilu0_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+        view, keep = _host_view(rp, ci, vals)
+        return cls._build("cvr_precond_ilu0", C.byref(view), int(device), None)
 
     @classmethod
     def ilu0_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
         """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
-        return cls._ilu0_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
-
-    @classmethod
-    def _ilu0_from_view(cls, view, device, sweeps=None):
-        self = cls()
-        if sweeps is None:
-            name, rc = "cvr_precond_ilu0", lib().cvr_precond_ilu0(C.byref(self._p), C.byref(view), int(device), None)
-        else:
-            name, rc = "cvr_precond_ilu0_jacobi", lib().cvr_precond_ilu0_jacobi(C.byref(self._p), C.byref(view), int(sweeps), int(device), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, name)
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        return self
+        view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
+        return cls._build("cvr_precond_ilu0", C.byref(view), int(device), None)
 
     @classmethod
     def ilu0_jacobi(cls, rp, ci, vals, sweeps, device=0):
         """cvr_precond_ilu0_jacobi from host CSR arrays, read as Precond.ilu0 reads them: the same ILU(0) factors, each triangular solve of the apply
         replaced by `sweeps` (1 .. ILU0_MAX_SWEEPS) Jacobi sweeps -- 2 * sweeps launches per apply whatever the level structure.  Kind 2: pcg,
         pbicgstab and pgmres take it as they take Precond.ilu0's.  Serves one stream at a time."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._ilu0_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device, sweeps)
+        view, keep = _host_view(rp, ci, vals)
+        return cls._build("cvr_precond_ilu0_jacobi", C.byref(view), int(sweeps), int(device), None)
 
     @classmethod
     def ilu0_jacobi_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, sweeps, is_f32=False, device=0):
         """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
-        return cls._ilu0_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device, sweeps)
+        view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
+        return cls._build("cvr_precond_ilu0_jacobi", C.byref(view), int(sweeps), int(device), None)
 
     def ilu0_jacobi_info(self):
         """cvr_precond_ilu0_jacobi_info: an Ilu0JacobiInfo (n, nnz, sweeps, launches_per_apply, lanes_per_row, levels_*, is_f32)"""
-        info = Ilu0JacobiInfo()
-        rc = lib().cvr_precond_ilu0_jacobi_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_ilu0_jacobi_info")
-        return info
+        return self._info("cvr_precond_ilu0_jacobi_info", Ilu0JacobiInfo)
 
     def ilu0_info(self):
         """cvr_precond_ilu0_info: an Ilu0Info (n, nnz, levels_*, launches_*, max_level_width, lanes_per_row, wide_threshold, is_f32)"""
-        info = Ilu0Info()
-        rc = lib().cvr_precond_ilu0_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_ilu0_info")
-        return info
+        return self._info("cvr_precond_ilu0_info", Ilu0Info)
 
     def ilu0_export(self):
         """cvr_precond_ilu0_export: nnz values of the object's dtype in the CSR's own positions -- L strictly below the diagonal (without its unit
@@ -1184,38 +1111,18 @@ class Precond:
         """cvr_precond_mcsgs from host CSR arrays of a square matrix whose rows are sorted, without duplicates and with a diagonal entry each, and
         whose off-diagonal pattern is structurally symmetric (n = len(rp) - 1; the type is vals' dtype, float32 or else float64): multicolour
         symmetric Gauss-Seidel, 2 * ncolors launches per apply.  Serves one stream at a time."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._mcsgs_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+        view, keep = _host_view(rp, ci, vals)
+        return cls._build("cvr_precond_mcsgs", C.byref(view), int(device), None)
 
     @classmethod
     def mcsgs_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
         """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
-        return cls._mcsgs_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
-
-    @classmethod
-    def _mcsgs_from_view(cls, view, device):
-        self = cls()
-        rc = lib().cvr_precond_mcsgs(C.byref(self._p), C.byref(view), int(device), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_mcsgs")
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        return self
+        view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
+        return cls._build("cvr_precond_mcsgs", C.byref(view), int(device), None)
 
     def mcsgs_info(self):
         """cvr_precond_mcsgs_info: a McSgsInfo (n, nnz, ncolors, rounds, launches_per_apply, lanes_per_row, max_color_rows, min_color_rows, is_f32)"""
-        info = McSgsInfo()
-        rc = lib().cvr_precond_mcsgs_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_mcsgs_info")
-        return info
+        return self._info("cvr_precond_mcsgs_info", McSgsInfo)
 
     def mcsgs_export(self):
         """cvr_precond_mcsgs_export: (color, perm, color_ptr) of the object's colouring as int32 arrays"""
@@ -1231,38 +1138,18 @@ class Precond:
         """cvr_precond_fsai from host CSR arrays of a symmetric positive definite matrix whose rows are sorted, without duplicates and with a
         diagonal entry each; only the entries with column <= row are read (n = len(rp) - 1; the type is vals' dtype, float32 or else float64).
         Serves one stream at a time."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._fsai_from_view(CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), device)
+        view, keep = _host_view(rp, ci, vals)
+        return cls._build("cvr_precond_fsai", C.byref(view), int(device), None)
 
     @classmethod
     def fsai_from_device(cls, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, device=0):
         """the same from CSR arrays in the memory of `device` (raw pointers, as CvrMatrix.from_device)"""
-        return cls._fsai_from_view(CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), device)
-
-    @classmethod
-    def _fsai_from_view(cls, view, device):
-        self = cls()
-        rc = lib().cvr_precond_fsai(C.byref(self._p), C.byref(view), int(device), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_fsai")
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        return self
+        view = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32)
+        return cls._build("cvr_precond_fsai", C.byref(view), int(device), None)
 
     def fsai_info(self):
         """cvr_precond_fsai_info: an FsaiInfo (n, nnz of W, max_row, lanes_per_row, truncated_rows, is_f32)"""
-        info = FsaiInfo()
-        rc = lib().cvr_precond_fsai_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_fsai_info")
-        return info
+        return self._info("cvr_precond_fsai_info", FsaiInfo)
 
     def fsai_export(self):
         """cvr_precond_fsai_export: (row_ptr, col_idx, wa, wb) of W -- its own CSR pattern (A's lower triangle, a row's CVR_FSAI_MAX_ROW entries
@@ -1281,55 +1168,43 @@ class Precond:
         """cvr_precond_amg: one V-cycle of plain aggregation AMG for the symmetric positive definite `matrix` (a CvrMatrix, borrowed for level 0's
         products and kept alive here; close the object before the matrix), from host CSR arrays of the same matrix whose rows are sorted, without
         duplicates and with a diagonal entry each.  options: max_levels, coarse_size, sweeps, strength, coarse_scale.  Serves one stream at a time."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options)
+        view, keep = _host_view(rp, ci, vals)
+        opt = amg_options(**options)
+        return cls._build("cvr_precond_amg", matrix._h, C.byref(view), C.byref(opt), None, matrix=matrix)
 
     @classmethod
     def amg_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, **options):
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
-        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options)
+        view, opt = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32), amg_options(**options)
+        return cls._build("cvr_precond_amg", matrix._h, C.byref(view), C.byref(opt), None, matrix=matrix)
 
     @classmethod
     def amg_smoothed(cls, matrix, rp, ci, vals, omega=0.0, **options):
         """cvr_precond_amg_smoothed: Precond.amg with the smoothed prolongator P = (I - omega D^-1 A) T and the Galerkin coarse operators P^T A P,
         built on the device by the SpGEMM; omega = 0.0: the default 4/3, else 0 < omega < 2.  The same kind of object (kind 4) for the same calls."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options, omega)
+        view, keep = _host_view(rp, ci, vals)
+        opt = amg_options(**options)
+        return cls._build("cvr_precond_amg_smoothed", matrix._h, C.byref(view), C.byref(opt), float(omega), None, matrix=matrix)
 
     @classmethod
     def amg_smoothed_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, omega=0.0, **options):
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
-        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega)
+        view, opt = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32), amg_options(**options)
+        return cls._build("cvr_precond_amg_smoothed", matrix._h, C.byref(view), C.byref(opt), float(omega), None, matrix=matrix)
 
     @classmethod
     def amg_mis2(cls, matrix, rp, ci, vals, omega=0.0, **options):
         """cvr_precond_amg_mis2: Precond.amg_smoothed with the MIS(2) aggregation, the whole level loop on the device; the same kind of object
         (kind 4, smoothed) for the same calls."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._amg_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), options, omega, mis2=True)
+        view, keep = _host_view(rp, ci, vals)
+        opt = amg_options(**options)
+        return cls._build("cvr_precond_amg_mis2", matrix._h, C.byref(view), C.byref(opt), float(omega), None, matrix=matrix)
 
     @classmethod
     def amg_mis2_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, is_f32=False, omega=0.0, **options):
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
-        return cls._amg_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), options, omega, mis2=True)
+        view, opt = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32), amg_options(**options)
+        return cls._build("cvr_precond_amg_mis2", matrix._h, C.byref(view), C.byref(opt), float(omega), None, matrix=matrix)
 
     @classmethod
     def amg_block(cls, matrix, rp, ci, vals, nvec, setup="plain", omega=0.0, **options):
@@ -1337,89 +1212,35 @@ class Precond:
         Precond.amg_mis2 ("mis2") -- the same hierarchy byte for byte -- built for blocks of up to nvec = K columns, 1 .. 8: apply_multi and
         CvrMatrix.pcg_multi / pcg_multi_host take it for 1 <= nvec <= K, one V-cycle for all columns.  For K >= 2 `matrix` must have the plain
         layout (nvec >= 2 at creation).  apply, pcg and pcg_host take it as any kind-4 object."""
-        rp = np.ascontiguousarray(rp, dtype=np.int64)
-        ci = np.ascontiguousarray(ci, dtype=np.int32)
-        f32 = np.asarray(vals).dtype == np.float32
-        va = np.ascontiguousarray(vals, dtype=np.float32 if f32 else np.float64)
-        n = len(rp) - 1
-        if n > 0 and (len(ci) < rp[-1] or len(va) < rp[-1]):
-            raise ValueError(f"col_idx / vals hold {len(ci)} / {len(va)} entries, row_ptr[nrows] = {int(rp[-1])}")
-        return cls._amg_block_from_view(matrix, CsrView(n, n, rp.ctypes.data, ci.ctypes.data, va.ctypes.data, int(f32), 0), nvec, setup, omega, options)
+        view, keep = _host_view(rp, ci, vals)
+        opt, setup = amg_options(**options), _amg_setup(setup)
+        return cls._build("cvr_precond_amg_block", matrix._h, C.byref(view), C.byref(opt), int(setup), float(omega), int(nvec), None, matrix=matrix)
 
     @classmethod
     def amg_block_from_device(cls, matrix, n, row_ptr_dev, col_idx_dev, vals_dev, nvec, is_f32=False, setup="plain", omega=0.0, **options):
         """the same from CSR arrays in the memory of the matrix's device (raw pointers, as CvrMatrix.from_device)"""
-        return cls._amg_block_from_view(matrix, CsrView(n, n, row_ptr_dev, col_idx_dev, vals_dev, int(bool(is_f32)), 1), nvec, setup, omega, options)
-
-    @classmethod
-    def _amg_block_from_view(cls, matrix, view, nvec, setup, omega, options):
-        self = cls()
-        opt = amg_options(**options)
-        if isinstance(setup, str):
-            if setup not in AMG_SETUPS:
-                raise ValueError(f"setup = {setup!r}: one of {sorted(AMG_SETUPS)}")
-            setup = AMG_SETUPS[setup]
-        rc = lib().cvr_precond_amg_block(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), int(setup), float(omega), int(nvec), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, "cvr_precond_amg_block")
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        self._matrix = matrix
-        return self
+        view, opt, setup = _device_view(n, row_ptr_dev, col_idx_dev, vals_dev, is_f32), amg_options(**options), _amg_setup(setup)
+        return cls._build("cvr_precond_amg_block", matrix._h, C.byref(view), C.byref(opt), int(setup), float(omega), int(nvec), None, matrix=matrix)
 
     def amg_block_info(self):
         """cvr_precond_amg_block_info: an AmgBlockInfo (nvec = K, setup, buffer_bytes); CvrError on an object built another way"""
-        info = AmgBlockInfo()
-        rc = lib().cvr_precond_amg_block_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_amg_block_info")
-        return info
+        return self._info("cvr_precond_amg_block_info", AmgBlockInfo)
 
     def amg_mis2_info(self):
         """cvr_precond_amg_mis2_info: an AmgMis2Info (mis2, the MIS rounds of every level); all zero of a kind-4 object built another way"""
-        info = AmgMis2Info()
-        rc = lib().cvr_precond_amg_mis2_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_amg_mis2_info")
-        return info
+        return self._info("cvr_precond_amg_mis2_info", AmgMis2Info)
 
     def amg_smoothed_info(self):
         """cvr_precond_amg_smoothed_info: an AmgSmoothedInfo (smoothed, omega, products_per_apply, p_nnz of every level); all zero of a plain object"""
-        info = AmgSmoothedInfo()
-        rc = lib().cvr_precond_amg_smoothed_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_amg_smoothed_info")
-        return info
+        return self._info("cvr_precond_amg_smoothed_info", AmgSmoothedInfo)
 
     def amg_export_prolongator(self, level):
         """cvr_precond_amg_export_prolongator: an AmgProlongator (row_ptr, col_idx, vals of P_l, n x nc) of level 0 .. levels - 2"""
         return _amg_export_prolongator(lib().cvr_precond_amg_export_prolongator, self._p, self.amg_info(), self.amg_smoothed_info(), level, self.dtype)
 
-    @classmethod
-    def _amg_from_view(cls, matrix, view, options, omega=None, mis2=False):
-        self = cls()
-        opt = amg_options(**options)
-        entry = "cvr_precond_amg" if omega is None else "cvr_precond_amg_mis2" if mis2 else "cvr_precond_amg_smoothed"
-        if omega is None:
-            rc = lib().cvr_precond_amg(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), None)
-        else:
-            rc = getattr(lib(), entry)(C.byref(self._p), matrix._h, C.byref(view), C.byref(opt), float(omega), None)
-        if rc:
-            self._p = C.c_void_p()
-            raise CvrError(rc, entry)
-        lib().cvr_precond_get_info(self._p, C.byref(self.info))
-        self.dtype = np.float32 if self.info.is_f32 else np.float64
-        self._matrix = matrix
-        return self
-
     def amg_info(self):
         """cvr_precond_amg_info: an AmgInfo (levels, coarse_direct, the options, operator_complexity, n and nnz of every level)"""
-        info = AmgInfo()
-        rc = lib().cvr_precond_amg_info(self._p, C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_precond_amg_info")
-        return info
+        return self._info("cvr_precond_amg_info", AmgInfo)
 
     def amg_export_level(self, level):
         """cvr_precond_amg_export_level: an AmgLevel (row_ptr, col_idx, vals, dinv, agg, winv) of level 0 .. levels - 1"""
@@ -1459,6 +1280,19 @@ class Precond:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def _which(which):
+    """EIG_LARGEST / EIG_SMALLEST of an eigensolver's `which`"""
+    try:
+        return {"LA": EIG_LARGEST, "SA": EIG_SMALLEST}[which]
+    except KeyError:
+        raise ValueError(f"which = {which!r}: must be 'LA' or 'SA'") from None
+
+
+def _returned_count(res, nev):
+    """how many pairs or triplets an EigResult / SvdResult stands for: nev, less at EIG_INVARIANT (nconv) and 0 at EIG_BREAKDOWN"""
+    return 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
 
 
 class CvrMatrix:
@@ -1652,25 +1486,35 @@ class CvrMatrix:
         opt.minv_dev = minv_ptr
         return opt
 
-    def _solve(self, symbol, opt, head, tail=()):
-        """one single-vector solver call: symbol(handle, *head, &opt, &res, *tail); returns the CgResult"""
+    def _solve(self, symbol, opt, head, tail=(), out=()):
+        """one single-vector solver call: symbol(handle, *head, &opt, &res, *&out, *tail) with the solver's further out-structs; returns the CgResult"""
         res = CgResult()
-        rc = getattr(lib(), symbol)(self._h, *head, C.byref(opt), C.byref(res), *tail)
+        rc = getattr(lib(), symbol)(self._h, *head, C.byref(opt), C.byref(res), *map(C.byref, out), *tail)
         if rc:
             raise CvrError(rc, symbol)
         return res
 
-    def _host_vectors(self, b, x0):
-        """a host solver's b, contiguous in the handle's type, and its x: x0 (None: zero) in a new array of at least one value"""
+    def _solve_multi(self, symbol, opt, nvec, head, tail=()):
+        """one batched solver call: symbol(handle, *head, &opt, res[nvec], *tail); returns the list of CgResult"""
+        res = (CgResult * max(int(nvec), 1))()
+        rc = getattr(lib(), symbol)(self._h, *head, C.byref(opt), res, *tail)
+        if rc:
+            raise CvrError(rc, symbol)
+        return list(res)
+
+    def _host_vectors(self, b, x0, x_len="nrows"):
+        """a host solver's b, contiguous in the handle's type, and its x: x0 (None: zero) in a new array of at least one value; x has nrows values,
+        or x_len = "ncols" of them"""
         b = np.ascontiguousarray(b, dtype=self.dtype)
         if len(b) < self.nrows:
             raise ValueError("b is shorter than nrows")
-        x = np.zeros(max(self.nrows, 1), dtype=self.dtype)
+        n = getattr(self, x_len)
+        x = np.zeros(max(n, 1), dtype=self.dtype)
         if x0 is not None:
             x0 = np.asarray(x0, dtype=self.dtype)
-            if len(x0) < self.nrows:
-                raise ValueError("x0 is shorter than nrows")
-            x[: self.nrows] = x0[: self.nrows]
+            if len(x0) < n:
+                raise ValueError(f"x0 is shorter than {x_len}")
+            x[:n] = x0[:n]
         return b, x
 
     def _gmres_options(self, name, options, minv):
@@ -1709,11 +1553,7 @@ class CvrMatrix:
         X_ptr are row-major device blocks of nrows rows of ldb / ldx values (X: the start block in, the solutions out), minv_ptr one
         preconditioner for all columns.  Column j is bit for bit cg()'s result for B[:, j] and X[:, j].  Needs a handle of the plain layout
         (nvec >= 2 at creation) unless nvec == ldb == ldx == 1.  Returns a list of nvec CgResult; synchronises the stream."""
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), (CgResult * max(int(nvec), 1))()
-        rc = lib().cvr_cg_multi_device(self._h, B_ptr, ldb, X_ptr, ldx, nvec, C.byref(opt), res, stream)
-        if rc:
-            raise CvrError(rc, "cvr_cg_multi_device")
-        return list(res)
+        return self._solve_multi("cvr_cg_multi_device", self._cg_options(rtol, max_iters, check_every, minv_ptr), nvec, (B_ptr, ldb, X_ptr, ldx, nvec), (stream,))
 
     def _host_blocks(self, B, X0):
         """a host block solver's B, contiguous in the handle's type with exactly nrows rows, and its X: X0 (None: zero) in a new array"""
@@ -1734,31 +1574,21 @@ class CvrMatrix:
         """the same through host arrays (cvr_cg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec); minv_ptr stays a
         device pointer.  Returns (X of shape (nrows, nvec), list of CgResult)."""
         B, X, k = self._host_blocks(B, X0)
-        opt, res = self._cg_options(rtol, max_iters, check_every, minv_ptr), (CgResult * max(k, 1))()
-        rc = lib().cvr_cg_multi(self._h, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)
-        if rc:
-            raise CvrError(rc, "cvr_cg_multi")
-        return X[: self.nrows], list(res)
+        res = self._solve_multi("cvr_cg_multi", self._cg_options(rtol, max_iters, check_every, minv_ptr), k, (B.ctypes.data, X.ctypes.data, k))
+        return X[: self.nrows], res
 
     def pcg_multi(self, precond, B_ptr, ldb, X_ptr, ldx, nvec, rtol=None, max_iters=None, check_every=0, stream=None):
         """cg_multi preconditioned by a Precond object (cvr_pcg_multi_device): Z = M^-1 R by its k-wide apply in place of a diagonal; the
         blocks and the list of nvec CgResult are cg_multi's.  Column j is bit for bit pcg()'s result for B[:, j] and X[:, j].  Takes block-Jacobi
         objects and, for nvec up to the width they were built for, Precond.amg_block's (one V-cycle per step for all columns)."""
-        opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(int(nvec), 1))()
-        rc = lib().cvr_pcg_multi_device(self._h, precond._p, B_ptr, ldb, X_ptr, ldx, nvec, C.byref(opt), res, stream)
-        if rc:
-            raise CvrError(rc, "cvr_pcg_multi_device")
-        return list(res)
+        return self._solve_multi("cvr_pcg_multi_device", self._cg_options(rtol, max_iters, check_every, None), nvec, (precond._p, B_ptr, ldb, X_ptr, ldx, nvec), (stream,))
 
     def pcg_multi_host(self, precond, B, X0=None, rtol=None, max_iters=None, check_every=0):
         """the same through host arrays (cvr_pcg_multi): B and the start block X0 (None: zero) of shape (nrows, nvec), for the objects pcg_multi
         takes.  Returns (X of shape (nrows, nvec), list of CgResult)."""
         B, X, k = self._host_blocks(B, X0)
-        opt, res = self._cg_options(rtol, max_iters, check_every, None), (CgResult * max(k, 1))()
-        rc = lib().cvr_pcg_multi(self._h, precond._p, B.ctypes.data, X.ctypes.data, k, C.byref(opt), res)
-        if rc:
-            raise CvrError(rc, "cvr_pcg_multi")
-        return X[: self.nrows], list(res)
+        res = self._solve_multi("cvr_pcg_multi", self._cg_options(rtol, max_iters, check_every, None), k, (precond._p, B.ctypes.data, X.ctypes.data, k))
+        return X[: self.nrows], res
 
     def bicgstab(self, b_ptr, x_ptr, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
         """solves A x = b for a nonsymmetric A by right-preconditioned BiCGSTAB on the device (cvr_bicgstab_device): the arguments and the
@@ -1788,70 +1618,45 @@ class CvrMatrix:
         """min ||b - A x||_2 (damp > 0: with the Tikhonov term damp^2 ||x - x0||^2) by LSQR on the device (cvr_lsqr_device) for A of any shape:
         `at` is a CvrMatrix of A^T (transpose=1 on the same CSR; self for a square symmetric A), b_ptr a device array of nrows values, x_ptr one
         of ncols values (the start vector in, the solution out).  Returns (CgResult, LsqrInfo); synchronises the stream."""
-        res, info = CgResult(), LsqrInfo()
-        opt = self._cg_options(rtol, max_iters, check_every, None)
-        rc = lib().cvr_lsqr_device(self._h, at._h, b_ptr, x_ptr, float(damp), C.byref(opt), C.byref(res), C.byref(info), stream)
-        if rc:
-            raise CvrError(rc, "cvr_lsqr_device")
+        info = LsqrInfo()
+        res = self._solve("cvr_lsqr_device", self._cg_options(rtol, max_iters, check_every, None), (at._h, b_ptr, x_ptr, float(damp)), (stream,), (info,))
         return res, info
 
     def lsqr_host(self, at, b, x0=None, damp=0.0, rtol=None, max_iters=None, check_every=0):
         """the same through host arrays (cvr_lsqr): b of nrows values and the start vector x0 (None: zero) of ncols values.  Returns
         (x, CgResult, LsqrInfo)."""
-        b = np.ascontiguousarray(b, dtype=self.dtype)
-        if len(b) < self.nrows:
-            raise ValueError("b is shorter than nrows")
-        x = np.zeros(max(self.ncols, 1), dtype=self.dtype)
-        if x0 is not None:
-            x0 = np.asarray(x0, dtype=self.dtype)
-            if len(x0) < self.ncols:
-                raise ValueError("x0 is shorter than ncols")
-            x[: self.ncols] = x0[: self.ncols]
-        res, info = CgResult(), LsqrInfo()
-        opt = self._cg_options(rtol, max_iters, check_every, None)
-        rc = lib().cvr_lsqr(self._h, at._h, b.ctypes.data, x.ctypes.data, float(damp), C.byref(opt), C.byref(res), C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_lsqr")
+        (b, x), info = self._host_vectors(b, x0, "ncols"), LsqrInfo()
+        res = self._solve("cvr_lsqr", self._cg_options(rtol, max_iters, check_every, None), (at._h, b.ctypes.data, x.ctypes.data, float(damp)), out=(info,))
         return x[: self.ncols], res, info
 
     def minres(self, b_ptr, x_ptr, shift=0.0, rtol=None, max_iters=None, check_every=0, minv_ptr=None, stream=None):
         """solves (A - shift I) x = b for a symmetric A, indefinite ones included, by MINRES on the device (cvr_minres_device): the arguments are
         cg's (minv_ptr: an optional positive diagonal preconditioner).  Returns (CgResult, MinresInfo); synchronises the stream."""
-        res, info = CgResult(), MinresInfo()
-        opt = self._cg_options(rtol, max_iters, check_every, minv_ptr)
-        rc = lib().cvr_minres_device(self._h, b_ptr, x_ptr, float(shift), C.byref(opt), C.byref(res), C.byref(info), stream)
-        if rc:
-            raise CvrError(rc, "cvr_minres_device")
+        info = MinresInfo()
+        res = self._solve("cvr_minres_device", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b_ptr, x_ptr, float(shift)), (stream,), (info,))
         return res, info
 
     def minres_host(self, b, x0=None, shift=0.0, rtol=None, max_iters=None, check_every=0, minv_ptr=None):
         """the same through host arrays (cvr_minres): b and the start vector x0 (None: zero) of nrows values; minv_ptr stays a device pointer.
         Returns (x, CgResult, MinresInfo)."""
-        b, x = self._host_vectors(b, x0)
-        res, info = CgResult(), MinresInfo()
-        opt = self._cg_options(rtol, max_iters, check_every, minv_ptr)
-        rc = lib().cvr_minres(self._h, b.ctypes.data, x.ctypes.data, float(shift), C.byref(opt), C.byref(res), C.byref(info))
-        if rc:
-            raise CvrError(rc, "cvr_minres")
+        (b, x), info = self._host_vectors(b, x0), MinresInfo()
+        res = self._solve("cvr_minres", self._cg_options(rtol, max_iters, check_every, minv_ptr), (b.ctypes.data, x.ctypes.data, float(shift)), out=(info,))
         return x[: self.nrows], res, info
 
     def _eig_options(self, nev, which, ncv, tol, max_restarts):
         opt = EigOptions()
         lib().cvr_eig_default_options(C.byref(opt))
-        try:
-            opt.which = {"LA": EIG_LARGEST, "SA": EIG_SMALLEST}[which]
-        except KeyError:
-            raise ValueError(f"which = {which!r}: must be 'LA' or 'SA'") from None
+        opt.which = _which(which)
         opt.nev, opt.ncv, opt.tol, opt.max_restarts = int(nev), int(ncv), float(tol), int(max_restarts)
         return opt
 
-    def _eig_start(self, v0):
-        """the start vector on the host: v0, or a seeded standard normal one"""
+    def _start_vector(self, v0, n, seed, what):
+        """a start vector of n values on the host: v0, or a standard normal one from `seed`; `what` names n in the error"""
         if v0 is None:
-            return np.random.default_rng(20261019).standard_normal(max(self.nrows, 1)).astype(self.dtype)
+            return np.random.default_rng(seed).standard_normal(max(n, 1)).astype(self.dtype)
         v0 = np.ascontiguousarray(v0, dtype=self.dtype)
-        if len(v0) < self.nrows:
-            raise ValueError("v0 is shorter than nrows")
+        if len(v0) < n:
+            raise ValueError(f"v0 is shorter than {what}")
         return v0
 
     def eigsh(self, nev, which="LA", ncv=0, tol=1e-8, v0=None, max_restarts=100, vectors=True, stream=None):
@@ -1863,7 +1668,7 @@ class CvrMatrix:
         opt, res = self._eig_options(nev, which, ncv, tol, max_restarts), EigResult()
         tdt = torch.float32 if self.dtype == np.float32 else torch.float64
         if v0 is None:
-            v0 = torch.from_numpy(self._eig_start(None)).to("cuda")
+            v0 = torch.from_numpy(self._start_vector(None, self.nrows, 20261019, "nrows")).to("cuda")
         n = max(self.nrows, 1)
         evals = np.zeros(max(int(nev), 1))
         evecs = torch.zeros((max(int(nev), 1), n), dtype=tdt, device="cuda") if vectors else None
@@ -1871,21 +1676,21 @@ class CvrMatrix:
         rc = lib().cvr_eigsh_device(self._h, v0.data_ptr(), evals.ctypes.data, None if evecs is None else evecs.data_ptr(), n, C.byref(opt), C.byref(res), stream)
         if rc:
             raise CvrError(rc, "cvr_eigsh_device")
-        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        count = _returned_count(res, nev)
         return evals[:count], (None if evecs is None else evecs[:count, : self.nrows]), res
 
     def eigsh_host(self, nev, which="LA", ncv=0, tol=1e-8, v0=None, max_restarts=100, vectors=True):
         """the same through host arrays (cvr_eigsh).  Returns (evals, evecs: numpy of shape (nrows, count) with the vector of evals[c] in column c, or
         None without vectors; EigResult)."""
         opt, res = self._eig_options(nev, which, ncv, tol, max_restarts), EigResult()
-        v0 = self._eig_start(v0)
+        v0 = self._start_vector(v0, self.nrows, 20261019, "nrows")
         n = max(self.nrows, 1)
         evals = np.zeros(max(int(nev), 1))
         evecs = np.zeros((max(int(nev), 1), n), dtype=self.dtype) if vectors else None
         rc = lib().cvr_eigsh(self._h, v0.ctypes.data, evals.ctypes.data, None if evecs is None else evecs.ctypes.data, n, C.byref(opt), C.byref(res))
         if rc:
             raise CvrError(rc, "cvr_eigsh")
-        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        count = _returned_count(res, nev)
         return evals[:count], (None if evecs is None else evecs[:count, : self.nrows].T), res
 
     def _svd_options(self, nev, ncv, tol, max_restarts):
@@ -1893,15 +1698,6 @@ class CvrMatrix:
         lib().cvr_svd_default_options(C.byref(opt))
         opt.nev, opt.ncv, opt.tol, opt.max_restarts = int(nev), int(ncv), float(tol), int(max_restarts)
         return opt
-
-    def _svd_start(self, v0):
-        """the start vector on the host: v0, or a seeded standard normal one, of ncols values"""
-        if v0 is None:
-            return np.random.default_rng(20261021).standard_normal(max(self.ncols, 1)).astype(self.dtype)
-        v0 = np.ascontiguousarray(v0, dtype=self.dtype)
-        if len(v0) < self.ncols:
-            raise ValueError("v0 is shorter than ncols")
-        return v0
 
     def svds(self, at, v0=None, nev=1, ncv=0, tol=1e-8, max_restarts=100, vectors=True, stream=None):
         """the nev largest singular values of A, of any shape, and their vectors by thick-restart Golub-Kahan-Lanczos on the device (cvr_svds_device).
@@ -1913,7 +1709,7 @@ class CvrMatrix:
         opt, res = self._svd_options(nev, ncv, tol, max_restarts), SvdResult()
         tdt = torch.float32 if self.dtype == np.float32 else torch.float64
         if v0 is None:
-            v0 = torch.from_numpy(self._svd_start(None)).to("cuda")
+            v0 = torch.from_numpy(self._start_vector(None, self.ncols, 20261021, "ncols")).to("cuda")
         nr, nc, cols = max(self.nrows, 1), max(self.ncols, 1), max(int(nev), 1)
         svals = np.zeros(cols)
         U = torch.zeros((cols, nr), dtype=tdt, device="cuda") if vectors else None
@@ -1923,14 +1719,14 @@ class CvrMatrix:
                                    None if V is None else V.data_ptr(), nc, C.byref(opt), C.byref(res), stream)
         if rc:
             raise CvrError(rc, "cvr_svds_device")
-        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        count = _returned_count(res, nev)
         return svals[:count], (None if U is None else U[:count, : self.nrows]), (None if V is None else V[:count, : self.ncols]), res
 
     def svds_host(self, at, v0=None, nev=1, ncv=0, tol=1e-8, max_restarts=100, vectors=True):
         """the same through host arrays (cvr_svds).  Returns (svals; U: numpy of shape (nrows, count) with the left vector of svals[c] in column c; V:
         the same of shape (ncols, count); both None without vectors; SvdResult)."""
         opt, res = self._svd_options(nev, ncv, tol, max_restarts), SvdResult()
-        v0 = self._svd_start(v0)
+        v0 = self._start_vector(v0, self.ncols, 20261021, "ncols")
         nr, nc, cols = max(self.nrows, 1), max(self.ncols, 1), max(int(nev), 1)
         svals = np.zeros(cols)
         U = np.zeros((cols, nr), dtype=self.dtype) if vectors else None
@@ -1939,16 +1735,13 @@ class CvrMatrix:
                             None if V is None else V.ctypes.data, nc, C.byref(opt), C.byref(res))
         if rc:
             raise CvrError(rc, "cvr_svds")
-        count = 0 if res.status == EIG_BREAKDOWN else res.nconv if res.status == EIG_INVARIANT else int(nev)
+        count = _returned_count(res, nev)
         return svals[:count], (None if U is None else U[:count, : self.nrows].T), (None if V is None else V[:count, : self.ncols].T), res
 
     def _lobpcg_options(self, nev, which, tol, max_iters):
         opt = LobpcgOptions()
         lib().cvr_lobpcg_default_options(C.byref(opt))
-        try:
-            opt.which = {"LA": EIG_LARGEST, "SA": EIG_SMALLEST}[which]
-        except KeyError:
-            raise ValueError(f"which = {which!r}: must be 'LA' or 'SA'") from None
+        opt.which = _which(which)
         opt.nev, opt.tol, opt.max_iters = int(nev), float(tol), int(max_iters)
         return opt
 
